@@ -2,7 +2,8 @@
 """
 bench.py -- IRs/sec of the metrics-only full report (BASELINE.json metric) on MI355X, and the other BASELINE configs.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config report|2|3|4|5] [--batch B] [--seconds S]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config report|2|3|4|5] [--batch B] [--seconds S] [--full]
+                    [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -20,8 +21,16 @@ stream under the kernels of batch k (audio_analysis_amd.feed).  Weak scaling: B 
   --config 5   bundle: stereo 5 s PCM16 taps from files through bundle.run_bundle_metrics (native ingest, int16 upload,
                full pipeline), 128 taps per step
 
+  --full       every field of the line below past "ms_per_step": without it a run sets up, warms up (the upload autotune
+               included), times the --steps steps and prints the headline fields (metric, value, unit, higher_is_better,
+               dtype, ms_per_step, the configuration and the upload method)
+  --dump-outputs DIR   after the timed steps: the metric records of the last timed step -> DIR/metrics.npy (float64,
+               non-finite fields as 0.0) + DIR/metrics_nonfinite.npy (what stood there: 0 finite, 1 NaN, 2 +inf, 3 -inf)
+
 Rank 0 prints ONE JSON line:
   "value"           H2D-inclusive throughput, float32 upload (what section 8d defines)
+  "ms_per_step"     wall milliseconds of one timed step
+  -- with --full:
   "value_int16"     the same with 2-byte PCM16 upload + device conversion (what a tap bundle delivers)
   "value_resident"  inputs already in HBM (still rotating over the distinct batches): the compute-only rate
   "value_pull_kernel" the same steps with the batch moved by ira_host_pull instead of hipMemcpyAsync (A/B)
@@ -700,6 +709,45 @@ def note(msg):
         print(f"[bench {time.strftime('%H:%M:%S')}] {msg}", file=sys.stderr, flush=True)
 
 
+def check_records(gathered, rows_per_step: int, steps: int):
+    """Rank 0's gathered records of the timed region: every step's rows are there and every channel reported status ok."""
+    import numpy as np
+    from audio_analysis_amd.pipeline import METRICS_WIDTH
+    rows = rows_per_step * steps
+    assert gathered is not None and gathered.shape == (rows, METRICS_WIDTH), (None if gathered is None else gathered.shape, rows)
+    assert np.all(gathered[:, 0] == 0.0), "a channel of the timed region did not report status ok"
+
+
+def dump_outputs(path: str, gathered, world: int, rows_per_rank_step: int) -> None:
+    """--dump-outputs: the metric records the timed path returned in its LAST step (float64, one row per channel, every
+    rank's rows in rank order) -> path/metrics.npy.  The inputs are seeded by generator index, so the same arguments give
+    the same inputs in every run.  `gathered` holds either every step's rows (rank-major: rank, step, row) or the last
+    step's alone (--gather step).
+    A record marks a field it does not hold (a block that is off, a band slot past the bank, a fit whose range the decay
+    never reaches) with NaN.  Both files are finite and together lossless: metrics.npy has 0.0 where the record is not
+    finite, metrics_nonfinite.npy (float32, same shape) says what stood there: 0 a finite value, 1 NaN, 2 +inf, 3 -inf."""
+    import numpy as np
+    rec = np.asarray(gathered, dtype=np.float64)
+    steps = rec.shape[0] // (world * rows_per_rank_step)
+    assert steps >= 1 and rec.shape[0] == world * steps * rows_per_rank_step, (rec.shape, world, rows_per_rank_step)
+    rec = rec.reshape(world, steps, rows_per_rank_step, rec.shape[1])[:, -1].reshape(world * rows_per_rank_step, -1)
+    code = np.zeros(rec.shape, dtype=np.float32)
+    code[np.isnan(rec)] = 1.0
+    code[np.isposinf(rec)] = 2.0
+    code[np.isneginf(rec)] = 3.0
+    values = np.where(np.isfinite(rec), rec, 0.0)
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "metrics.npy"), np.ascontiguousarray(values))
+    np.save(os.path.join(path, "metrics_nonfinite.npy"), code)
+    note(f"outputs of the last timed step: {path}/metrics.npy {values.shape} (+ metrics_nonfinite.npy, "
+         f"{int(np.count_nonzero(code))} non-finite fields)")
+
+
+def upload_mode(feed) -> str:
+    return ("pull kernel (ira_host_pull reads pinned host memory over PCIe)" if feed.pull else
+            f"hipMemcpyAsync, {len(feed.side_streams) + 1} piece(s) on as many copy streams")
+
+
 def spawn_ranks(n: int) -> int:
     """`python bench.py --gpus N` outside a torchrun environment: start the N rank processes ourselves (one per GPU, fresh
     interpreters started BEFORE this process has imported torch or touched a GPU; never an exec), hand them the
@@ -767,7 +815,18 @@ def main():
     ap.add_argument("--spawn-probe", action="store_true",
                     help="launch check without a GPU: every rank joins a gloo group, rank 0 prints the ranks it gathered "
                          "(tests/test_host_cpu.py runs `bench.py --gpus 2 --spawn-probe`)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: int16 / resident / pull-kernel / new-lengths variants, the "
+                         "serialised pass (per-call device times, rooflines), the literal report, the STFT error probe, "
+                         "the cpu baseline and its parity sample.  Without it a run sets up, warms up, times --steps "
+                         "steps and prints the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the metric records of the last timed step (what the report "
+                         "returns, float64, every rank's rows in rank order) to DIR/metrics.npy, its NaN / inf fields "
+                         "as 0.0 and recorded in DIR/metrics_nonfinite.npy")
     a = ap.parse_args()
+    if a.steps is not None and a.steps < 1:
+        ap.error("--steps must be at least 1")
     a.roofline_steps = max(1, a.roofline_steps)      # the bench line needs the serialised pass (roofline, per-call times)
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(a.gpus))
@@ -804,7 +863,7 @@ def main():
 
     from audio_analysis_amd.engine import Engine
     from audio_analysis_amd.feed import DeviceFeed, HostBatch, run_pipelined
-    from audio_analysis_amd.pipeline import METRICS_WIDTH, FullReport
+    from audio_analysis_amd.pipeline import FullReport
     from audio_analysis_amd.synth import synth_ir
 
     cfg = config_table()[a.config]
@@ -818,7 +877,7 @@ def main():
                    cpu_s=cfg["cpu_s"] + 4.0 * ((a.ar_order / 64.0) ** 2 - 1.0) * (settings.run_zplane))
     B = a.batch or cfg["batch"]
     seconds = a.seconds or cfg["seconds"]
-    steps = a.steps or cfg["steps"]
+    steps = a.steps if a.steps is not None else cfg["steps"]
     n = int(seconds * 48000)
 
     rank, local_rank, world = D.init_process_group()
@@ -839,9 +898,9 @@ def main():
     for c in my_cpus:
         if c < 208:
             aff_row[0, 4 + c // 52] += float(1 << (c % 52))           # 52-bit pieces: exact in a float64
-    aff_all = D.gather_metrics(aff_row, eng.device, equal_rows=True)
+    aff_all = D.gather_metrics(aff_row, eng.device, equal_rows=True) if a.full else None
     affinity = None
-    if rank == 0:
+    if a.full and rank == 0:
         ranks = []
         for r in aff_all:
             cpus = [52 * j + b for j in range(4) for b in range(52) if (int(r[4 + j]) >> b) & 1]
@@ -861,7 +920,7 @@ def main():
         chans = list(ex.map(lambda i: synth_ir(first + i, 0, n), range(K * B)))
     host_f32 = [HostBatch(eng, np.stack(chans[k * B : (k + 1) * B])) for k in range(K)]
     host_i16 = None
-    if a.variants == "all":
+    if a.full and a.variants == "all":
         host_i16 = [HostBatch(eng, (np.stack(chans[k * B : (k + 1) * B]) * np.float32(32767.0)).astype(np.int16), pcm16=True)
                     for k in range(K)]
     del chans
@@ -906,11 +965,14 @@ def main():
     run_fed(a.warmup, host_f32)
     D.barrier(); torch.cuda.synchronize()
     # the link alone: three uploads of a batch with nothing else on the GPU, HIP events on the copy streams (DeviceFeed.timing)
-    feed.timing = []
-    for k in range(3):
-        feed.push(host_f32[k % K])
-        torch.cuda.synchronize()
-    upload_alone = feed.upload_times()
+    # (the autotune's yardstick; a plain run without the autotune has no use for it)
+    upload_alone = None
+    if a.full or a.upload == "auto":
+        feed.timing = []
+        for k in range(3):
+            feed.push(host_f32[k % K])
+            torch.cuda.synchronize()
+        upload_alone = feed.upload_times()
     upload_tuning = None
     if a.upload == "auto":
         def tune_steps(c):
@@ -926,8 +988,9 @@ def main():
         note("upload: " + "; ".join(f"{r['mode']} {r['ms_per_step']:.2f} ms/step" + (" (chosen)" if r["chosen"] else "") for r in upload_tuning))
         flush()
         D.barrier(); torch.cuda.synchronize()
-    eng.events = []
-    feed.timing = []                                   # ... and under the kernels of the timed region
+    # per-call events in the timed region and on its copy streams feed --full's figures only: a plain run records none
+    eng.events = [] if a.full else None
+    feed.timing = [] if a.full else None               # ... and under the kernels of the timed region
     elapsed = timed(lambda c: run_fed(c, host_f32), steps)
     upload_timed = feed.upload_times()
     feed.timing = None
@@ -935,6 +998,45 @@ def main():
     eng.events = None
     gathered = last.get("g")
     note(f"timed region: {steps} steps in {elapsed:.3f} s = {B * world * steps / elapsed:.0f} IRs/s")
+    total_irs = B * world * steps
+    head = {
+        "metric": cfg["metric"],
+        "value": total_irs / elapsed,
+        "unit": "IRs/s",
+        "n_gpus": world,
+        "steps": steps,
+        "warmup": a.warmup,
+        "ms_per_step": 1e3 * elapsed / steps,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f64",
+        "data": "synthetic",
+        "config": {
+            "workload": f"{cfg['what']} on {B} mono synthetic IRs per GPU per step, {seconds:g} s @ 48 kHz (SURVEY.md 8d "
+                        f"generator), H2D included: every step uploads its batch from pinned host memory (float32, "
+                        f"{B * n * 4 / 1e6:.0f} MB) on a copy stream under the previous step's kernels; {K} distinct "
+                        f"batches rotate",
+            "baseline_config": a.config,
+            "blocks": settings.blocks(),
+            "excluded": cfg["excluded"],
+            "batch_per_gpu": B, "ir_seconds": seconds, "parallelism": f"file-sharded dp{world}",
+            "arithmetic": "f64 (EDC scan, long FFTs, modal/waterfall STFT, AR Gram/solve/roots); "
+                          "f32 butterflies for the spectrogram STFT",
+            "timed_region": "H2D + peak pick + all kernels + metric pack + D2H of records + "
+                            + ("ONE gather of every step's records to rank 0 after the last step" if a.gather == "final"
+                               else "a gather to rank 0 per step"),
+            "gather": a.gather,
+        },
+    }
+    if rank == 0:
+        check_records(gathered, B * world, steps if a.gather == "final" else 1)
+        if a.dump_outputs:
+            dump_outputs(a.dump_outputs, gathered, world, B)
+    if not a.full:
+        if rank == 0:
+            print(json.dumps(dict(head, upload=upload_mode(feed), upload_autotune=upload_tuning, full=False)))
+        return
 
     el_pull = None
     if a.variants == "all" and a.upload != "pull" and not feed.pull:
@@ -1038,10 +1140,6 @@ def main():
 
     if rank != 0:
         return
-    rows = B * world * (steps if a.gather == "final" else 1)
-    assert gathered is not None and gathered.shape == (rows, METRICS_WIDTH), (None if gathered is None else gathered.shape, rows)
-    assert np.all(gathered[:, 0] == 0.0), "a channel of the timed region did not report status ok"
-    total_irs = B * world * steps
     # trimmed lengths of the batch the serialised pass saw last (synthetic pre-delays are 240 + i mod 512)
     pre = np.array([240 + ((first + i) % 512) for i in range(B)], dtype=np.float64)
     L = n - pre
@@ -1055,40 +1153,13 @@ def main():
     if rs is not None and stft_err is not None:
         rs["f32_error"] = stft_err
     out = {
-        "metric": cfg["metric"],
-        "value": total_irs / elapsed,
-        "unit": "IRs/s",
-        "n_gpus": world,
-        "steps": steps,
-        "warmup": a.warmup,
-        "ms_per_step": 1e3 * elapsed / steps,
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "f64",
-        "data": "synthetic",
-        "config": {
-            "workload": f"{cfg['what']} on {B} mono synthetic IRs per GPU per step, {seconds:g} s @ 48 kHz (SURVEY.md 8d "
-                        f"generator), H2D included: every step uploads its batch from pinned host memory (float32, "
-                        f"{B * n * 4 / 1e6:.0f} MB) on a copy stream under the previous step's kernels; {K} distinct "
-                        f"batches rotate",
-            "baseline_config": a.config,
-            "blocks": settings.blocks(),
-            "excluded": cfg["excluded"],
-            "batch_per_gpu": B, "ir_seconds": seconds, "parallelism": f"file-sharded dp{world}",
-            "arithmetic": "f64 (EDC scan, long FFTs, modal/waterfall STFT, AR Gram/solve/roots); "
-                          "f32 butterflies for the spectrogram STFT",
-            "timed_region": "H2D + peak pick + all kernels + metric pack + D2H of records + "
-                            + ("ONE gather of every step's records to rank 0 after the last step" if a.gather == "final"
-                               else "a gather to rank 0 per step"),
-            "gather": a.gather,
-        },
+        **head,
+        "full": True,
         "steps_in_process": counters["steps"],
         "value_int16": None if el_i16 is None else total_irs / el_i16,
         "value_resident": None if el_res is None else total_irs / el_res,
         "value_pull_kernel": None if el_pull is None else total_irs / el_pull,
-        "upload": "pull kernel (ira_host_pull reads pinned host memory over PCIe)" if feed.pull else
-                  f"hipMemcpyAsync, {len(feed.side_streams) + 1} piece(s) on as many copy streams",
+        "upload": upload_mode(feed),
         "upload_autotune": upload_tuning,
         "variants": {"value": "float32 upload inside the timed region (SURVEY.md 8d)",
                      "value_int16": "PCM16 upload (2 B/sample) + device conversion inside the timed region",
@@ -1216,8 +1287,9 @@ def bench_bundle(a, cfg, eng, rank, world, B, n, steps, blocks, affinity=None, c
 
         run(os.path.join(base, "warm"))
         D.barrier(); torch.cuda.synchronize()
-        eng.events = []
-        os.environ["IRA_BUNDLE_TIMING"] = "1"          # host milliseconds per phase of the loop (a dozen clock reads per group)
+        if a.full:                                     # per-call events and host phases of the timed region: --full only
+            eng.events = []
+            os.environ["IRA_BUNDLE_TIMING"] = "1"      # host milliseconds per phase of the loop (a dozen clock reads per group)
         t0 = time.perf_counter()
         labels, local = run(os.path.join(base, "timed"))
         gathered = D.gather_metrics(local, eng.device)
@@ -1228,6 +1300,25 @@ def bench_bundle(a, cfg, eng, rank, world, B, n, steps, blocks, affinity=None, c
         host_phases = _bundle.LAST_HOST_MS_PER_GROUP
         ev_timed = eng.collect_events()
         eng.events = None
+        head = {
+            "metric": cfg["metric"], "value": B * steps * world / elapsed, "unit": "stereo taps/s", "n_gpus": world,
+            "steps": steps, "warmup": a.warmup, "ms_per_step": 1e3 * elapsed / steps, "higher_is_better": True,
+            "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+            "config": {"workload": f"{cfg['what']}; {B} stereo taps of {n / 48000:g} s per step per GPU read from files on "
+                                   f"tmpfs (page-cache resident), {2 * B} channels per step; H2D (int16) included",
+                       "baseline_config": "5", "blocks": settings.blocks(), "excluded": cfg["excluded"],
+                       "batch_per_gpu": B, "ir_seconds": n / 48000, "parallelism": f"file-sharded dp{world}",
+                       "timed_region": "file reads + H2D (int16) + device conversion + peak pick + all kernels + metric pack + "
+                                       "D2H + gather"},
+        }
+        if rank == 0:
+            assert gathered.shape == (2 * B * steps * world, METRICS_WIDTH)
+            if a.dump_outputs:
+                dump_outputs(a.dump_outputs, gathered, world, 2 * B)
+        if not a.full:
+            if rank == 0:
+                print(json.dumps(dict(head, full=False)))
+            return
         # serialised pass for the per-call durations
         lanes_used = eng.num_lanes
         eng.num_lanes = 1
@@ -1241,7 +1332,6 @@ def bench_bundle(a, cfg, eng, rank, world, B, n, steps, blocks, affinity=None, c
         shutil.rmtree(base, ignore_errors=True)
     if rank != 0:
         return
-    assert gathered.shape == (2 * B * steps * world, METRICS_WIDTH)
     pre = np.repeat(np.array([240 + ((100000 + i) % 512) for i in range(B)], dtype=np.float64), 2)
     L = n - pre
     traffic_tab = load_traffic("5")
@@ -1250,15 +1340,8 @@ def bench_bundle(a, cfg, eng, rank, world, B, n, steps, blocks, affinity=None, c
     dominant = max(analysis, key=analysis.get)
     files = B * steps * world
     out = {
-        "metric": cfg["metric"], "value": files / elapsed, "unit": "stereo taps/s", "n_gpus": world, "steps": steps,
-        "warmup": a.warmup, "ms_per_step": 1e3 * elapsed / steps, "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-        "config": {"workload": f"{cfg['what']}; {B} stereo taps of {n / 48000:g} s per step per GPU read from files on "
-                               f"tmpfs (page-cache resident), {2 * B} channels per step; H2D (int16) included",
-                   "baseline_config": "5", "blocks": settings.blocks(), "excluded": cfg["excluded"],
-                   "batch_per_gpu": B, "ir_seconds": n / 48000, "parallelism": f"file-sharded dp{world}",
-                   "timed_region": "file reads + H2D (int16) + device conversion + peak pick + all kernels + metric pack + "
-                                   "D2H + gather"},
+        **head,
+        "full": True,
         "channels_per_s": 2 * files / elapsed,
         "roofline": roof(dominant),
         "roofline_kernel": roofline_kernel("5", tot, roof, dict(channels=2 * B, n=n, bands=nb_bands(settings),

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Side by side: per-call device times (serialised pass) of two or more bench lines.  usage: cmp_bench.py a.json b.json ..."""
+"""Side by side: per-call device times (serialised pass) of two or more `bench.py --full` lines.  usage: cmp_bench.py a.json b.json ..."""
 import json, sys
 lines = [json.loads(open(f).read().strip().splitlines()[-1]) for f in sys.argv[1:]]
 print("value            ", *[f"{d['value']:10.0f}" for d in lines])

@@ -3,7 +3,7 @@
 # (kernel stats + FETCH/WRITE/RDREQ counters) of the four single-GPU configurations.
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r2_final; mkdir -p $O
 for c in report 2 3 4 5; do
-  timeout -k 10 400 python3 $R/bench.py --config $c > $O/bench_cfg$c.json 2> $O/bench_cfg$c.err || echo "bench $c failed" >> $O/fail.log
+  timeout -k 10 400 python3 $R/bench.py --config $c --full > $O/bench_cfg$c.json 2> $O/bench_cfg$c.err || echo "bench $c failed" >> $O/fail.log
   grep "timed region" $O/bench_cfg$c.err
 done
 for c in report 2 3 4; do

@@ -5,7 +5,7 @@ R=$GRAFT_REPO_ROOT; tag=$1; shift; O=$R/gpurun_out/$tag; mkdir -p $O
 for a in "$@"; do
   case $a in
     test)   timeout -k 10 900 python3 -m pytest $R/tests -m gpu -x -q > $O/gputest.log 2>&1; rc=$?; tail -3 $O/gputest.log; [ $rc -ne 0 ] && exit $rc ;;
-    bench:*) c=${a#bench:}; timeout -k 10 400 python3 $R/bench.py --config $c > $O/bench_cfg$c.json 2> $O/bench_cfg$c.err || { echo "bench $c failed"; tail -5 $O/bench_cfg$c.err; exit 1; }
+    bench:*) c=${a#bench:}; timeout -k 10 400 python3 $R/bench.py --config $c --full > $O/bench_cfg$c.json 2> $O/bench_cfg$c.err || { echo "bench $c failed"; tail -5 $O/bench_cfg$c.err; exit 1; }
              python3 - $O/bench_cfg$c.json <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -6,7 +6,7 @@ R=$GRAFT_REPO_ROOT; O=$R/${1:-gpurun_out/r4_sparse_q}; mkdir -p $O; shift
 export IRA_TUNING=1 IRA_LIBRARY=$R/audio_analysis_amd/csrc/libira_tuning.so
 for q in ${@:-0 1 2 4 6 9 12 14}; do
   export IRA_SPARSE_Q=$q
-  timeout -k 10 200 python3 $R/bench.py --config 3 --steps 6 --warmup 2 --no-cpu-baseline --variants value > $O/q$q.json 2> $O/q$q.err || { echo "q $q failed" >> $O/summary.txt; break; }
+  timeout -k 10 200 python3 $R/bench.py --config 3 --steps 6 --warmup 2 --no-cpu-baseline --variants value --full > $O/q$q.json 2> $O/q$q.err || { echo "q $q failed" >> $O/summary.txt; break; }
   python3 - $O/q$q.json $q >> $O/summary.txt <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))

@@ -5,7 +5,7 @@ R=$GRAFT_REPO_ROOT; O=$R/${1:-gpurun_out/r5_upload}; reps=${2:-2}; mkdir -p $O
 for rep in $(seq $reps); do
   for arm in "2" "4" "8" "1" "2 --upload-priority" "4 --upload-priority" "2 --upload pull"; do
     tag=$(echo $arm | tr -d ' -'); f=$O/s${tag}_$rep
-    timeout -k 10 300 python3 $R/bench.py --steps 20 --warmup 3 --no-cpu-baseline --variants resident --literal-steps 0 --roofline-steps 1 --upload-streams $arm > $f.json 2> $f.err || echo "failed $arm $rep"
+    timeout -k 10 300 python3 $R/bench.py --steps 20 --warmup 3 --no-cpu-baseline --variants resident --literal-steps 0 --roofline-steps 1 --upload-streams $arm --full > $f.json 2> $f.err || echo "failed $arm $rep"
     python3 - $f.json "$arm" $rep <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))

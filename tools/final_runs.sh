@@ -8,7 +8,7 @@ R=$GRAFT_REPO_ROOT; tag=${1:-r05}; what=${2:-bench}; shift 2
 O=$R/gpurun_out/${tag}_final; mkdir -p $O
 if [ "$what" = bench ]; then
   for c in ${@:-report literal 2 3 4 5}; do
-    timeout -k 10 500 python3 $R/bench.py --config $c > $O/bench_cfg$c.json 2> $O/bench_cfg$c.err || echo "bench $c failed" >> $O/fail.log
+    timeout -k 10 500 python3 $R/bench.py --config $c --full > $O/bench_cfg$c.json 2> $O/bench_cfg$c.err || echo "bench $c failed" >> $O/fail.log
     grep "timed region" $O/bench_cfg$c.err
   done
 else
