@@ -13,7 +13,7 @@ _LIB_PATH = Path(__file__).resolve().parent / "csrc" / "libira.so"
 _lib = None
 # must equal IRA_ABI_VERSION of include/ira.h: a stale .so called with this file's prototypes would read shifted
 # arguments or undersized scratch (memory corruption on the GPU instead of a clean error)
-ABI_VERSION = 8
+ABI_VERSION = 9
 
 c_f32p = C.c_void_p
 c_i64p = C.c_void_p
@@ -77,6 +77,9 @@ PROTOTYPES = {
     "ira_ar_fit": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, f64, vp, vp, vp, vp, i32, vp]),
     "ira_poly_roots": (i32, [vp, i32, i32, f64, vp, vp, vp]),
     "ira_fir_numerator": (i32, [vp, i32, vp, vp, vp, vp, i32, i32, vp, vp]),
+    "ira_onset_index": (i32, [vp, vp, vp, i32, C.c_int64, vp, vp, f64, vp, vp]),
+    "ira_energy_scratch_doubles": (C.c_int64, [i32, C.c_int64, i32]),
+    "ira_energy_windows": (i32, [vp, vp, vp, vp, vp, i32, C.c_int64, vp, i32, vp, vp, vp]),
 }
 
 

@@ -40,6 +40,8 @@ SOURCES = {
     "ira_deconv.hip": ["-ffp-contract=off"],
     # float32 arithmetic of the reference is reproduced operation by operation: no FMA contraction
     "ira_diffusion.hip": ["-ffp-contract=off"],
+    # float64 energy products and sums round one operation at a time, like NumPy's
+    "ira_energy.hip": ["-ffp-contract=off"],
 }
 COMMON = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function"]
 

@@ -1,0 +1,269 @@
+// ISO 3382-1 energy-ratio parameters (clarity C_k, definition D, centre time Ts): onset search and windowed float64
+// energy sums.  Nothing in the reference computes these; the host side is audio_analysis_amd/analyse/energy.py.
+// Compiled with -ffp-contract=off: the float64 products and sums must round one operation at a time, like NumPy's.
+#include "ira_common.h"
+
+namespace {
+
+// ------------------------------------------------------------------------------------------------
+// Onset (ISO 3382-1 A.3.4): o = smallest n <= p with float64(x[n])^2 >= float64(x[p])^2 * rel_energy, p = the peak
+// index ira_peak_index left on the device.  Chunks of ON_CHUNK samples x segments; chunks that start after p exit at
+// once.  A chunk's first hit goes to the segment's slot by atomicMin (the pattern of crossing_search_kernel in
+// ira_edc.hip); onset_init_kernel seeds every slot with p, which always satisfies the test for a finite peak.
+// ------------------------------------------------------------------------------------------------
+constexpr int ON_THREADS = 256;
+constexpr int ON_PER_THREAD = 16;
+constexpr int ON_CHUNK = ON_THREADS * ON_PER_THREAD;
+
+__global__ void onset_init_kernel(const int64_t* __restrict__ peak, int nseg, int64_t* __restrict__ onset) {
+  const int s = blockIdx.x * blockDim.x + threadIdx.x;
+  if (s < nseg) onset[s] = peak[s];
+}
+
+__global__ __launch_bounds__(ON_THREADS) void onset_search_kernel(const float* __restrict__ x,
+                                                                  const int64_t* __restrict__ off,
+                                                                  const int64_t* __restrict__ len,
+                                                                  const int64_t* __restrict__ peak,
+                                                                  const float* __restrict__ peak_abs, double rel_energy,
+                                                                  int64_t* __restrict__ onset) {
+  const int s = blockIdx.y;
+  const int64_t p = ira::uniform(peak[s]);
+  const int64_t c0 = (int64_t)blockIdx.x * ON_CHUNK;
+  if (c0 > p || ira::uniform(len[s]) <= 0) return;
+  const double a = (double)ira::uniform(peak_abs[s]);
+  const double thr = (a * a) * rel_energy;
+  const float* q = x + ira::uniform(off[s]);
+  const int tid = threadIdx.x;
+  float v[ON_PER_THREAD];
+#pragma unroll
+  for (int u = 0; u < ON_PER_THREAD; ++u) {
+    const int64_t i = c0 + tid + (int64_t)ON_THREADS * u;
+    v[u] = i <= p ? q[i] : 0.0f;
+  }
+  int64_t first = INT64_MAX;
+#pragma unroll
+  for (int u = ON_PER_THREAD - 1; u >= 0; --u) {      // descending: the smallest index wins without a compare
+    const int64_t i = c0 + tid + (int64_t)ON_THREADS * u;
+    const double d = (double)v[u];
+    if (i <= p && d * d >= thr) first = i;
+  }
+  if (__any(first != INT64_MAX)) {                    // wave-uniform
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const int64_t other = __shfl_xor(first, o, 64);
+      first = other < first ? other : first;
+    }
+    if ((tid & 63) == 0) atomicMin(reinterpret_cast<unsigned long long*>(&onset[s]), (unsigned long long)first);
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Windowed energy sums.  Segment j is base_off[j] + onset[chan_of_seg[j]] .. base_off[j] + base_len[j]; n is counted
+// from its first sample.  With the segment's limits N_1 < ... < N_K:
+//   P_0 = sum e[0, N_1), ..., P_K = sum e[N_K, L),  S1 = sum n e[n],  e = float64(x)^2.
+//   energy_partial_kernel (chunks x segments)  one EW_CHUNK-sample chunk per workgroup -> one record of K + 2 doubles
+//   energy_fold_kernel    (1 wave / segment)   the records folded in a fixed order -> out
+// Every chunk boundary, every thread's share of a chunk and every reduction tree is a function of the segment's own length
+// only: a segment's result does not depend on the batch, its place in it or the alignment of its first sample (the loads
+// are 16-byte loads at 4-byte alignment, like tile_load in ira_edc.hip, so the order of the sums never changes with the
+// address).  Only a chunk that straddles a limit tests per sample which partition a sample falls in; every other chunk
+// lies in one partition and forms one sum.
+// ------------------------------------------------------------------------------------------------
+constexpr int EW_THREADS = 256;
+constexpr int EW_QUADS = 16;                                  // 16-byte loads per thread per chunk, all in flight together
+constexpr int EW_CHUNK = EW_THREADS * 4 * EW_QUADS;           // 16384 samples
+constexpr int EW_WAVES = EW_THREADS / IRA_WAVE;
+constexpr int EW_MAX_LIMITS = 4;
+constexpr int EW_MAX_REC = EW_MAX_LIMITS + 2;                 // P_0 .. P_K, S1
+constexpr int64_t EW_MAX_LEN = (int64_t)1 << 31;
+
+typedef float ew_f4 __attribute__((ext_vector_type(4), aligned(4)));   // 16-byte access, 4-byte alignment
+
+// The thread's samples of a chunk of cnt valid samples, quad u = local samples 4 (tid + 256 u) .. + 3 (zeros past cnt).
+template <bool FULL>
+__device__ __forceinline__ void ew_load(const float* __restrict__ q, int cnt, ew_f4 a[EW_QUADS]) {
+#pragma unroll
+  for (int u = 0; u < EW_QUADS; ++u) {
+    const int b = 4 * (threadIdx.x + EW_THREADS * u);
+    if (FULL || b + 4 <= cnt) {
+      a[u] = *reinterpret_cast<const ew_f4*>(q + b);
+    } else {
+      a[u] = ew_f4{0.0f, 0.0f, 0.0f, 0.0f};
+      if (b < cnt) a[u].x = q[b];
+      if (b + 1 < cnt) a[u].y = q[b + 1];
+      if (b + 2 < cnt) a[u].z = q[b + 2];
+    }
+  }
+}
+
+// One partition: acc = sum e, s1 = sum (local index) e, in the thread's fixed sample order.
+__device__ __forceinline__ void ew_sum_one(const ew_f4 a[EW_QUADS], double& acc, double& s1) {
+#pragma unroll
+  for (int u = 0; u < EW_QUADS; ++u) {
+    const int b = 4 * (threadIdx.x + EW_THREADS * u);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const double d = (double)a[u][r];
+      const double e = d * d;
+      acc += e;
+      s1 += (double)(b + r) * e;
+    }
+  }
+}
+
+// A chunk that straddles a limit (one or two chunks per limit and segment): every sample goes to partition
+// #{k : N_k <= c0 + local index}.  The same samples in the same order as ew_load + ew_sum_one, read one quad at a time.
+__device__ __forceinline__ void ew_sum_split(const float* __restrict__ q, int cnt, int64_t c0,
+                                             const int64_t lim[EW_MAX_LIMITS], int nlim, double acc[EW_MAX_LIMITS + 1],
+                                             double& s1) {
+#pragma unroll 1
+  for (int u = 0; u < EW_QUADS; ++u) {
+    const int b = 4 * (threadIdx.x + EW_THREADS * u);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const double d = (double)(b + r < cnt ? q[b + r] : 0.0f);
+      const double e = d * d;
+      const int64_t n = c0 + b + r;
+      int part = 0;
+#pragma unroll
+      for (int k = 0; k < EW_MAX_LIMITS; ++k) part += (k < nlim && n >= lim[k]) ? 1 : 0;
+#pragma unroll
+      for (int k = 0; k <= EW_MAX_LIMITS; ++k) acc[k] += (part == k) ? e : 0.0;
+      s1 += (double)(b + r) * e;
+    }
+  }
+}
+
+__global__ __launch_bounds__(EW_THREADS) void energy_partial_kernel(
+    const float* __restrict__ x, const int64_t* __restrict__ base_off, const int64_t* __restrict__ base_len,
+    const int32_t* __restrict__ chan_of_seg, const int64_t* __restrict__ onset, const int64_t* __restrict__ limits,
+    int nlim, int64_t chunk_stride, double* __restrict__ scratch) {
+  __shared__ double wsum[EW_WAVES][EW_MAX_REC];
+  const int seg = blockIdx.y;
+  const int64_t o = ira::uniform(onset[ira::uniform(chan_of_seg[seg])]);
+  const int64_t n = ira::uniform(base_len[seg]) - o;
+  const int64_t c0 = (int64_t)blockIdx.x * EW_CHUNK;
+  if (c0 >= n) return;                                        // the fold reads only the chunks of the segment's length
+  const int cnt = (int)(n - c0 < EW_CHUNK ? n - c0 : EW_CHUNK);
+  const float* q = x + ira::uniform(base_off[seg]) + o + c0;
+  int64_t lim[EW_MAX_LIMITS];
+  int part0 = 0;
+  bool split = false;
+#pragma unroll
+  for (int k = 0; k < EW_MAX_LIMITS; ++k) {
+    lim[k] = k < nlim ? ira::uniform(limits[(int64_t)seg * nlim + k]) : INT64_MAX;
+    if (k < nlim) {
+      part0 += lim[k] <= c0 ? 1 : 0;
+      split = split || (lim[k] > c0 && lim[k] < c0 + cnt);
+    }
+  }
+  const int nrec = nlim + 2;
+  double acc[EW_MAX_LIMITS + 1];
+#pragma unroll
+  for (int k = 0; k <= EW_MAX_LIMITS; ++k) acc[k] = 0.0;
+  double s1 = 0.0;
+  if (split) {                                                 // workgroup-uniform
+    ew_sum_split(q, cnt, c0, lim, nlim, acc, s1);
+  } else {
+    ew_f4 a[EW_QUADS];
+    if (cnt == EW_CHUNK) ew_load<true>(q, cnt, a);
+    else ew_load<false>(q, cnt, a);
+    double one = 0.0;
+    ew_sum_one(a, one, s1);
+#pragma unroll
+    for (int k = 0; k <= EW_MAX_LIMITS; ++k) acc[k] = (k == part0) ? one : 0.0;
+  }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int k = 0; k <= EW_MAX_LIMITS; ++k) {
+    if (k <= nlim) {
+      const double w = ira::wave_sum(acc[k]);
+      if (lane == 0) wsum[wave][k] = w;
+    }
+  }
+  {
+    const double w = ira::wave_sum(s1);
+    if (lane == 0) wsum[wave][EW_MAX_REC - 1] = w;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double* rec = scratch + ((int64_t)seg * chunk_stride + blockIdx.x) * nrec;
+    double tot = 0.0;
+    for (int k = 0; k <= nlim; ++k) {
+      double v = wsum[0][k];
+      for (int w = 1; w < EW_WAVES; ++w) v += wsum[w][k];
+      rec[k] = v;
+      tot += v;
+    }
+    double sl = wsum[0][EW_MAX_REC - 1];
+    for (int w = 1; w < EW_WAVES; ++w) sl += wsum[w][EW_MAX_REC - 1];
+    rec[nlim + 1] = (double)c0 * tot + sl;                     // sum n e = c0 sum e + sum (n - c0) e
+  }
+}
+
+// One wave per segment: lane l folds chunks l, l + 64, ... in ascending order, then a fixed butterfly across the lanes.
+__global__ __launch_bounds__(IRA_WAVE) void energy_fold_kernel(const int64_t* __restrict__ base_len,
+                                                               const int32_t* __restrict__ chan_of_seg,
+                                                               const int64_t* __restrict__ onset, int nseg, int nlim,
+                                                               int64_t chunk_stride, const double* __restrict__ scratch,
+                                                               double* __restrict__ out) {
+  const int seg = blockIdx.x;
+  if (seg >= nseg) return;
+  const int64_t n = base_len[seg] - onset[chan_of_seg[seg]];
+  const int64_t nch = n > 0 ? (n + EW_CHUNK - 1) / EW_CHUNK : 0;
+  const int nrec = nlim + 2;
+  const double* rec = scratch + (int64_t)seg * chunk_stride * nrec;
+  const int lane = threadIdx.x;
+  for (int r = 0; r < nrec; ++r) {
+    double v = 0.0;
+    for (int64_t c = lane; c < nch; c += IRA_WAVE) v += rec[c * nrec + r];
+    v = ira::wave_sum(v);
+    if (lane == 0) out[(int64_t)seg * nrec + r] = v;
+  }
+}
+
+static inline int64_t ew_chunks(int64_t max_len) { return (max_len + EW_CHUNK - 1) / EW_CHUNK; }
+
+}  // namespace
+
+extern "C" int32_t ira_onset_index(const float* x_dev, const int64_t* off_dev, const int64_t* len_dev, int32_t nseg,
+                                   int64_t max_len, const int64_t* peak_dev, const float* peak_abs_dev, double rel_energy,
+                                   int64_t* onset_dev, void* stream) {
+  IRA_CHECK_PTR(x_dev); IRA_CHECK_PTR(off_dev); IRA_CHECK_PTR(len_dev); IRA_CHECK_PTR(peak_dev);
+  IRA_CHECK_PTR(peak_abs_dev); IRA_CHECK_PTR(onset_dev);
+  if (!(rel_energy >= 0.0 && rel_energy <= 1.0)) return IRA_E_SIZE;        // onset_db <= 0 (NaN fails both tests)
+  if (nseg <= 0) return nseg == 0 ? IRA_OK : IRA_E_SIZE;
+  if (nseg > 65535 || max_len < 0 || max_len > 0xFFFFFFFFll) return IRA_E_SIZE;
+  hipStream_t st = (hipStream_t)stream;
+  onset_init_kernel<<<(nseg + 255) / 256, 256, 0, st>>>(peak_dev, nseg, onset_dev);
+  const int64_t chunks = max_len > 0 ? (max_len + ON_CHUNK - 1) / ON_CHUNK : 0;
+  if (chunks > 0)
+    onset_search_kernel<<<dim3((unsigned)chunks, nseg), ON_THREADS, 0, st>>>(x_dev, off_dev, len_dev, peak_dev,
+                                                                             peak_abs_dev, rel_energy, onset_dev);
+  IRA_RETURN_LAUNCH();
+}
+
+extern "C" int64_t ira_energy_scratch_doubles(int32_t nseg, int64_t max_len, int32_t nlim) {
+  if (nseg < 0 || nseg > 65535 || max_len < 0 || max_len > EW_MAX_LEN || nlim < 1 || nlim > EW_MAX_LIMITS)
+    return IRA_E_SIZE;
+  return (int64_t)nseg * ew_chunks(max_len) * (nlim + 2);
+}
+
+extern "C" int32_t ira_energy_windows(const float* x_dev, const int64_t* base_off_dev, const int64_t* base_len_dev,
+                                      const int32_t* chan_of_seg_dev, const int64_t* onset_dev, int32_t nseg,
+                                      int64_t max_len, const int64_t* limits_dev, int32_t nlim, double* scratch_dev,
+                                      double* out_dev, void* stream) {
+  IRA_CHECK_PTR(x_dev); IRA_CHECK_PTR(base_off_dev); IRA_CHECK_PTR(base_len_dev); IRA_CHECK_PTR(chan_of_seg_dev);
+  IRA_CHECK_PTR(onset_dev); IRA_CHECK_PTR(limits_dev); IRA_CHECK_PTR(scratch_dev); IRA_CHECK_PTR(out_dev);
+  if (nlim < 1 || nlim > EW_MAX_LIMITS) return IRA_E_SIZE;
+  if (nseg <= 0) return nseg == 0 ? IRA_OK : IRA_E_SIZE;
+  if (nseg > 65535 || max_len < 0 || max_len > EW_MAX_LEN) return IRA_E_SIZE;
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t chunks = ew_chunks(max_len);
+  if (chunks > 0)
+    energy_partial_kernel<<<dim3((unsigned)chunks, nseg), EW_THREADS, 0, st>>>(
+        x_dev, base_off_dev, base_len_dev, chan_of_seg_dev, onset_dev, limits_dev, nlim, chunks, scratch_dev);
+  energy_fold_kernel<<<nseg, IRA_WAVE, 0, st>>>(base_len_dev, chan_of_seg_dev, onset_dev, nseg, nlim, chunks, scratch_dev,
+                                                out_dev);
+  IRA_RETURN_LAUNCH();
+}

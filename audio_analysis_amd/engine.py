@@ -50,7 +50,8 @@ class _TimedLib:
     bracketed by two HIP events recorded on the SAME stream the kernels are enqueued on, so per-call device
     time can be read back after a synchronise (bench.py's roofline uses this).
     """
-    _PLAIN = {"ira_error_string", "ira_abi_version", "ira_ar_partial_doubles", "ira_ar_exact_doubles"}
+    _PLAIN = {"ira_error_string", "ira_abi_version", "ira_ar_partial_doubles", "ira_ar_exact_doubles",
+              "ira_energy_scratch_doubles"}
 
     def __init__(self, lib, eng):
         self._lib, self._eng, self._cache = lib, eng, {}
@@ -480,6 +481,47 @@ class Engine:
               "ira_edc_fits")
         return (fit[: n * nr * FIT_DOUBLES].view(n, nr, FIT_DOUBLES) if nr else None,
                 cr[: n * nc].view(n, nc) if nc else None, out, edc_off)
+
+    # ------------------------------------------------------------------ ISO 3382-1 energy parameters
+    def onset_index(self, b: ChannelBatch, rel_energy: float):
+        """ISO 3382-1 onset per channel: the first n <= peak with x[n]^2 >= x[peak]^2 * rel_energy (float64 compare).  The
+        peak pick and the search both run on the device (ira_peak_index -> ira_onset_index): nothing returns to the host.
+        Returns (onset int64 device (B,), peak int64 device (B,), |x[peak]| float32 device (B,))."""
+        t = self.torch
+        n = b.count
+        pk, pa, on = self.empty(n, t.int64), self.empty(n, t.float32), self.empty(n, t.int64)
+        max_len = int(b.length.max()) if n else 0
+        check(self.lib.ira_peak_index(_ptr(b.x), _ptr(b.off_dev), _ptr(b.len_dev), n, max_len, _ptr(pk), _ptr(pa),
+                                      self.stream), "ira_peak_index")
+        check(self.lib.ira_onset_index(_ptr(b.x), _ptr(b.off_dev), _ptr(b.len_dev), n, max_len, _ptr(pk), _ptr(pa),
+                                       float(rel_energy), _ptr(on), self.stream), "ira_onset_index")
+        return on[:n], pk[:n], pa[:n]
+
+    def energy_windows(self, x_dev, base_off: np.ndarray, base_len: np.ndarray, chan_of_seg: np.ndarray, onset_dev,
+                       limits: np.ndarray):
+        """Windowed float64 energy sums (ira_energy_windows).  Segment j: base_len[j] - o samples from base_off[j] + o of
+        x_dev, o = onset_dev[chan_of_seg[j]]; limits (nseg, nlim) int64 ascending sample counts from the segment's start.
+        Returns (nseg, nlim + 2) float64 device: P_0 .. P_nlim (energy between consecutive limits, the last one up to the
+        segment's end), S1 = sum n x[n]^2."""
+        t = self.torch
+        base_off = np.ascontiguousarray(base_off, dtype=np.int64)
+        base_len = np.ascontiguousarray(base_len, dtype=np.int64)
+        nseg = int(base_off.size)
+        limits = np.ascontiguousarray(limits, dtype=np.int64)
+        if limits.ndim != 2 or limits.shape[0] != nseg:
+            raise ValueError("limits must be (nseg, nlim)")
+        nlim = int(limits.shape[1])
+        max_len = int(base_len.max()) if nseg else 0
+        nsc = int(self.lib.ira_energy_scratch_doubles(nseg, max_len, nlim))
+        check(min(nsc, 0), "ira_energy_scratch_doubles")
+        scratch = self.empty(nsc, t.float64)
+        out = self.empty(nseg * (nlim + 2), t.float64)
+        d_off, d_len, d_ch, d_lim = self.job_tables(base_off, base_len, np.ascontiguousarray(chan_of_seg, np.int32),
+                                                    limits.reshape(-1))
+        check(self.lib.ira_energy_windows(_ptr(x_dev), _ptr(d_off), _ptr(d_len), _ptr(d_ch), _ptr(onset_dev), nseg,
+                                          max_len, _ptr(d_lim), nlim, _ptr(scratch), _ptr(out), self.stream),
+              "ira_energy_windows")
+        return out[: nseg * (nlim + 2)].view(nseg, nlim + 2)
 
     # ------------------------------------------------------------------ a4/a5/a16
     def curve_fits(self, y_dev, off: np.ndarray, lens: np.ndarray, t_mul: float, t_div: float,

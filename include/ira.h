@@ -33,7 +33,7 @@ extern "C" {
 #define IRA_E_FORMAT (-5)     /* a file is not RIFF/WAVE (host-side ingest entry points only) */
 #define IRA_E_HIP_BASE (-1000)
 
-#define IRA_ABI_VERSION 8   /* bumped whenever an exported signature or a scratch-size constant changes */
+#define IRA_ABI_VERSION 9   /* bumped whenever an exported signature or a scratch-size constant changes */
 
 int32_t ira_abi_version(void);
 const char* ira_error_string(int32_t code);
@@ -530,6 +530,28 @@ int32_t ira_deconv_divide(double* yspec_dev, const int64_t* yspec_off_dev, const
 int32_t ira_deconv_finish(float* h_dev, const int64_t* h_off_dev, const int32_t* n_out_dev, const int32_t* group_dev,
                           int32_t nb, int32_t ngroups, int32_t max_len, int32_t remove_dc, int32_t normalise_peak,
                           double target_peak, float* mean_dev, uint32_t* peak_bits_dev, void* stream);
+
+/* ---- ISO 3382-1 energy-ratio parameters: clarity C_k, definition D, centre time Ts ----------------------------------
+ * Nothing in the reference computes these (it reports decay times only); they replace no reference function.  Host side:
+ * audio_analysis_amd/analyse/energy.py (`python -m analyse.energy`).
+ * ira_onset_index: onset_dev[s] = the smallest n <= p with float64(x[n])^2 >= float64(x[p])^2 * rel_energy (float64
+ *   compare), p = peak_dev[s] as ira_peak_index wrote it and peak_abs_dev[s] = |x[p]| -- read on the device, no host round
+ *   trip (ISO 3382-1 A.3.4: the first point within 20 dB of the maximum is rel_energy = 10^(-20/10)).  rel_energy in
+ *   [0, 1]; max_len = longest segment (sizes the grid; < 2^32); nseg <= 65535.  Exact integer result.
+ * ira_energy_windows: segment j = base_len[j] - o samples from base_off[j] + o, o = onset_dev[chan_of_seg[j]] (band signals
+ *   of a channel share its broadband onset).  With the segment's nlim (1..4) ascending sample limits
+ *   limits_dev[j * nlim + k] (per segment: channels of different sample rates share a launch), out_dev[j * (nlim + 2) + i]:
+ *   i <= nlim: P_i = sum of float64(x)^2 over [N_i, N_{i+1}) (N_0 = 0, N_{nlim+1} = segment length), i = nlim + 1:
+ *   S1 = sum n x[n]^2.  Float64 sums in an order that depends on the segment alone (bit-identical whatever the batch, the
+ *   segment's place in it or its alignment).  max_len >= every base_len (< 2^31); nseg <= 65535; scratch_dev holds
+ *   ira_energy_scratch_doubles(nseg, max_len, nlim) doubles (IRA_E_SIZE, negative, for arguments out of range). */
+int32_t ira_onset_index(const float* x_dev, const int64_t* off_dev, const int64_t* len_dev, int32_t nseg, int64_t max_len,
+                        const int64_t* peak_dev, const float* peak_abs_dev, double rel_energy, int64_t* onset_dev,
+                        void* stream);
+int64_t ira_energy_scratch_doubles(int32_t nseg, int64_t max_len, int32_t nlim);
+int32_t ira_energy_windows(const float* x_dev, const int64_t* base_off_dev, const int64_t* base_len_dev,
+                           const int32_t* chan_of_seg_dev, const int64_t* onset_dev, int32_t nseg, int64_t max_len,
+                           const int64_t* limits_dev, int32_t nlim, double* scratch_dev, double* out_dev, void* stream);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,395 @@
+"""
+ISO 3382-1 energy parameters on the device (ira_onset_index + ira_energy_windows, audio_analysis_amd.analyse.energy)
+against a NumPy restatement of the definitions in the module's docstring, written out here; band signals against the
+oracle's float64 filter bank.
+"""
+import json
+import math
+import os
+import subprocess
+import sys
+from pathlib import Path
+
+import numpy as np
+import pytest
+
+from oracle import ira_oracle as O
+
+pytestmark = pytest.mark.gpu
+
+REPO = Path(__file__).resolve().parent.parent
+SR = 48000
+
+
+# ------------------------------------------------------------------------------------------------ the restatement
+def ref_onset(x, onset_db=-20.0):
+    x = np.asarray(x, dtype=np.float32)
+    e = x.astype(np.float64) ** 2
+    p = int(np.argmax(np.abs(x)))
+    return int(np.flatnonzero(e[: p + 1] >= e[p] * 10.0 ** (onset_db / 10.0))[0])
+
+
+def ref_sums(y, onset, limits):
+    """P_0 .. P_K, S1 of e = float64(y)^2 over y[onset:] (float64, NumPy's own sums)."""
+    s = np.asarray(y, dtype=np.float32)[onset:].astype(np.float64) ** 2
+    edges = [0] + [int(v) for v in limits] + [s.size]
+    parts = [float(np.sum(s[a:b])) if b > a else 0.0 for a, b in zip(edges[:-1], edges[1:])]
+    return np.array(parts + [float(np.sum(np.arange(s.size, dtype=np.float64) * s))])
+
+
+def ref_params(sums, fs, d_index=0):
+    p, s1 = sums[:-1], sums[-1]
+    total = float(np.sum(p))
+    k = p.size - 1
+    c = []
+    for i in range(1, k + 1):
+        early, late = float(np.sum(p[:i])), float(np.sum(p[i:]))
+        c.append(math.inf if late == 0.0 and early > 0.0 else 10.0 * math.log10(early / late))
+    return c, float(np.sum(p[: d_index + 1])) / total, s1 / (fs * total)
+
+
+def limits_at(fs, ms=(50.0, 80.0)):
+    return [math.ceil(v * fs / 1000.0) for v in ms]
+
+
+def _eng():
+    from audio_analysis_amd.engine import get_engine
+    return get_engine()
+
+
+def device_sums(eng, chans, limits_per_chan, onset_db=-20.0):
+    """Engine level: onsets and window sums of every channel in one batch, one launch."""
+    b = eng.upload([np.asarray(c, dtype=np.float32) for c in chans])
+    on, _, _ = eng.onset_index(b, 10.0 ** (onset_db / 10.0))
+    out = eng.energy_windows(b.x, b.off, b.length, np.arange(b.count, dtype=np.int32), on,
+                             np.asarray(limits_per_chan, dtype=np.int64))
+    return on.cpu().numpy(), out.cpu().numpy()
+
+
+def close(a, b, rel):
+    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
+    return np.all(np.abs(a - b) <= rel * np.abs(b))
+
+
+def assert_params(res, want_c, want_d, want_ts, tol_c=1e-9, tol_d=1e-9, tol_ts=1e-9):
+    for g, w in zip(res.clarity_db, want_c):
+        if math.isinf(w):
+            assert g == w
+        else:
+            assert abs(g - w) <= tol_c, (g, w)
+    assert abs(res.definition - want_d) <= tol_d, (res.definition, want_d)
+    assert abs(res.centre_time_seconds - want_ts) <= tol_ts * abs(want_ts) + 1e-300, (res.centre_time_seconds, want_ts)
+
+
+# ------------------------------------------------------------------------------------------------ broadband
+def _ragged_irs():
+    from audio_analysis_amd.synth import synth_ir
+    nk = limits_at(SR)[-1]
+    spec = [(480000, 1.2, None), (96000, 0.3, 17), (48000, 0.8, 0), (20000, 2.5, 1000), (nk + 1, 0.2, 0),
+            (nk + 7, 0.5, 0), (5000, 0.1, 3), (100003, 1.7, 555)]
+    return [synth_ir(i, 0, n, SR, rt60_seconds=rt, pre_delay=d) for i, (n, rt, d) in enumerate(spec)]
+
+
+def test_broadband_ragged_batch_vs_restatement():
+    from audio_analysis_amd.analyse import energy as E
+    eng = _eng()
+    chans = _ragged_irs()
+    lim = limits_at(SR)
+    on, out = device_sums(eng, chans, [lim] * len(chans))
+    for i, x in enumerate(chans):
+        o = ref_onset(x)
+        assert on[i] == o, (i, on[i], o)
+        want = ref_sums(x, o, lim)
+        assert close(out[i], want, 1e-12), (i, out[i], want)
+    res = E.analyse_energy_parameters_batch(chans, SR, [f"c{i}" for i in range(len(chans))],
+                                            E.EnergyParameterSettings(bands=None))
+    for i, x in enumerate(chans):
+        o = ref_onset(x)
+        assert res[i].status == 0 and res[i].onset_samples == o and res[i].onset_seconds == o / SR
+        c, d, ts = ref_params(ref_sums(x, o, lim), SR)
+        assert_params(res[i].broadband, c, d, ts)
+        assert res[i].band_parameters_by_name == {}
+
+
+def test_pure_exponential_closed_form():
+    """x[n] = float32(r^n): C50, C80 and Ts from geometric series in r (independent of the restatement).  The float32
+    rounding of the samples moves each energy by at most 2^-23 relative, i.e. C by at most ~1e-6 dB."""
+    from audio_analysis_amd.analyse import energy as E
+    for r, m in ((0.9995, 48000), (0.99985, 96000)):
+        x = (r ** np.arange(m, dtype=np.float64)).astype(np.float32)
+        q = r * r
+
+        def geo(a, b):                                 # sum_{n=a}^{b-1} q^n
+            return q ** a * (1.0 - q ** (b - a)) / (1.0 - q)
+
+        n1, n2 = limits_at(SR)
+        total = geo(0, m)
+        s1 = q * (1.0 - m * q ** (m - 1) + (m - 1) * q ** m) / (1.0 - q) ** 2
+        c50 = 10.0 * math.log10(geo(0, n1) / geo(n1, m))
+        c80 = 10.0 * math.log10(geo(0, n2) / geo(n2, m))
+        res = E.analyse_energy_parameters_batch([x], SR, ["exp"], E.EnergyParameterSettings(bands=None))[0]
+        assert res.onset_samples == 0 and res.status == 0
+        assert abs(res.broadband.clarity_db[0] - c50) <= 1e-6 and abs(res.broadband.clarity_db[1] - c80) <= 1e-6
+        assert abs(res.broadband.definition - geo(0, n1) / total) <= 1e-6
+        assert abs(res.broadband.centre_time_seconds - s1 / (SR * total)) <= 1e-6 * s1 / (SR * total)
+
+
+# ------------------------------------------------------------------------------------------------ onset
+def test_onset_threshold_ties_and_levels():
+    eng = _eng()
+    lim = [[4, 8]]
+    # the factor 10^(-20/10) = 0.01 makes the threshold for a peak of 10 exactly 1.0 (float64), so x = 1.0 meets it with
+    # equality (>=) and the float32 just below it does not
+    assert 100.0 * 10.0 ** (-20.0 / 10.0) == 1.0
+    below = np.nextafter(np.float32(1.0), np.float32(0.0))
+    ramp = np.array([0.0, 0.1, 0.5, below, 1.0, 3.0, 10.0, -10.0, 2.0] + [0.5] * 40, dtype=np.float32)
+    tie = np.array([0.0, 0.2, -4.0, 4.0, 4.0, 0.1] + [0.3] * 40, dtype=np.float32)
+    first = np.array([5.0, 0.1, 5.0, 1.0] + [0.2] * 40, dtype=np.float32)
+    long_ramp = np.concatenate([np.linspace(0.0, 1.0, 70001, dtype=np.float32), np.full(30000, 0.2, np.float32)])
+    chans = [ramp, tie, first, long_ramp]
+    for db in (-20.0, -40.0, -3.0, 0.0):
+        on, _ = device_sums(eng, chans, lim * len(chans), onset_db=db)
+        assert list(on) == [ref_onset(c, db) for c in chans], db
+    on, _ = device_sums(eng, chans, lim * len(chans))
+    assert on[0] == 4                                                    # the sample exactly at the threshold
+    assert on[1] == 2 and on[2] == 0                                     # first maximum is the peak; onset at index 0
+    on40, _ = device_sums(eng, [ramp], lim, onset_db=-40.0)
+    assert on40[0] == 1                                                  # float32(0.1)^2 = 0.0100000003 >= 100 * 1e-4
+
+
+# ------------------------------------------------------------------------------------------------ edge cases
+def test_edge_cases_keep_the_rest_of_the_batch():
+    from audio_analysis_amd.analyse import energy as E
+    from audio_analysis_amd.synth import synth_ir
+    nk = limits_at(SR)[-1]
+    good = synth_ir(3, 0, 30000, SR, rt60_seconds=0.4)
+    dirac = np.zeros(9000, np.float32)
+    dirac[0] = 0.7
+    silent = np.zeros(9000, np.float32)
+    exact = np.zeros(nk, np.float32)
+    exact[0] = 1.0                                                       # L == N_K: too short
+    plus1 = np.zeros(nk + 1, np.float32)
+    plus1[0] = 1.0
+    plus1[-1] = 0.5                                                      # L == N_K + 1: analysed
+    nan = good.copy()
+    nan[5000] = np.nan
+    inf = good.copy()
+    inf[7000] = np.inf
+    chans = [good, dirac, silent, exact, plus1, nan, inf, good]
+    st = E.EnergyParameterSettings(bands=None)
+    res = E.analyse_energy_parameters_batch(chans, SR, [str(i) for i in range(len(chans))], st)
+    alone = E.analyse_energy_parameters_batch([good], SR, ["g"], st)[0]
+    for i in (0, 7):
+        assert res[i].status == 0 and res[i].broadband == alone.broadband
+    assert res[1].status == 0 and res[1].broadband.clarity_db == (math.inf, math.inf)
+    assert res[1].broadband.definition == 1.0 and res[1].broadband.centre_time_seconds == 0.0
+    assert res[2].status == E.STATUS_SILENT
+    assert res[3].status == E.STATUS_TOO_SHORT
+    assert res[4].status == 0
+    c, d, ts = ref_params(ref_sums(plus1, 0, limits_at(SR)), SR)
+    assert_params(res[4].broadband, c, d, ts)
+    assert res[5].status & E.STATUS_NON_FINITE and res[6].status & E.STATUS_NON_FINITE
+    for i in (2, 3, 5, 6):
+        v = res[i].broadband
+        assert all(math.isnan(a) for a in v.clarity_db) and math.isnan(v.definition) and math.isnan(v.centre_time_seconds)
+    # with bands: a bad channel's bands are NaN too, the good ones are untouched
+    resb = E.analyse_energy_parameters_batch([good, silent, good], SR, ["a", "b", "c"], E.EnergyParameterSettings())
+    assert resb[0].band_parameters_by_name == resb[2].band_parameters_by_name
+    assert all(math.isnan(p.definition) for p in resb[1].band_parameters_by_name.values())
+
+
+# ------------------------------------------------------------------------------------------------ bands
+def _oracle_band_signals(x, sr, mode):
+    n = x.size
+    f = np.fft.rfftfreq(n, d=1.0 / float(sr)).astype(np.float32)
+    spec = np.fft.rfft(x.astype(np.float64))
+    kw = dict(band_mode=mode)
+    out = []
+    for b in O.band_definitions(sr, **kw):
+        m = O.band_mask(f, b, 1.0 / 6.0, 0.5 * float(sr))
+        out.append((b["name"], np.fft.irfft(spec * m.astype(np.float64), n=n).astype(np.float32)))
+    return out
+
+
+def test_kernel_precision_on_uploaded_band_signals():
+    """The windows kernel alone: the oracle's float64 band signals, rounded to float32 and uploaded as they are; every band
+    segment starts at the broadband channel's onset (chan_of_seg points at the broadband row)."""
+    from audio_analysis_amd.synth import synth_ir
+    eng = _eng()
+    x = synth_ir(11, 0, 72000, SR, rt60_seconds=0.9)
+    ys = [y for _, y in _oracle_band_signals(x, SR, "octave")]
+    b = eng.upload([x] + ys)
+    on, _, _ = eng.onset_index(b, 0.01)
+    lim = limits_at(SR, (20.0, 50.0, 80.0, 200.0))
+    out = eng.energy_windows(b.x, b.off, b.length, np.zeros(b.count, np.int32), on,
+                             np.tile(np.asarray(lim, np.int64), (b.count, 1))).cpu().numpy()
+    o = ref_onset(x)
+    assert int(on.cpu().numpy()[0]) == o
+    for j, y in enumerate([x] + ys):
+        want = ref_sums(y, o, lim)
+        assert close(out[j], want, 1e-12), (j, out[j], want)
+
+
+def _bound_params(y_ref, delta, onset, limits, fs, d_index=0):
+    """First-order bounds on C (dB), D and Ts (relative) when every sample of y_ref may be off by delta: a partition sum of
+    squares moves by at most 2 delta sum|y| + count delta^2, S1 by the same with the weights n."""
+    y = np.asarray(y_ref, dtype=np.float64)[onset:]
+    a = 2.0 * delta * np.abs(y) + delta * delta
+    n = np.arange(y.size, dtype=np.float64)
+    edges = [0] + list(limits) + [y.size]
+    dp = np.array([np.sum(a[s:e]) for s, e in zip(edges[:-1], edges[1:])])
+    p = np.array([np.sum(y[s:e] ** 2) for s, e in zip(edges[:-1], edges[1:])])
+    ds1, s1 = float(np.sum(n * a)), float(np.sum(n * y * y))
+    tc = []
+    for i in range(1, p.size):
+        e_, l_ = p[:i].sum(), p[i:].sum()
+        de, dl = dp[:i].sum(), dp[i:].sum()
+        tc.append(10.0 / math.log(10.0) * (de / max(e_ - de, 1e-300) + dl / max(l_ - dl, 1e-300)) * 1.01 + 1e-9)
+    tot, dtot = p.sum(), dp.sum()
+    rd = (dp[: d_index + 1].sum() / p[: d_index + 1].sum() + dtot / tot) * 1.01 + 1e-9
+    rts = (ds1 / s1 + dtot / tot) * 1.01 + 1e-9
+    return tc, rd, rts
+
+
+@pytest.mark.parametrize("mode", ["three", "octave", "third"])
+def test_band_path_vs_oracle_filter_bank(mode):
+    """Full band path (filter bank on the device + windows) against the restatement on the oracle's band signals.  The
+    device's band signals differ from the float64 ones rounded to float32 by a few 1e-7 of the peak (the tolerance of
+    test_band_masks_and_band_signals_vs_reference_goldens); the largest difference delta is measured here per band and
+    propagated to C, D and Ts by _bound_params -- the tolerance follows from it.  That is ~1e-4 dB for C and ~1e-5
+    relative for Ts on a decay that falls 60 dB inside the file."""
+    from audio_analysis_amd.analyse import energy as E
+    from audio_analysis_amd.analyse.rt60bands import Rt60BandsAnalysisSettings
+    from audio_analysis_amd.synth import synth_ir
+    eng = _eng()
+    chans = [synth_ir(20, 0, 48000, SR, rt60_seconds=0.6), synth_ir(21, 0, 37123, SR, rt60_seconds=0.35)]
+    st = E.EnergyParameterSettings(bands=Rt60BandsAnalysisSettings(band_mode=mode))
+    res = E.analyse_energy_parameters_batch(chans, SR, ["a", "b"], st)
+    lim = limits_at(SR)
+    batch = eng.upload(chans)
+    bands, y, y_off = E.band_signals_device(eng, batch, SR, st.bands)
+    yh = y.cpu().numpy()
+    worst_c = 0.0
+    for i, x in enumerate(chans):
+        o = ref_onset(x)
+        ob = _oracle_band_signals(x, SR, mode)
+        assert [b.name for b in res[i].band_definitions] == [nm for nm, _ in ob]
+        for j, (name, yref) in enumerate(ob):
+            ydev = yh[y_off[i, j] : y_off[i, j] + x.size]
+            delta = float(np.max(np.abs(ydev.astype(np.float64) - yref.astype(np.float64))))
+            assert delta <= 1e-6 * float(np.max(np.abs(x))), (name, delta)
+            c, d, ts = ref_params(ref_sums(yref, o, lim), SR)
+            tc, rd, rts = _bound_params(yref, delta, o, lim, SR)
+            got = res[i].band_parameters_by_name[name]
+            for g, w, t in zip(got.clarity_db, c, tc):
+                assert abs(g - w) <= t, (mode, name, g, w, t)
+                worst_c = max(worst_c, abs(g - w))
+            assert abs(got.definition - d) <= rd * abs(d), (mode, name)
+            assert abs(got.centre_time_seconds - ts) <= rts * abs(ts), (mode, name)
+    assert worst_c < 1e-2
+
+
+# ------------------------------------------------------------------------------------------------ determinism, rates
+def test_bit_identical_whatever_the_batch():
+    from audio_analysis_amd.synth import synth_ir
+    eng = _eng()
+    x = synth_ir(7, 0, 250001, SR, rt60_seconds=1.1, pre_delay=333)
+    lim = limits_at(SR, (20.0, 50.0, 80.0))
+    _, alone = device_sums(eng, [x], [lim])
+    rng = np.random.default_rng(3)
+    others = [synth_ir(100 + k, 0, int(rng.integers(4000, 60000)), SR) for k in range(299)]
+    chans = others[:200] + [x] + others[200:]
+    _, many = device_sums(eng, chans, [lim] * len(chans))
+    for shift in (1, 2, 3):                                              # the channel starts 4, 8, 12 bytes past a 16-byte line
+        _, mis = device_sums(eng, [np.zeros(shift, np.float32) + 0.25, x], [lim, lim])
+        assert np.array_equal(mis[1].view(np.uint64), alone[0].view(np.uint64)), shift
+    assert np.array_equal(many[200].view(np.uint64), alone[0].view(np.uint64))
+
+
+def test_mixed_sample_rates_in_one_launch():
+    from audio_analysis_amd.synth import synth_ir
+    eng = _eng()
+    rates = [44100, 48000, 44100, 48000]
+    chans = [synth_ir(30 + i, 0, 60000 + 999 * i, fs, rt60_seconds=0.5 + 0.2 * i) for i, fs in enumerate(rates)]
+    lims = [limits_at(fs) for fs in rates]
+    assert lims[0] == [2205, 3528] and lims[1] == [2400, 3840]
+    on, out = device_sums(eng, chans, lims)
+    for i, x in enumerate(chans):
+        o = ref_onset(x)
+        assert on[i] == o
+        assert close(out[i], ref_sums(x, o, lims[i]), 1e-12)
+
+
+# ------------------------------------------------------------------------------------------------ long inputs
+def test_long_channel_and_long_stereo_file(tmp_path):
+    from scipy.io import wavfile
+    from audio_analysis_amd.analyse import energy as E
+    from audio_analysis_amd.synth import synth_ir
+    eng = _eng()
+    x = synth_ir(40, 0, 2_880_000, SR, rt60_seconds=2.8)
+    lim = limits_at(SR)
+    on, out = device_sums(eng, [x], [lim])
+    o = ref_onset(x)
+    assert on[0] == o and close(out[0], ref_sums(x, o, lim), 1e-12)
+    n = 24 * SR
+    st = np.stack([synth_ir(41, 0, n, SR, rt60_seconds=1.9), synth_ir(41, 1, n, SR, rt60_seconds=2.2)], axis=1)
+    path = tmp_path / "long.wav"
+    wavfile.write(str(path), SR, st.astype(np.float32))
+    res = E.analyse_energy_parameters_from_wav_file(path)
+    assert [r.channel_name for r in res] == ["left", "right"]
+    for j, r in enumerate(res):
+        ch = st[:, j].astype(np.float32)
+        o = ref_onset(ch)
+        assert r.status == 0 and r.onset_samples == o
+        c, d, ts = ref_params(ref_sums(ch, o, lim), SR)
+        assert_params(r.broadband, c, d, ts)
+        assert len(r.band_parameters_by_name) == 9
+        assert all(math.isfinite(p.definition) for p in r.band_parameters_by_name.values())
+
+
+# ------------------------------------------------------------------------------------------------ command line
+def _run_cli(args, timeout=600):
+    env = dict(os.environ, PYTHONPATH=str(REPO))
+    r = subprocess.run([sys.executable, "-m", "analyse.energy", *map(str, args)], capture_output=True, text=True,
+                       cwd=str(REPO), env=env, timeout=timeout)
+    assert r.returncode == 0, r.stderr[-3000:]
+    return r.stdout
+
+
+def test_cli_on_wav_and_bundle(tmp_path):
+    from audio_analysis_amd.analyse import energy as E
+    from audio_analysis_amd.analyse.rt60bands import Rt60BandsAnalysisSettings
+    from audio_analysis_amd.synth import synth_ir
+    n = SR
+    taps = {}
+    for k, name in enumerate(["hall", "plate"]):
+        st = np.stack([synth_ir(50 + k, 0, n, SR, rt60_seconds=0.8), synth_ir(50 + k, 1, n, SR, rt60_seconds=0.9)], axis=1)
+        taps[name] = O.recorder_wav_bytes(st.reshape(-1), SR)
+    wav = tmp_path / "hall.wav"
+    wav.write_bytes(taps["hall"])
+    out = _run_cli(["--input", wav, "--bands", "third", "--json", tmp_path / "w.json"])
+    st_third = E.EnergyParameterSettings(bands=Rt60BandsAnalysisSettings(band_mode="third"))
+    api = E.analyse_energy_parameters_files([wav], st_third)
+    assert out == E.summarise_energy_parameters_text(api)
+    assert [r.channel_name for r in api] == ["hall.wav:left", "hall.wav:right"]
+    assert "1000Hz" in out and "C80_dB" in out
+    back = E.energy_results_from_json(json.loads((tmp_path / "w.json").read_text()))
+    assert E.summarise_energy_parameters_text(back) == out
+    assert back[0].broadband == api[0].broadband and back[1].band_parameters_by_name == api[1].band_parameters_by_name
+    # bundle: meta.json + taps/<name>.wav, read through the native ingest
+    root = tmp_path / "bundle"
+    (root / "taps").mkdir(parents=True)
+    for name, blob in taps.items():
+        (root / "taps" / f"{name}.wav").write_bytes(blob)
+    (root / "meta.json").write_text(O.recorder_meta_json(SR, n, list(taps)))
+    out = _run_cli(["--bundle", root, "--mono", "--bands", "none", "--limits-ms", "30", "50", "80"])
+    st_b = E.EnergyParameterSettings(bands=None, early_limits_ms=(30.0, 50.0, 80.0), use_mono_downmix_for_stereo=True)
+    api = E.analyse_energy_parameters_bundle(root, st_b)
+    assert out == E.summarise_energy_parameters_text(api)
+    assert [r.channel_name for r in api] == ["hall:mono", "plate:mono"]
+    # the native ingest's mono downmix is the channel policy's: same numbers as the Python reader
+    wav2 = tmp_path / "plate.wav"
+    wav2.write_bytes(taps["plate"])
+    ref = E.analyse_energy_parameters_files([wav, wav2], st_b)
+    for a, b in zip(api, ref):
+        assert a.broadband == b.broadband and a.onset_samples == b.onset_samples
