@@ -1,5 +1,6 @@
 // a11: STFT magnitude in dB (reference analyse/spectrogram.py:107-160 and its copies in waterfall.py /
-// modalcloud.py).  One workgroup handles TB consecutive output columns (frames) of one segment:
+// modalcloud.py): the three STFT entry points, which pick the kernel of every (precision, n_fft, layout), and the
+// generic kernel stft_kernel.  One workgroup of stft_kernel handles TB consecutive output columns (frames) of one segment:
 //   frame*window -> packed real FFT (n_fft/2-point complex DIF in LDS) -> |X| -> floor -> 20 log10 -> f32,
 // collecting the TB columns in an LDS tile so that each output row is written as a TB-float run of the
 // C-contiguous (F, T) matrix the reference returns.
@@ -7,6 +8,7 @@
 #include <cstdlib>
 
 #include "ira_fft_lds.h"
+#include "ira_stft.h"
 
 namespace {
 
@@ -119,18 +121,14 @@ int32_t launch_stft(const float* x, const int64_t* off, const int32_t* nframes, 
 
 }  // namespace
 
-// register-resident configurations (ira_stft2.hip); IRA_E_UNSUPPORTED = use the generic kernel above
-int32_t ira_stft2_dispatch(const float* x, const int64_t* off, const int32_t* nframes, int32_t nseg,
-                           int32_t max_frames, int32_t n_fft, int32_t hop, const void* window, const void* tw,
-                           int32_t precision, double floor_db, float* out, const int64_t* out_off,
-                           const int32_t* frame_sel, const int64_t* sel_off, hipStream_t st);
-
-// float32 / n_fft 4096 at 16 one-wave teams per CU (ira_stft3.hip)
-int32_t ira_stft3_dispatch(const float* x, const int64_t* off, const int32_t* nframes, int32_t nseg,
-                           int32_t max_frames, int32_t n_fft, int32_t hop, const void* window, const void* tw,
-                           int32_t precision, double floor_db, float* out, const int64_t* out_off,
-                           const int32_t* frame_sel, const int64_t* sel_off, hipStream_t st);
-
+// The three entry points below are the only place that decides which kernel serves which request:
+//   ira_stft_mag_db     (F, T)  f32 / 4096                         stft3_kernel  (ira_stft3.hip)
+//                               f32 / 8192, f64 / 4096, f64 / 8192  stft2_kernel  (ira_stft2.hip)
+//                               any other power of two 64 .. 16384  stft_kernel   (above)
+//   ira_stft_mag_db_tf  (T, F)  f32 / 4096                         stft6_kernel  (ira_stft3.hip)
+//                               f64 / 8192                         stft5_kernel  (ira_stft4.hip)
+//   ira_stft_logbin             f64 / 8192                         stft5_kernel  (ira_stft4.hip)
+// Every other configuration of the last two is IRA_E_UNSUPPORTED.
 extern "C" int32_t ira_stft_mag_db(const float* x_dev, const int64_t* off_dev, const int32_t* nframes_dev,
                                    int32_t nseg, int32_t max_frames, int32_t n_fft, int32_t hop,
                                    const void* window_dev, const void* twiddle_dev, int32_t precision,
@@ -146,38 +144,18 @@ extern "C" int32_t ira_stft_mag_db(const float* x_dev, const int64_t* off_dev, c
   while ((1 << log2n) < n_fft) ++log2n;
   hipStream_t st = (hipStream_t)stream;
   if (precision != 32 && precision != 64) return IRA_E_UNSUPPORTED;
-  const bool force_generic = ira_tune_flag("IRA_STFT_GENERIC");   // A/B switch for benchmarking
-  const bool no_v3 = ira_tune_flag("IRA_STFT_NO_V3");             // A/B switch for benchmarking
-  if (!force_generic && !no_v3) {
-    const int32_t rc = ira_stft3_dispatch(x_dev, off_dev, nframes_dev, nseg, max_frames, n_fft, hop, window_dev,
-                                          twiddle_dev, precision, floor_db, out_dev, out_off_dev, frame_sel_dev,
-                                          sel_off_dev, st);
-    if (rc != IRA_E_UNSUPPORTED) return rc;
-  }
-  if (!force_generic) {
-    const int32_t rc = ira_stft2_dispatch(x_dev, off_dev, nframes_dev, nseg, max_frames, n_fft, hop, window_dev,
-                                          twiddle_dev, precision, floor_db, out_dev, out_off_dev, frame_sel_dev,
-                                          sel_off_dev, st);
-    if (rc != IRA_E_UNSUPPORTED) return rc;
-  }
+  if (precision == 32 && n_fft == 4096)
+    return ira_stft3_launch(x_dev, off_dev, nframes_dev, nseg, max_frames, hop, window_dev, twiddle_dev, floor_db,
+                            out_dev, out_off_dev, frame_sel_dev, sel_off_dev, st);
+  if (n_fft == 8192 || (precision == 64 && n_fft == 4096))
+    return ira_stft2_launch(x_dev, off_dev, nframes_dev, nseg, max_frames, n_fft, hop, window_dev, twiddle_dev,
+                            precision, floor_db, out_dev, out_off_dev, frame_sel_dev, sel_off_dev, st);
   if (precision == 32)
     return launch_stft<float>(x_dev, off_dev, nframes_dev, nseg, max_frames, log2n, hop, window_dev, twiddle_dev,
                               floor_db, out_dev, out_off_dev, frame_sel_dev, sel_off_dev, st);
-  if (precision == 64)
-    return launch_stft<double>(x_dev, off_dev, nframes_dev, nseg, max_frames, log2n, hop, window_dev, twiddle_dev,
-                               floor_db, out_dev, out_off_dev, frame_sel_dev, sel_off_dev, st);
-  return IRA_E_UNSUPPORTED;
+  return launch_stft<double>(x_dev, off_dev, nframes_dev, nseg, max_frames, log2n, hop, window_dev, twiddle_dev,
+                             floor_db, out_dev, out_off_dev, frame_sel_dev, sel_off_dev, st);
 }
-
-int32_t ira_stft3_dispatch_tf(const float* x, const int64_t* off, const int32_t* nframes, int32_t nseg,
-                              int32_t max_frames, int32_t n_fft, int32_t hop, const void* window, const void* tw,
-                              int32_t precision, double floor_db, float* out, const int64_t* out_off,
-                              const int32_t* frame_sel, const int64_t* sel_off, hipStream_t st);
-
-int32_t ira_stft4_dispatch_tf(const float* x, const int64_t* off, const int32_t* nframes, int32_t nseg,
-                              int32_t max_frames, int32_t n_fft, int32_t hop, const void* window, const void* tw,
-                              int32_t precision, double floor_db, float* out, const int64_t* out_off,
-                              const int32_t* frame_sel, const int64_t* sel_off, hipStream_t st);
 
 extern "C" int32_t ira_stft_mag_db_tf(const float* x_dev, const int64_t* off_dev, const int32_t* nframes_dev,
                                       int32_t nseg, int32_t max_frames, int32_t n_fft, int32_t hop,
@@ -190,20 +168,15 @@ extern "C" int32_t ira_stft_mag_db_tf(const float* x_dev, const int64_t* off_dev
   if (nseg < 0 || max_frames < 0 || hop <= 0) return IRA_E_SIZE;
   if (nseg == 0 || max_frames == 0) return IRA_OK;
   if (nseg > 65535) return IRA_E_SIZE;
-  const int32_t rc = ira_stft3_dispatch_tf(x_dev, off_dev, nframes_dev, nseg, max_frames, n_fft, hop, window_dev,
-                                           twiddle_dev, precision, floor_db, out_dev, out_off_dev, frame_sel_dev,
-                                           sel_off_dev, (hipStream_t)stream);
-  if (rc != IRA_E_UNSUPPORTED) return rc;
-  return ira_stft4_dispatch_tf(x_dev, off_dev, nframes_dev, nseg, max_frames, n_fft, hop, window_dev, twiddle_dev,
-                               precision, floor_db, out_dev, out_off_dev, frame_sel_dev, sel_off_dev,
-                               (hipStream_t)stream);
+  hipStream_t st = (hipStream_t)stream;
+  if (precision == 32 && n_fft == 4096)
+    return ira_stft6_launch(x_dev, off_dev, nframes_dev, nseg, max_frames, hop, window_dev, twiddle_dev, floor_db,
+                            out_dev, out_off_dev, frame_sel_dev, sel_off_dev, st);
+  if (precision == 64 && n_fft == 8192)
+    return ira_stft5_launch(x_dev, off_dev, nframes_dev, nseg, max_frames, hop, window_dev, twiddle_dev, floor_db,
+                            out_dev, out_off_dev, frame_sel_dev, sel_off_dev, 0, 0, nullptr, nullptr, st);
+  return IRA_E_UNSUPPORTED;
 }
-
-int32_t ira_stft4_dispatch_logbin(const float* x, const int64_t* off, const int32_t* nframes, int32_t nseg,
-                                  int32_t max_frames, int32_t n_fft, int32_t hop, const void* window, const void* tw,
-                                  int32_t precision, double floor_db, int32_t k_base, const int32_t* first,
-                                  const int32_t* count, int32_t nbins, float* curves, const int64_t* curves_off,
-                                  hipStream_t st);
 
 extern "C" int32_t ira_stft_logbin(const float* x_dev, const int64_t* off_dev, const int32_t* nframes_dev,
                                    int32_t nseg, int32_t max_frames, int32_t n_fft, int32_t hop,
@@ -216,7 +189,8 @@ extern "C" int32_t ira_stft_logbin(const float* x_dev, const int64_t* off_dev, c
   if (nseg < 0 || max_frames < 0 || hop <= 0 || nbins <= 0 || k_base < 0) return IRA_E_SIZE;
   if (nseg == 0 || max_frames == 0) return IRA_OK;
   if (nseg > 65535) return IRA_E_SIZE;
-  return ira_stft4_dispatch_logbin(x_dev, off_dev, nframes_dev, nseg, max_frames, n_fft, hop, window_dev, twiddle_dev,
-                                   precision, floor_db, k_base, first_dev, count_dev, nbins, curves_dev,
-                                   curves_off_dev, (hipStream_t)stream);
+  if (precision != 64 || n_fft != 8192) return IRA_E_UNSUPPORTED;
+  return ira_stft5_launch(x_dev, off_dev, nframes_dev, nseg, max_frames, hop, window_dev, twiddle_dev, floor_db,
+                          curves_dev, curves_off_dev, nullptr, nullptr, nbins, k_base, first_dev, count_dev,
+                          (hipStream_t)stream);
 }

@@ -1,4 +1,5 @@
-// STFT v2: register-resident FFT, one TEAM of TW waves per frame (TW = 1: n_fft 4096, TW = 2: n_fft 8192).
+// stft2_kernel (STFT v2): register-resident FFT, one TEAM of TW waves per frame (TW = 1: n_fft 4096, TW = 2: n_fft 8192),
+// (F, T) output.  Serves float32 / 8192, float64 / 4096 and float64 / 8192.
 //
 // Packed real FFT: z[n] = xw[2n] + i xw[2n+1], M = n_fft/2 = 2048*TW complex points, 32 per lane.
 // M = 16 * 16 * R3 (R3 = 8 or 16), decimation in frequency, natural-order input:
@@ -16,6 +17,7 @@
 
 #include "ira_fft_reg.h"
 #include "ira_log.h"
+#include "ira_stft.h"
 
 namespace {
 
@@ -70,7 +72,7 @@ struct Cfg {
 
 // Synchronisation between the waves of one TEAM.  A one-wave team needs no barrier at all: the exchange buffer
 // is private to the wave and a wave's LDS instructions execute in program order, so only the compiler has to be
-// told not to move the reads above the writes.  That lets the 8 waves of a workgroup drift apart and overlap each
+// told not to move the reads above the writes.  That lets the waves of a workgroup drift apart and overlap each
 // other's global-load and LDS latencies.  Two-wave teams use the workgroup barrier.
 template <int TW>
 __device__ __forceinline__ void team_sync() {
@@ -347,23 +349,17 @@ int32_t launch2(const float* x, const int64_t* off, const int32_t* nframes, int3
 
 }  // namespace
 
-// Returns IRA_E_UNSUPPORTED when (n_fft, precision) has no register-resident configuration; the caller then
-// falls back to the generic LDS kernel in ira_stft.hip.
-int32_t ira_stft2_dispatch(const float* x, const int64_t* off, const int32_t* nframes, int32_t nseg,
-                           int32_t max_frames, int32_t n_fft, int32_t hop, const void* window, const void* tw,
-                           int32_t precision, double floor_db, float* out, const int64_t* out_off,
-                           const int32_t* frame_sel, const int64_t* sel_off, hipStream_t st) {
-  if (precision == 32 && n_fft == 4096)
-    return launch2<float, 1, 8, 2>(x, off, nframes, nseg, max_frames, hop, window, tw, floor_db, out, out_off,
-                                   frame_sel, sel_off, st);
-  if (precision == 32 && n_fft == 8192)
+// float32 / 8192, float64 / 4096 or float64 / 8192 (ira_stft_mag_db routes nothing else here)
+int32_t ira_stft2_launch(const float* x, const int64_t* off, const int32_t* nframes, int32_t nseg, int32_t max_frames,
+                         int32_t n_fft, int32_t hop, const void* window, const void* tw, int32_t precision,
+                         double floor_db, float* out, const int64_t* out_off, const int32_t* frame_sel,
+                         const int64_t* sel_off, hipStream_t st) {
+  if (precision == 32)
     return launch2<float, 2, 4, 2>(x, off, nframes, nseg, max_frames, hop, window, tw, floor_db, out, out_off,
                                    frame_sel, sel_off, st);
-  if (precision == 64 && n_fft == 4096)
+  if (n_fft == 4096)
     return launch2<double, 1, 4, 2>(x, off, nframes, nseg, max_frames, hop, window, tw, floor_db, out, out_off,
                                     frame_sel, sel_off, st);
-  if (precision == 64 && n_fft == 8192)
-    return launch2<double, 2, 2, 2>(x, off, nframes, nseg, max_frames, hop, window, tw, floor_db, out, out_off,
-                                    frame_sel, sel_off, st);
-  return IRA_E_UNSUPPORTED;
+  return launch2<double, 2, 2, 2>(x, off, nframes, nseg, max_frames, hop, window, tw, floor_db, out, out_off,
+                                  frame_sel, sel_off, st);
 }

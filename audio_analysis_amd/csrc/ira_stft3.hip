@@ -1,5 +1,5 @@
-// STFT v3: the float32 / n_fft = 4096 configuration (the reference's spectrogram default, spectrogram.py:107-160)
-// at SIXTEEN one-wave teams per CU.
+// stft3_kernel (STFT v3, (F, T) output) and stft6_kernel (frame-major (T, F) output, below): the float32 / n_fft = 4096
+// configuration (the reference's spectrogram default, spectrogram.py:107-160) at SIXTEEN one-wave teams per CU.
 //
 // Why a third kernel: tools/pk_f32_rate.hip shows that on gfx950 one wave can issue an f32 VALU instruction only
 // every ~5 cycles while the SIMD retires one every ~2.5, and that packed f32 math saturates the SIMD with a single
@@ -26,6 +26,7 @@
 #include <type_traits>
 
 #include "ira_fft_reg.h"
+#include "ira_stft.h"
 
 namespace {
 
@@ -41,6 +42,7 @@ constexpr int ROWH = 66;     // E1 half: row stride (complex)
 constexpr int E2N3 = 272;    // E2 half: n3' stride (complex)
 constexpr int EXC = 1072;    // complex slots per team: max(16*66, 15 + 240 + 3*272 + 1, 2048 floats / 2)
 static_assert(EXC >= 16 * ROWH && EXC >= 15 + 16 * 15 + 3 * E2N3 + 1 && EXC * 2 >= M3, "exchange buffer too small");
+constexpr int NT = 16;       // one-wave teams per workgroup: four waves per SIMD, <= 128 VGPRs each
 
 __device__ __forceinline__ void wave_sync() {
   // One-wave team: LDS instructions of a wave execute in order; only the compiler must not reorder across this.
@@ -107,13 +109,12 @@ __device__ __forceinline__ void powers16_exact(const cf* __restrict__ tw, unsign
   }
 }
 
-template <int NT3, bool TF>
-__global__ __launch_bounds__(64 * NT3) void stft3_kernel(
+__global__ __launch_bounds__(64 * NT) void stft3_kernel(
     const float* __restrict__ x, const int64_t* __restrict__ off, const int32_t* __restrict__ nframes, int hop,
     const float* __restrict__ window, const cf* __restrict__ tw, float floor_lin, float floor_db,
     float* __restrict__ out, const int64_t* __restrict__ out_off, const int32_t* __restrict__ frame_sel,
     const int64_t* __restrict__ sel_off, int ablate, unsigned win_lds_off) {
-  constexpr int TB3 = NT3;   // one frame per team -> NT3 output columns per workgroup
+  constexpr int TB3 = NT;   // one frame per team -> NT output columns per workgroup
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   // XCD-aware bijective remap: each XCD (own L2) gets a contiguous range of (segment, frame group) pairs, so the
   // groups that share 7/8 of their samples and adjacent halves of the same output lines meet in one L2.
@@ -121,10 +122,9 @@ __global__ __launch_bounds__(64 * NT3) void stft3_kernel(
   const unsigned orig = blockIdx.y * gx + blockIdx.x;
   const unsigned xq = nwg / 8, xr = nwg % 8, xcd = orig % 8;
   const unsigned wg = (xcd < xr ? xcd * (xq + 1) : xr * (xq + 1) + (xcd - xr) * xq) + orig / 8;
-  if ((IRA_ABL(ablate & 48)) && orig < 256u * (16 / NT3) * 1u) {
+  if ((IRA_ABL(ablate & 48)) && orig < 256u) {
     // diagnostic: stagger the first round of workgroups so that co-resident ones are out of phase
-    const unsigned slot = (NT3 == 16) ? ((IRA_ABL(ablate & 16)) ? ((orig >> 3) & 1u) : ((orig >> 3) & 3u))
-                                      : ((IRA_ABL(ablate & 16)) ? (orig / 256u) % (16 / NT3) : orig % (16 / NT3));
+    const unsigned slot = (IRA_ABL(ablate & 16)) ? ((orig >> 3) & 1u) : ((orig >> 3) & 3u);
     for (unsigned i = 0; i < slot * (unsigned)IRA_ABL(ablate >> 8); ++i) __builtin_amdgcn_s_sleep(100);
   }
   const int seg = (int)(wg / gx);
@@ -141,7 +141,7 @@ __global__ __launch_bounds__(64 * NT3) void stft3_kernel(
   // The Hann window (16 KB) is the same for every frame: one copy in LDS per workgroup instead of 16 KB of L1 traffic
   // per frame (the frame loads were L1-bound).  Lives behind the exchange buffers / tile.
   float* winl = reinterpret_cast<float*>(smem_raw + win_lds_off);
-  for (int i = tid; i < 2 * M3; i += 64 * NT3) winl[i] = window[i];
+  for (int i = tid; i < 2 * M3; i += 64 * NT) winl[i] = window[i];
   __syncthreads();
 
   const int col = col0 + team;
@@ -293,22 +293,6 @@ __global__ __launch_bounds__(64 * NT3) void stft3_kernel(
   }
   IRA_STAMP(2);
 
-  if (TF) {
-    // Frame-major output (T, F): the frame's 2049 values are contiguous, so every wave stores its own frame straight
-    // from registers in 256-byte runs -- no tile, no workgroup barrier, no partial-line write requests.
-    if (col < T_out) {
-      float* fo = out + out_off[seg] + (int64_t)col * F3;
-#pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        const int k = q + 64 * i;
-        fo[k] = lo[i];
-        fo[M3 - k] = hi[i];                                   // k = 0 -> bin M (Nyquist)
-      }
-      if (q == 0) fo[M3 / 2] = mid;
-    }
-    return;
-  }
-
   __syncthreads();
   IRA_STAMP(3);   // every team is done with its exchange buffer: the tile may overwrite them
   float* tile = reinterpret_cast<float*>(smem_raw);      // [F][TB + 1]
@@ -328,7 +312,7 @@ __global__ __launch_bounds__(64 * NT3) void stft3_kernel(
   // aligned (T is arbitrary); global dwordx4 stores accept that.
   typedef float f4u __attribute__((ext_vector_type(4), aligned(4)));
   constexpr int QR = TB3 / 4;
-  for (int idx = tid; idx < ((IRA_ABL(ablate & 4)) ? 1 : F3 * QR); idx += 64 * NT3) {
+  for (int idx = tid; idx < ((IRA_ABL(ablate & 4)) ? 1 : F3 * QR); idx += 64 * NT) {
     const int k = idx / QR, c4 = (idx % QR) * 4;
     const float* tp = tile + k * (TB3 + 1) + c4;
     float* gp = o + (int64_t)k * T_out + col0 + c4;
@@ -345,49 +329,52 @@ __global__ __launch_bounds__(64 * NT3) void stft3_kernel(
     __builtin_amdgcn_sched_barrier(0);
     asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t5) :: "memory");          // stores issued, not yet acknowledged
     asm volatile("s_waitcnt vmcnt(0)\n\ts_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t6) :: "memory");
-    if ((wg == nwg / 2 || wg == nwg / 2 + 1) && q == 0 && (team == 0 || team == NT3 - 1))
+    if ((wg == nwg / 2 || wg == nwg / 2 + 1) && q == 0 && (team == 0 || team == NT - 1))
       printf("STAMP wg %u team %d: step1(load+dft) %llu  steps2-3+post %llu  barrier1 %llu  tile %llu  store-issue %llu  store-ack %llu\n",
              wg, team, st[1] - st[0], st[2] - st[1], st[3] - st[2], st[4] - st[3], t5 - st[4], t6 - t5);
   }
 #undef IRA_STAMP
 }
 
-// float32 / n_fft 4096 only; anything else returns IRA_E_UNSUPPORTED and the caller falls through to v2 / v1.
-template <int NT3, bool TF>
-int32_t launch3(const float* x, const int64_t* off, const int32_t* nframes, int32_t nseg, int32_t max_frames,
-                int32_t hop, const void* window, const void* tw, double floor_db, float* out, const int64_t* out_off,
-                const int32_t* frame_sel, const int64_t* sel_off, hipStream_t st) {
-  constexpr int TB3 = NT3;
-  constexpr size_t lds_ex = (size_t)NT3 * EXC * sizeof(cf);
+}  // namespace
+
+int32_t ira_stft3_launch(const float* x, const int64_t* off, const int32_t* nframes, int32_t nseg, int32_t max_frames,
+                         int32_t hop, const void* window, const void* tw, double floor_db, float* out,
+                         const int64_t* out_off, const int32_t* frame_sel, const int64_t* sel_off, hipStream_t st) {
+  constexpr int TB3 = NT;
+  constexpr size_t lds_ex = (size_t)NT * EXC * sizeof(cf);
   constexpr size_t lds_tile = (size_t)F3 * (TB3 + 1) * sizeof(float);
-  constexpr size_t lds_main = ((TF ? lds_ex : (lds_ex > lds_tile ? lds_ex : lds_tile)) + 15) & ~(size_t)15;
+  constexpr size_t lds_main = ((lds_ex > lds_tile ? lds_ex : lds_tile) + 15) & ~(size_t)15;
   constexpr size_t lds = lds_main + (size_t)2 * M3 * sizeof(float);          // + the window copy
   static_assert(lds <= 160 * 1024, "one workgroup must fit the CU's LDS");
   const hipError_t attr = lds <= 64 * 1024 ? hipSuccess
-                                            : hipFuncSetAttribute(reinterpret_cast<const void*>(&stft3_kernel<NT3, TF>),
+                                            : hipFuncSetAttribute(reinterpret_cast<const void*>(&stft3_kernel),
                                                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (attr != hipSuccess) return ira_hip_status(attr);
   const double floor_lin = std::pow(10.0, floor_db / 20.0);
   const int ablate = ira_tune_int("IRA_STFT3_ABLATE", 0);   // diagnostics
   dim3 grid((max_frames + TB3 - 1) / TB3, nseg);
-  stft3_kernel<NT3, TF><<<grid, 64 * NT3, lds, st>>>(x, off, nframes, hop, static_cast<const float*>(window),
-                                            static_cast<const cf*>(tw), (float)floor_lin, (float)floor_db, out,
-                                            out_off, frame_sel, sel_off, ablate, (unsigned)lds_main);
+  stft3_kernel<<<grid, 64 * NT, lds, st>>>(x, off, nframes, hop, static_cast<const float*>(window),
+                                           static_cast<const cf*>(tw), (float)floor_lin, (float)floor_db, out, out_off,
+                                           frame_sel, sel_off, ablate, (unsigned)lds_main);
   IRA_RETURN_LAUNCH();
 }
 
+namespace {
 
 // ------------------------------------------------------------------------------------------------------------
-// STFT v6: the frame-major (T, F) variant as a PERSISTENT kernel -- one 16-wave workgroup per CU that walks many tiles of
-// 16 frames, every wave transforming "its" frame of each tile on its own, with NO workgroup barrier inside the loop.
+// stft6_kernel (STFT v6): the frame-major (T, F) output as a PERSISTENT kernel -- one 16-wave workgroup per CU that walks
+// many tiles of 16 frames, every wave transforming "its" frame of each tile on its own, with NO workgroup barrier inside
+// the loop.
 //
 // Why (round 3, tools/micro/dft16_rate.hip, profiles/r03_dft16_rate.txt): the frame's own instruction stream (1915 VALU
 // instructions, the LDS exchanges included) issues at 1.27 wave-instructions per CU-cycle when 16 waves free-run through
-// it, but stft3_kernel<16, true> ran at 0.65 -- and still at 0.79 with every load and store ablated.  A 16-wave / 150 KB
-// workgroup is the only one its CU can hold, so with one workgroup PER TILE each CU went through launch -> window staging
-// -> barrier -> 16 waves loading at once (L1-bound) -> 16 waves computing in lock-step -> stores -> drain, one phase at a
-// time, ~230 times per launch.  Here the window is staged once per CU, waves drift out of phase within a few tiles, and
-// one wave's loads / stores / LDS round trips run under the arithmetic of the other three on its SIMD.
+// it, but the same frame body with one workgroup per tile ran at 0.65 -- and still at 0.79 with every load and store
+// ablated.  A 16-wave / 150 KB workgroup is the only one its CU can hold, so with one workgroup PER TILE each CU went
+// through launch -> window staging -> barrier -> 16 waves loading at once (L1-bound) -> 16 waves computing in lock-step
+// -> stores -> drain, one phase at a time, ~230 times per launch.  Here the window is staged once per CU, waves drift out
+// of phase within a few tiles, and one wave's loads / stores / LDS round trips run under the arithmetic of the other three
+// on its SIMD.
 // The grid is the CU count (every wave has a fixed trip count: no work queue, nothing to drain).
 // ------------------------------------------------------------------------------------------------------------
 // element at a 32-bit BYTE offset from a wave-uniform base: written this way the access compiles to the scalar-base +
@@ -397,15 +384,11 @@ __device__ __forceinline__ T& at32(T* base, unsigned byte_off) {
   return *reinterpret_cast<T*>(reinterpret_cast<char*>(const_cast<typename std::remove_const<T>::type*>(base)) + byte_off);
 }
 
-// NT: one-wave teams per workgroup (16 = four waves per SIMD and <= 128 registers; 12 = three per SIMD and <= 170).
-// PF: software pipeline -- the NEXT frame's half-0 samples are requested before this frame's results are computed and
-//     stored, half 1 before half 0 is transformed.  gfx950 counts loads and stores in ONE in-order counter, so a load
-//     issued after a frame's 33 stores cannot be consumed before those stores are acknowledged; issued before them it can.
 // AB: ablation bits, instantiated only by the tuning build (IRA_STFT6_ABLATE): 1 no sample loads, 2 no window reads,
 //     4 no stores, 8 post-stage twiddles without the scalar table loads, 16 polynomial logarithm, 32 E3 through LDS (the
 //     pre-round-5 mirror exchange), 64 samples from LDS + emulated staging (timing only: see load_half),
 //     128 every twiddle read from the table instead of formed by products (error measurement).  The product runs AB = 0.
-template <int NT, bool PF, int AB>
+template <int AB>
 __global__ __launch_bounds__(64 * NT) void stft6_kernel(
     const float* __restrict__ x, const int64_t* __restrict__ off, const int32_t* __restrict__ nframes, int hop,
     const float* __restrict__ window, const cf* __restrict__ tw, float floor_lin, float floor_db,
@@ -473,8 +456,6 @@ __global__ __launch_bounds__(64 * NT) void stft6_kernel(
   float* fo = out;
   bool have = false;
   while (t < t_end && !(have = locate(t, fx, fo))) t += t_step;
-  float xa0[16], xb0[16];                                  // half 0 of the frame about to be transformed (PF)
-  if (PF && have) load_half(fx, q0, 0, xa0, xb0);
 
   // The sixteen wave-uniform factors W_N^(64 i) of the post step live in scalar registers for the whole walk: inside the loop
   // they were sixteen scalar loads per frame in four to eight serial round trips (s_waitcnt lgkmcnt(0)).
@@ -512,16 +493,14 @@ __global__ __launch_bounds__(64 * NT) void stft6_kernel(
 
     // ---- step 1 ---------------------------------------------------------------------------------------------------
     cf a1[16];
-    float xa1[16], xb1[16];
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
       const int m = q + 64 * h;
       float xa[16], xb[16], wa[16], wb[16];
-      if (!PF) load_half(fx, q, h, xa, xb);                // (all loads first, one wait)
+      load_half(fx, q, h, xa, xb);                         // (all loads first, one wait)
 #pragma unroll
       for (int n1 = 0; n1 < 16; ++n1) {
         const unsigned n = (unsigned)(n1 * 128 + m);
-        if (PF) { xa[n1] = h ? xa1[n1] : xa0[n1]; xb[n1] = h ? xb1[n1] : xb0[n1]; }
         if (AB & 2) { wa[n1] = 0.5f; wb[n1] = 0.25f; }
         else { wa[n1] = winl[2u * n]; wb[n1] = winl[2u * n + 1u]; }
       }
@@ -529,11 +508,6 @@ __global__ __launch_bounds__(64 * NT) void stft6_kernel(
       cf v[16];
 #pragma unroll
       for (int n1 = 0; n1 < 16; ++n1) v[n1] = {xa[n1] * wa[n1], xb[n1] * wb[n1]};
-      if (PF && h == 0) {                                  // half 1's samples: in flight under half 0's DFT
-        __builtin_amdgcn_sched_barrier(0);
-        load_half(fx, q, 1, xa1, xb1);
-        __builtin_amdgcn_sched_barrier(0);
-      }
       dft_dif<float, 16>(v);
       cf p[16];
       if (AB & 128) powers16_exact(tw, (unsigned)(2 * m), p);
@@ -652,13 +626,6 @@ __global__ __launch_bounds__(64 * NT) void stft6_kernel(
     }
     const int perm_src = ((64 - q) & 63) << 2;              // byte address of the partner lane for ds_bpermute
 
-    // ---- next frame, half 0 (PF): requested BEFORE this frame's results are computed and stored ---------------------------
-    if (PF) {
-      __builtin_amdgcn_sched_barrier(0);
-      if (have_n) load_half(fxn, q, 0, xa0, xb0);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-
     // ---- post: X[k] = E + P, X[M-k] = conj(E - P) with E = (Zk + conj Zp)/2, P = W_N^k (-i)(Zk - conj Zp)/2 -> dB -> store.
     // A NaN (or infinite) sample anywhere in the frame makes every bin of numpy's rfft NaN (spectrogram.py:150): it shows
     // in Z[0] = sum of the packed inputs, which lane 0 holds as its first pair -- one flag per frame.  Every result is
@@ -709,10 +676,11 @@ __global__ __launch_bounds__(64 * NT) void stft6_kernel(
 // measured (profiles/r04_stft6_resync.txt): 2 brings the fetch traffic from 3.7x the samples down to 1.08x at the same run time
 constexpr int IRA_STFT6_RESYNC_DEFAULT = 2;
 
-template <int NT, bool PF>
-int32_t launch6(const float* x, const int64_t* off, const int32_t* nframes, int32_t nseg, int32_t max_frames, int32_t hop,
-                const void* window, const void* tw, double floor_db, float* out, const int64_t* out_off,
-                const int32_t* frame_sel, const int64_t* sel_off, hipStream_t st) {
+}  // namespace
+
+int32_t ira_stft6_launch(const float* x, const int64_t* off, const int32_t* nframes, int32_t nseg, int32_t max_frames,
+                         int32_t hop, const void* window, const void* tw, double floor_db, float* out,
+                         const int64_t* out_off, const int32_t* frame_sel, const int64_t* sel_off, hipStream_t st) {
   constexpr size_t lds_main = ((size_t)NT * EXC * sizeof(cf) + 15) & ~(size_t)15;
 #ifdef IRA_TUNING_BUILD
   constexpr size_t lds = lds_main + (size_t)2 * M3 * sizeof(float) + 4096;   // + the scratch tail of the AB & 64 emulation
@@ -734,13 +702,13 @@ int32_t launch6(const float* x, const int64_t* off, const int32_t* nframes, int3
   const int stagger = ira_tune_int("IRA_STFT6_STAGGER", 0);
 #define IRA_LAUNCH6(AB)                                                                                                   \
   do {                                                                                                                    \
-    const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&stft6_kernel<NT, PF, AB>),                 \
+    const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&stft6_kernel<AB>),                         \
                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                    \
     if (attr != hipSuccess) return ira_hip_status(attr);                                                                  \
-    stft6_kernel<NT, PF, AB><<<grid, 64 * NT, lds, st>>>(x, off, nframes, hop, static_cast<const float*>(window),         \
-                                              static_cast<const cf*>(tw), (float)floor_lin, (float)floor_db, out, out_off, \
-                                              frame_sel, sel_off, gx, (unsigned)tiles, (unsigned)lds_main, stagger,       \
-                                              ira_tune_int("IRA_STFT6_RESYNC", IRA_STFT6_RESYNC_DEFAULT));                \
+    stft6_kernel<AB><<<grid, 64 * NT, lds, st>>>(x, off, nframes, hop, static_cast<const float*>(window),                 \
+                                                 static_cast<const cf*>(tw), (float)floor_lin, (float)floor_db, out,      \
+                                                 out_off, frame_sel, sel_off, gx, (unsigned)tiles, (unsigned)lds_main,    \
+                                                 stagger, ira_tune_int("IRA_STFT6_RESYNC", IRA_STFT6_RESYNC_DEFAULT));    \
   } while (0)
 #ifdef IRA_TUNING_BUILD
   switch (ira_tune_int("IRA_STFT6_ABLATE", 0)) {
@@ -761,39 +729,4 @@ int32_t launch6(const float* x, const int64_t* off, const int32_t* nframes, int3
 #endif
 #undef IRA_LAUNCH6
   IRA_RETURN_LAUNCH();
-}
-
-}  // namespace
-
-int32_t ira_stft3_dispatch(const float* x, const int64_t* off, const int32_t* nframes, int32_t nseg,
-                           int32_t max_frames, int32_t n_fft, int32_t hop, const void* window, const void* tw,
-                           int32_t precision, double floor_db, float* out, const int64_t* out_off,
-                           const int32_t* frame_sel, const int64_t* sel_off, hipStream_t st) {
-  if (precision != 32 || n_fft != 4096) return IRA_E_UNSUPPORTED;
-  const int nt = ira_tune_int("IRA_STFT3_NT", 16);   // tuning
-  if (nt == 8)
-    return launch3<8, false>(x, off, nframes, nseg, max_frames, hop, window, tw, floor_db, out, out_off, frame_sel, sel_off, st);
-  if (nt == 4)
-    return launch3<4, false>(x, off, nframes, nseg, max_frames, hop, window, tw, floor_db, out, out_off, frame_sel, sel_off, st);
-  return launch3<16, false>(x, off, nframes, nseg, max_frames, hop, window, tw, floor_db, out, out_off, frame_sel, sel_off, st);
-}
-
-// Frame-major variant: out[e] is a (T, F) matrix (each frame's F values contiguous).
-int32_t ira_stft3_dispatch_tf(const float* x, const int64_t* off, const int32_t* nframes, int32_t nseg,
-                              int32_t max_frames, int32_t n_fft, int32_t hop, const void* window, const void* tw,
-                              int32_t precision, double floor_db, float* out, const int64_t* out_off,
-                              const int32_t* frame_sel, const int64_t* sel_off, hipStream_t st) {
-  if (precision != 32 || n_fft != 4096) return IRA_E_UNSUPPORTED;
-  if (ira_tune_flag("IRA_STFT_V3"))                       // tuning build: the one-workgroup-per-tile kernel (A/B, ablations)
-    return launch3<16, true>(x, off, nframes, nseg, max_frames, hop, window, tw, floor_db, out, out_off, frame_sel, sel_off, st);
-#ifdef IRA_TUNING_BUILD
-  switch (ira_tune_int("IRA_STFT6_VARIANT", 0)) {          // A/B: teams per workgroup x software pipeline
-    case 1: return launch6<16, false>(x, off, nframes, nseg, max_frames, hop, window, tw, floor_db, out, out_off, frame_sel, sel_off, st);
-    case 2: return launch6<12, false>(x, off, nframes, nseg, max_frames, hop, window, tw, floor_db, out, out_off, frame_sel, sel_off, st);
-    case 3: return launch6<12, true>(x, off, nframes, nseg, max_frames, hop, window, tw, floor_db, out, out_off, frame_sel, sel_off, st);
-    case 4: return launch6<16, true>(x, off, nframes, nseg, max_frames, hop, window, tw, floor_db, out, out_off, frame_sel, sel_off, st);
-    default: break;
-  }
-#endif
-  return launch6<16, false>(x, off, nframes, nseg, max_frames, hop, window, tw, floor_db, out, out_off, frame_sel, sel_off, st);
 }

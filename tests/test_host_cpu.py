@@ -73,6 +73,12 @@ def test_argument_validation_without_gpu():
     assert lib.ira_peak_index(0, 0, 0, 1, 16, 0, 0, 0) == -1                      # IRA_E_NULL
     assert lib.ira_stft_mag_db(1, 1, 1, 1, 1, 1000, 512, 1, 1, 32, -120.0, 1, 1, 0, 0, 0) == -2   # n_fft not a power of 2
     assert lib.ira_stft_mag_db(1, 1, 1, 1, 1, 4096, 512, 1, 1, 16, -120.0, 1, 1, 0, 0, 0) == -3  # precision
+    assert lib.ira_stft_mag_db_tf(1, 1, 1, 1, 1, 2048, 512, 1, 1, 32, -120.0, 1, 1, 0, 0, 0) == -3   # no (T, F) kernel
+    assert lib.ira_stft_mag_db_tf(1, 1, 1, 1, 1, 8192, 512, 1, 1, 32, -120.0, 1, 1, 0, 0, 0) == -3
+    assert lib.ira_stft_mag_db_tf(1, 1, 1, 70000, 1, 4096, 512, 1, 1, 32, -120.0, 1, 1, 0, 0, 0) == -2   # nseg > 65535
+    assert lib.ira_stft_logbin(1, 1, 1, 1, 1, 8192, 512, 1, 1, 32, -120.0, 0, 1, 1, 10, 1, 1, 0) == -3   # float64 only
+    assert lib.ira_stft_logbin(1, 1, 1, 1, 1, 4096, 512, 1, 1, 64, -120.0, 0, 1, 1, 10, 1, 1, 0) == -3   # n_fft 8192 only
+    assert lib.ira_stft_logbin(1, 1, 1, 70000, 1, 8192, 512, 1, 1, 64, -120.0, 0, 1, 1, 10, 1, 1, 0) == -2
     assert lib.ira_poly_roots(1, 1, 5000, 1e-14, 1, 1, 0) == -2
     assert lib.ira_ar_gram(1, 0, 1, 1, 0, 1, 100, 2000, 1, 0, 0) == -2
 

@@ -30,6 +30,6 @@ L = n - 300
 bytes_ = a.batch * (4.0 * L + 4.0 * (a.nfft // 2 + 1) * nfr[0])
 if os.environ.get("IRA_STFT2_ABLATE") == "256":
     print("stamps [step1, step2, step3, post, copy/keep, barrier, tile+store] cycles:", out[:7].cpu().numpy().tolist(), " step2(h=1) [16 LDS reads, dft16, twiddle+16 LDS writes]:", out[8:11].cpu().numpy().tolist())
-print(f"variant={'generic' if os.environ.get('IRA_STFT_GENERIC') else 'v2'} f{a.precision} nfft={a.nfft} "
+print(f"f{a.precision} nfft={a.nfft}{' (T, F)' if a.tf else ''} "
       f"B={a.batch}: {dt*1e3:.3f} ms/launch, {bytes_/dt/1e9:.1f} GB/s algorithmic, "
       f"{dt*1e9/(a.batch*nfr[0]):.1f} ns/frame")
