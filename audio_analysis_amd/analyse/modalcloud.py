@@ -155,7 +155,8 @@ def modal_cloud_device(eng, batch, sample_rate_hz: int, settings: ModalCloudAnal
         curves, cur_off = eng.stft_logbin(batch.x, batch.off + starts, nframes, n_fft, hop,
                                           bool(settings.use_hann_window), float(settings.floor_db), k_base, first, count)
     else:
-        tf = eng.stft_frame_major_ok(n_fft, 64)
+        # frame-major only up to n_fft 16384: ira_logbin_aggregate's frame-major kernel holds at most 8193 rows in LDS
+        tf = eng.stft_frame_major_ok(n_fft, 64) and n_fft // 2 + 1 <= 8193
         mag, mag_off, cols = eng.stft_mag_db(batch.x, batch.off + starts, nframes, n_fft, hop,
                                              bool(settings.use_hann_window), float(settings.floor_db), 64,
                                              frame_major=tf)

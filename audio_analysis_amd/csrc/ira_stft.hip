@@ -3,7 +3,8 @@
 // generic kernel stft_kernel.  One workgroup of stft_kernel handles TB consecutive output columns (frames) of one segment:
 //   frame*window -> packed real FFT (n_fft/2-point complex DIF in LDS) -> |X| -> floor -> 20 log10 -> f32,
 // collecting the TB columns in an LDS tile so that each output row is written as a TB-float run of the
-// C-contiguous (F, T) matrix the reference returns.
+// C-contiguous (F, T) matrix the reference returns.  Float64 / 16384 has no room for a tile beside its 128 KB FFT buffer:
+// there (TILED = false) a workgroup transforms one column and stores every bin straight to the matrix.
 #include <cmath>
 #include <cstdlib>
 
@@ -32,7 +33,7 @@ __device__ __forceinline__ float mag_to_db<double>(double re, double im, double 
   return (float)(20.0 * log10(m));
 }
 
-template <typename T>
+template <typename T, bool TILED>
 __global__ __launch_bounds__(STFT_THREADS) void stft_kernel(
     const float* __restrict__ x, const int64_t* __restrict__ off, const int32_t* __restrict__ nframes, int log2n,
     int hop, const T* __restrict__ window, const cplx<T>* __restrict__ tw, T floor_lin, float* __restrict__ out,
@@ -81,10 +82,12 @@ __global__ __launch_bounds__(STFT_THREADS) void stft_kernel(
         re = e.re + wo.re;
         im = e.im + wo.im;
       }
-      tile[k * tb + c] = mag_to_db<T>(re, im, floor_lin);
+      if constexpr (TILED) tile[k * tb + c] = mag_to_db<T>(re, im, floor_lin);
+      else out[out_off[seg] + (int64_t)k * T_out + col] = mag_to_db<T>(re, im, floor_lin);
     }
     __syncthreads();
   }
+  if constexpr (!TILED) return;
   // write the tile: row k gets ncol consecutive floats at out[k*T_out + col0 ...]
   float* o = out + out_off[seg];
   const int total = F * ncol;
@@ -99,23 +102,30 @@ int32_t launch_stft(const float* x, const int64_t* off, const int32_t* nframes, 
                     int log2n, int32_t hop, const void* window, const void* tw, double floor_db, float* out,
                     const int64_t* out_off, const int32_t* frame_sel, const int64_t* sel_off, hipStream_t st) {
   const int N = 1 << log2n, M = N / 2, F = M + 1;
-  const size_t fft_bytes = sizeof(cplx<T>) * (size_t)M;
-  // columns per workgroup: as many as fit beside the FFT buffer in 64 KB of LDS, at most 8
-  int tb = (int)((65536 - fft_bytes) / (sizeof(float) * (size_t)F));
+  const int64_t fft_bytes = (int64_t)sizeof(cplx<T>) * M, col_bytes = (int64_t)sizeof(float) * F;
+  // columns per workgroup: as many as fit beside the FFT buffer in 64 KB of LDS, at most 8 (signed: the float64 / 16384
+  // buffer alone is 128 KB)
+  int tb = (int)((65536 - fft_bytes) / col_bytes);
   if (tb > 8) tb = 8;
-  size_t lds = fft_bytes + sizeof(float) * (size_t)F * (size_t)(tb < 1 ? 1 : tb);
-  if (tb < 1) {
-    tb = 1;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&stft_kernel<T>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  // not even one column in 64 KB: a one-column tile in more LDS (float32 / 16384); when that exceeds the CU's 160 KB too
+  // (float64 / 16384: by 4 bytes), no tile -- one column per workgroup, stored straight from the FFT (TILED = false)
+  const bool tiled = tb >= 1 || fft_bytes + col_bytes <= 160 * 1024;
+  if (tb < 1) tb = 1;
+  const size_t lds = (size_t)(fft_bytes + (tiled ? col_bytes * tb : 0));
+  if (lds > 160 * 1024) return IRA_E_SIZE;
+  auto kern = stft_kernel<T, true>;
+  if constexpr (sizeof(T) == sizeof(double))     // float32 always has room for a column: no untiled float32 instance
+    if (!tiled) kern = stft_kernel<T, false>;
+  if (lds > 64 * 1024) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       (int)lds);
     if (e != hipSuccess) return ira_hip_status(e);
   }
-  if (lds > 160 * 1024) return IRA_E_SIZE;
   const double floor_lin = std::pow(10.0, floor_db / 20.0);
   dim3 grid((max_frames + tb - 1) / tb, nseg);
-  stft_kernel<T><<<grid, STFT_THREADS, lds, st>>>(x, off, nframes, log2n, hop, static_cast<const T*>(window),
-                                                  static_cast<const cplx<T>*>(tw), (T)floor_lin, out, out_off,
-                                                  frame_sel, sel_off, tb);
+  kern<<<grid, STFT_THREADS, lds, st>>>(x, off, nframes, log2n, hop, static_cast<const T*>(window),
+                                        static_cast<const cplx<T>*>(tw), (T)floor_lin, out, out_off, frame_sel, sel_off,
+                                        tb);
   IRA_RETURN_LAUNCH();
 }
 

@@ -281,7 +281,7 @@ int32_t ira_waterfall_rel(const float* mag_dev, const int64_t* mag_off_dev, cons
  * mag[e] is the (F, T_e) STFT dB matrix; for log bin b rows k_base+first[b] .. +count[b]-1 are averaged as
  * linear magnitude 10^(dB/20) in float64 (rows added in order), then 20 log10(max(mean, 1e-30)) -> float32;
  * count[b] == 0 gives a NaN row.  out[e] is (nbins, T_e).  frame_major_rows > 0: mag[e] is the FRAME-MAJOR (T_e, F)
- * matrix of ira_stft_mag_db_tf with F = frame_major_rows (same results, same row order).
+ * matrix of ira_stft_mag_db_tf with F = frame_major_rows <= 8193 (same results, same row order).
  * Replaces _aggregate_to_log_bins, reference analyse/modalcloud.py:176-207. */
 int32_t ira_logbin_aggregate(const float* mag_dev, const int64_t* mag_off_dev, const int32_t* nframes_dev,
                              int32_t nb, int32_t max_frames, int32_t k_base, const int32_t* first_dev,
