@@ -8,13 +8,15 @@ namespace {
 
 // ------------------------------------------------------------------------------------------------
 // a2: argmax |x| with first-maximum-wins.  Key = (bits(|x|) << 32) | (0xFFFFFFFF - index):
-// unsigned 64-bit max picks the largest magnitude, then the smallest index.
+// unsigned 64-bit max picks the largest magnitude, then the smallest index.  Every NaN takes ONE key (above +Inf), so
+// that the first NaN wins whatever its payload, as in numpy.argmax(numpy.abs(x)).
 // ------------------------------------------------------------------------------------------------
 constexpr int PEAK_THREADS = 256;
 constexpr int PEAK_CHUNK = 16384;  // samples per workgroup
 
 __device__ __forceinline__ unsigned long long peak_key(float v, int64_t i) {
-  return ((unsigned long long)__float_as_uint(fabsf(v)) << 32) | (unsigned long long)(0xFFFFFFFFu - (uint32_t)i);
+  const uint32_t mag = (v != v) ? 0x7fc00000u : __float_as_uint(fabsf(v));
+  return ((unsigned long long)mag << 32) | (unsigned long long)(0xFFFFFFFFu - (uint32_t)i);
 }
 
 // Sixteen-byte loads, all of a thread's loads in flight together: the chunk is cut into a scalar head up to the first
@@ -696,7 +698,7 @@ __global__ void curve_fit_kernel(const float* __restrict__ ybase, const int64_t*
 // The records live in the first half of the segment's scratch (the tile totals, dead once edc_carry has run).
 // ------------------------------------------------------------------------------------------------
 constexpr int FITREC_HDR = 8;                                   // j_first, j_last, K (tiles per chunk), nchunks
-constexpr int FITREC_RANGE = 8;                                 // ts, te, tmid, ymid, a0, a1, ok, -
+constexpr int FITREC_RANGE = 8;                                 // ts, te, tmid, ymid, a0, a1, ok (2 = flat mask), flat value
 constexpr int FITREC_PART = FITREC_HDR + FITREC_RANGE * 4;      // partial moments: [chunk][range][6]
 constexpr int FIT_MAX_CHUNKS = 80;
 constexpr int FIT_MIN_CHUNK_TILES = 4;                          // 16 k samples per chunk at least
@@ -901,6 +903,7 @@ __global__ __launch_bounds__(EDC_THREADS) __attribute__((amdgpu_waves_per_eu(4, 
   if (tid < FIT_MAX_RANGES) {
     EdcFitRange g;
     g.ok = 0; g.ts = g.te = qnan; g.tmid = g.ymid = 0.0; g.ts32 = g.te32 = 0.0f; g.a0 = 0; g.a1 = -1; g.pad = 0;
+    double flat_y = 0.0;
     if (tid < P.nranges) {
       const int r = tid;
       const long long i_hi = sh.idx[2 * r], i_lo = sh.idx[2 * r + 1];
@@ -912,12 +915,23 @@ __global__ __launch_bounds__(EDC_THREADS) __attribute__((amdgpu_waves_per_eu(4, 
         g.a1 = i_lo + 2 < n - 1 ? i_lo + 2 : n - 1;
         g.tmid = 0.5 * (g.ts + g.te);
         g.ymid = 0.5 * (P.hi[r] + P.lo[r]);
+        // A mask whose values are all equal (a plateau of leading silence that drops through the whole range within one
+        // sample): the least-squares line is flat, slope exactly 0, which the reference refuses (slope >= 0).  The shifted
+        // moments would leave rounding noise of either sign in its place, so the case is flagged here, where the curve
+        // values at both ends of the mask are known: an EDC falls monotonically, so first == last means all equal.  The
+        // mask t >= float32(ts) & t <= float32(te) starts at i_hi (at i_hi - 1 when float32(ts) rounds down onto
+        // t[i_hi - 1]) and ends at i_lo - 1 (at i_lo when te is t[i_lo] itself); anything wider is left to the moments.
+        const float ts32 = (float)g.ts, te32 = (float)g.te;
+        const bool wider = (i_hi >= 2 && ta.at(i_hi - 2) >= ts32) || (i_lo + 1 < n && ta.at(i_lo + 1) <= te32);
+        const float first = (i_hi >= 1 && ta.at(i_hi - 1) >= ts32) ? sh.y_prev[2 * r] : sh.y_at[2 * r];
+        const float last = (ta.at(i_lo) <= te32) ? sh.y_at[2 * r + 1] : sh.y_prev[2 * r + 1];
+        if (!wider && first == last) { g.ok = 2; flat_y = (double)first; }
       }
     }
     sh.rng[tid] = g;
     double* rec = sc + FITREC_HDR + FITREC_RANGE * tid;
     rec[0] = g.ts; rec[1] = g.te; rec[2] = g.tmid; rec[3] = g.ymid;
-    rec[4] = (double)g.a0; rec[5] = (double)g.a1; rec[6] = (double)g.ok; rec[7] = 0.0;
+    rec[4] = (double)g.a0; rec[5] = (double)g.a1; rec[6] = (double)g.ok; rec[7] = flat_y;
   }
   __syncthreads();
   if (tid == 0) {
@@ -1060,6 +1074,10 @@ __global__ __launch_bounds__(256) void edc_line_kernel(int nseg, FitParams P, co
   const long long npts = (long long)cnt;
   if (npts < P.min_points) {
     o[0] = 0.0; o[1] = ts; o[2] = te; for (int k = 3; k < 7; ++k) o[k] = qnan; o[7] = (double)npts;
+    return;
+  }
+  if (rec[6] == 2.0 && npts >= 2) {                          // every value in the mask is rec[7]: a flat line, refused
+    o[0] = 0.0; o[1] = ts; o[2] = te; o[3] = 0.0; o[4] = rec[7]; o[5] = 0.0; o[6] = -INFINITY; o[7] = (double)npts;
     return;
   }
   // centred moments from the shifted sums (shift = mid-range: the subtractions lose nothing that matters in f64)

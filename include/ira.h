@@ -39,7 +39,8 @@ int32_t ira_abi_version(void);
 const char* ira_error_string(int32_t code);
 
 /* ---- a2: peak pick ---------------------------------------------------------------------------
- * peak_dev[s] = argmax_n |x[off[s]+n]|, n < len[s]; the FIRST maximum wins (bit-exact integer).
+ * peak_dev[s] = argmax_n |x[off[s]+n]|, n < len[s]; the FIRST maximum wins (bit-exact integer); a NaN beats every number
+ * and the first NaN wins whatever its payload (peak_abs_dev[s] is then NaN).
  * Replaces np.argmax(np.abs(x)) at reference analyse/decay.py:136, spectrogram.py:181,
  * waterfall.py:359, modalcloud.py:299, frequency_response.py:186, filterplot.py:125,
  * zplane.py:197, rt60bands.py:335.  Also returns the peak magnitude (zplane.py:211).
@@ -91,8 +92,10 @@ int32_t ira_curve_fits(const float* y_dev, const int64_t* off_dev, const int64_t
 
 /* Optional dB smoothing of the EDC (reference analyse/decay.py:159-166, default off): out[s][i] = float32(max(floor_db,
  * numpy.convolve(edc_db64[s], ones(window)/window, mode="same")[i])) on the unfloored float64 curve ira_edc_db writes
- * (edc_db64_dev); in and out share the offsets off_dev.  IRA_E_UNSUPPORTED when a segment is shorter than the window
- * (numpy's "same" then changes the length of the curve). */
+ * (edc_db64_dev); in and out share the offsets off_dev.  IRA_E_UNSUPPORTED when window > max_len.  The function sees the
+ * lengths on the device only: a segment of a ragged batch that is shorter than the window (where numpy's "same" returns
+ * `window` values instead of len) is NOT refused, its sums are clipped to the segment; the caller refuses such a request
+ * (analyse/decay.py and analyse/rt60bands.py raise ValueError when any analysed length is shorter than the window). */
 int32_t ira_edc_box_smooth(const double* edc_db64_dev, const int64_t* off_dev, const int64_t* len_dev, int32_t nseg,
                            int64_t max_len, int32_t window, double floor_db, float* out_dev, void* stream);
 
