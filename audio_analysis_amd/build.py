@@ -70,13 +70,19 @@ def build_tuning(verbose: bool = True) -> Path:
     out = CSRC / "libira_tuning.so"
     tmp = CSRC / "_tuning"
     tmp.mkdir(exist_ok=True)
+    cmds = []
     for name, extra in SOURCES.items():
         obj = tmp / (Path(name).stem + ".o")
-        cmd = [hipcc, *COMMON, "-DIRA_TUNING_BUILD", *extra, "-c", str(CSRC / name), "-o", str(obj)]
+        cmds.append([hipcc, *COMMON, "-DIRA_TUNING_BUILD", *extra, "-c", str(CSRC / name), "-o", str(obj)])
+        objs.append(obj)
+
+    def run(cmd):
         if verbose:
             print(" ".join(cmd), flush=True)
         subprocess.run(cmd, check=True)
-        objs.append(obj)
+
+    with ThreadPoolExecutor(max_workers=4) as ex:
+        list(ex.map(run, cmds))
     subprocess.run([hipcc, "-shared", "-fPIC", f"--offload-arch={ARCH}", *map(str, objs), "-o", str(out)], check=True)
     return out
 

@@ -20,8 +20,8 @@ int32_t ira_stft2_launch(const float* x, const int64_t* off, const int32_t* nfra
                          double floor_db, float* out, const int64_t* out_off, const int32_t* frame_sel,
                          const int64_t* sel_off, hipStream_t st);
 
-// stft5_kernel (ira_stft4.hip): float64 / n_fft 8192.  lb_nbins <= 0: the frame-major (T, F) dB matrix; lb_nbins > 0: the
-// (lb_nbins, T) log-bin curves of ira_stft_logbin
+// stft5_kernel (ira_stft4.hip): float64 / n_fft 8192, a grid of ceil(max_frames / 8) x nseg workgroups of eight consecutive
+// frames.  lb_nbins <= 0: the frame-major (T, F) dB matrix; lb_nbins > 0: the (lb_nbins, T) log-bin curves of ira_stft_logbin
 int32_t ira_stft5_launch(const float* x, const int64_t* off, const int32_t* nframes, int32_t nseg, int32_t max_frames,
                          int32_t hop, const void* window, const void* tw, double floor_db, float* out,
                          const int64_t* out_off, const int32_t* frame_sel, const int64_t* sel_off, int32_t lb_nbins,

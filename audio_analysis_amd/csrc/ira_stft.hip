@@ -138,7 +138,8 @@ int32_t launch_stft(const float* x, const int64_t* off, const int32_t* nframes, 
 //   ira_stft_mag_db_tf  (T, F)  f32 / 4096                         stft6_kernel  (ira_stft3.hip)
 //                               f64 / 8192                         stft5_kernel  (ira_stft4.hip)
 //   ira_stft_logbin             f64 / 8192                         stft5_kernel  (ira_stft4.hip)
-// Every other configuration of the last two is IRA_E_UNSUPPORTED.
+// Every other configuration of the last two is IRA_E_UNSUPPORTED.  stft5_kernel takes eight consecutive frames of a segment
+// per workgroup in both of its modes; its results do not depend on that number.
 extern "C" int32_t ira_stft_mag_db(const float* x_dev, const int64_t* off_dev, const int32_t* nframes_dev,
                                    int32_t nseg, int32_t max_frames, int32_t n_fft, int32_t hop,
                                    const void* window_dev, const void* twiddle_dev, int32_t precision,

@@ -1,6 +1,6 @@
 // stft5_kernel: the float64 / n_fft = 8192 STFT (the reference's modal-cloud default, modalcloud.py:121-158) with ONE FRAME
-// ON FOUR WAVES (256 lanes, 16 complex values per lane): frame-major (T, F) dB output, or (ira_stft_logbin) the modal
-// cloud's log-bin aggregation fused in.
+// ON FOUR WAVES (256 lanes, 16 complex values per lane), KF5 consecutive frames of a segment per workgroup: frame-major
+// (T, F) dB output, or (ira_stft_logbin) the modal cloud's log-bin aggregation fused in.
 // Transform: packed real FFT, z[n] = xw[2n] + i xw[2n+1], M = 4096 = 16 * 16 * 16, DIF, n = n1*256 + n2*16 + n3,
 // k = k1 + 16 k2 + 256 k3:
 //   step 1  lane m = q: 16-point DFT over n1 from global memory, twiddle W_M^(k1 m)
@@ -72,161 +72,62 @@ __device__ __forceinline__ double lin_of4(double re, double im, double floor_pow
 }
 
 constexpr int TL5 = 256;
+// Frames per workgroup (tuning build: IRA_STFT5_K).  Measured on the report step and on the kernel alone at 2, 4, 8, 16
+// (profiles/stft5_chunks_ab.txt): 8 is the fastest on both.  It amortises 7/8 of the per-workgroup set-up; at 16 the
+// coarser tail of the launch (14.5 rounds of the 1024 resident workgroups) costs more than the last sixteenth saves.
+constexpr int KF5 = 8;
 
+// Two neighbouring samples / window values in one load.  A frame starts at any sample (segment offset + peak index +
+// frame * hop), so a sample pair is 4-byte aligned only; the window table is only known to be a double array.
+struct __attribute__((aligned(4))) fpair5 { float a, b; };
+struct __attribute__((aligned(8))) dpair5 { double a, b; };
+
+// One workgroup transforms kfr CONSECUTIVE frames of one segment, one after the other.  Everything that does not depend on
+// the frame is done once, before the frame loop: the XCD remap and (segment, chunk) decode, the segment's job values (as
+// scalars), the log2 table in LDS, the hull of the log bins and 10^(floor/20).  Only scalar state lives across the loop:
+// the frame's twiddle factors are reloaded per frame (they hit the caches), the frame alone needs 122 of the 128 VGPRs.
+// The loop body is the frame as described at the top of the file, barrier for barrier; its trip count is wave-uniform,
+// so every wave of the workgroup meets the same barriers.  The results do not depend on kfr: a frame's arithmetic reads
+// nothing of its neighbours.
 __global__ __launch_bounds__(TL5) __attribute__((amdgpu_waves_per_eu(4, 4))) void stft5_kernel(
     const float* __restrict__ x, const int64_t* __restrict__ off, const int32_t* __restrict__ nframes, int hop,
     const double* __restrict__ window, const cdd* __restrict__ tw, double floor_lin, float floor_db,
     float* __restrict__ out, const int64_t* __restrict__ out_off, const int32_t* __restrict__ frame_sel,
     const int64_t* __restrict__ sel_off, int lb_nbins, int lb_kbase, const int32_t* __restrict__ lb_first,
-    const int32_t* __restrict__ lb_count, int ablate) {
+    const int32_t* __restrict__ lb_count, int kfr, int ablate) {
   // ablate (IRA_STFT5_ABLATE, tuning build, timing only): 1 no window loads, 2 no sample loads, 4 no dB -> linear conversion
   __shared__ __attribute__((aligned(16))) cdd ex[EXC4];
   __shared__ ira::LogTabEntry ltab[ira::LOGTAB_N];
   __shared__ int lb_range[2];
   __shared__ int frame_bad;
+  // XCD-aware remap: the workgroups of one XCD (orig % 8) take a contiguous run of chunks, so that neighbouring chunks,
+  // whose frames overlap, share an L2
   const unsigned gx = gridDim.x, nwg = gridDim.x * gridDim.y;
   const unsigned orig = blockIdx.y * gx + blockIdx.x;
   const unsigned xq = nwg / 8, xr = nwg % 8, xcd = orig % 8;
   const unsigned wg = (xcd < xr ? xcd * (xq + 1) : xr * (xq + 1) + (xcd - xr) * xq) + orig / 8;
   const int seg = (int)(wg / gx);
-  const int col = (int)(wg % gx);
-  const int T_out = nframes[seg];
-  if (col >= T_out) return;
-  const int q = threadIdx.x;
+  const int col0 = (int)(wg % gx) * kfr;
+  const int T_out = ira::uniform(nframes[seg]);
+  if (col0 >= T_out) return;                       // the whole workgroup, before its first barrier
+  const int col1 = T_out - col0 < kfr ? T_out : col0 + kfr;
+  int q = threadIdx.x;
   double* exd = reinterpret_cast<double*>(ex);
   ira::build_log_table(ltab, q);
   if (q < 2) lb_range[q] = q == 0 ? F4 : 0;
 
-  const int64_t frame = frame_sel ? (int64_t)frame_sel[sel_off[seg] + col] : (int64_t)col;
-  const float* fx = x + off[seg] + frame * hop;
-  const int k1l = q & 15, n3l = q >> 4;            // step-2 role: (k1, n3)
-  const bool lower = q < TL4;                      // lanes whose step-1 / step-2 results go through the buffer first
-  // The eight wave-uniform factors W_N^(256 i) of the post step, requested HERE: they compile to scalar loads, and placed
-  // at their use each one stalled its wave for a scalar-cache round trip (s_waitcnt lgkmcnt(0), which also drains the LDS
-  // queue) in the middle of the conversion loop -- eight serial stalls per frame and wave.
-  cdd wuni[8];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) wuni[i] = tw[TL5 * i];
-
-  // ---- step 1 -------------------------------------------------------------------------------------------------
-  cdd v[16];
-  {
-    float xa[16], xb[16];
-    double wa[16], wb[16];
-#pragma unroll
-    for (int n1 = 0; n1 < 16; ++n1) {
-      const int n = n1 * 256 + q;
-      if (IRA_ABL(ablate & 2)) { xa[n1] = (float)(n & 7) * 0.125f; xb[n1] = (float)(q & 3); }
-      else { xa[n1] = fx[2 * n]; xb[n1] = fx[2 * n + 1]; }
-      if (IRA_ABL(ablate & 1)) { wa[n1] = 0.5 + 1e-4 * n1; wb[n1] = 0.25; }
-      else { wa[n1] = window[2 * n]; wb[n1] = window[2 * n + 1]; }
-    }
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int n1 = 0; n1 < 16; ++n1) v[n1] = {(double)xa[n1] * wa[n1], (double)xb[n1] * wb[n1]};
-  }
-  dft_dif<double, 16>(v);
-  ira::twiddle16<double, true>(v, tw[2 * q]);                 // W_M^(k1 q) = W_N^(2 q k1), k1 at v[brev(k1)]
-
-  // ---- E1: half-size exchange, lower lanes first ----------------------------------------------------------------
-  cdd b[16];
-  if (lower) {
-#pragma unroll
-    for (int k1 = 0; k1 < 16; ++k1) ex[k1 * ROW4 + q] = v[brev_bits(k1, 4)];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int n2 = 0; n2 < 8; ++n2) b[n2] = ex[k1l * ROW4 + n2 * 16 + n3l];
-  __syncthreads();
-  if (!lower) {
-#pragma unroll
-    for (int k1 = 0; k1 < 16; ++k1) ex[k1 * ROW4 + (q - TL4)] = v[brev_bits(k1, 4)];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int n2 = 0; n2 < 8; ++n2) b[8 + n2] = ex[k1l * ROW4 + n2 * 16 + n3l];
-  __syncthreads();
-
-  // ---- step 2 and E2 ---------------------------------------------------------------------------------------------
-  dft_dif<double, 16>(b);
-  ira::twiddle16<double, true>(b, tw[32 * n3l]);              // W_M^(16 k2 n3) = W_N^(32 n3 k2)
-  if (lower) {                                                 // n3 < 8
-#pragma unroll
-    for (int k2 = 0; k2 < 16; ++k2) ex[k1l + 16 * k2 + E2N4 * n3l] = b[brev_bits(k2, 4)];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int n3 = 0; n3 < 8; ++n3) v[n3] = ex[q + E2N4 * n3];
-  __syncthreads();
-  if (!lower) {
-#pragma unroll
-    for (int k2 = 0; k2 < 16; ++k2) ex[k1l + 16 * k2 + E2N4 * (n3l - 8)] = b[brev_bits(k2, 4)];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int n3 = 0; n3 < 8; ++n3) v[8 + n3] = ex[q + E2N4 * n3];
-  __syncthreads();
-
-  // ---- step 3: lane r = q holds Z[r + 256 k3] at v[brev(k3)] ----------------------------------------------------------
-  dft_dif<double, 16>(v);
-
-  // ---- E3: the mirror partners only.  The post step pairs Z[k] with Z[M - k]; lane q keeps k = q + 256 i, i < 8, which it
-  // already holds (v[brev(i)]), and M - k = (256 - q) + 256 (15 - i) is entry k3 = 15 - i >= 8 of lane 256 - q: every lane
-  // publishes its upper eight values and reads eight of its partner's -- 256 bytes per lane through LDS and one barrier pair
-  // instead of the 512 bytes and two of the round-2 natural-order exchange (real parts, then imaginary parts, own values
-  // included).  Lane 0 pairs with itself: M - 256 i = 256 (16 - i), its own entry 16 - i; i = 0 pairs Z[0] with Z[0].
-  double zkr[8], zpr[8], zki[8], zpi[8], midr, midi;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) ex[j * TL5 + q] = v[brev_bits(8 + j, 4)];       // k3 = 8 + j
-  __syncthreads();
-  {
-    const int partner = (TL5 - q) & (TL5 - 1);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      // partner entry k3 = 15 - i (slot 7 - i); lane 0: k3 = 16 - i (slot 8 - i), i = 0 -> Z[0] itself
-      const int slot = q == 0 ? 8 - i : 7 - i;
-      cdd zp = v[0];                                                             // Z[0] (lane 0, i = 0)
-      if (!(q == 0 && i == 0)) zp = ex[slot * TL5 + partner];
-      zkr[i] = v[brev_bits(i, 4)].re; zki[i] = v[brev_bits(i, 4)].im;
-      zpr[i] = zp.re; zpi[i] = zp.im;
-    }
-  }
-  {
-    const cdd mid = ex[0];                                                       // Z[2048]: lane 0, k3 = 8
-    midr = mid.re; midi = mid.im;
-  }
-  // A NaN (or infinite) sample anywhere in the frame makes every bin of numpy's rfft NaN (modalcloud.py:150): it shows in
-  // Z[0] = sum of the packed inputs (lane 0, first pair; 0 * NaN at the Hann end points is NaN too).  One check per frame.
-  if (q == 0) frame_bad = !((zkr[0] - zkr[0]) + (zki[0] - zki[0]) == 0.0) ? 1 : 0;
-  __syncthreads();                                            // E3 fully read; frame_bad, lb_range visible
-  const bool bad_frame = frame_bad != 0;
-  const float qnan32 = __uint_as_float(0x7fc00000u);
-
-  // ---- post ---------------------------------------------------------------------------------------------------
+  const float* xs = x + ira::uniform(off[seg]);
+  float* os = out + ira::uniform(out_off[seg]);
+  const int32_t* fsel = frame_sel ? frame_sel + ira::uniform(sel_off[seg]) : nullptr;
   const double floor_pow = floor_lin * floor_lin;
-  const cdd wlane = tw[q];
-  if (lb_nbins <= 0) {
-    float* fo = out + out_off[seg] + (int64_t)col * F4;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      const int k = q + TL5 * i;
-      const cdd e = {0.5 * (zkr[i] + zpr[i]), 0.5 * (zki[i] - zpi[i])};
-      const cdd d = {0.5 * (zkr[i] - zpr[i]), 0.5 * (zki[i] + zpi[i])};
-      const cdd o = {d.im, -d.re};
-      const cdd wk = ira::cmul(wlane, wuni[i]);              // W_N^k = W_N^q W_N^(256 i); second factor wave-uniform
-      const cdd pp = ira::cmul(wk, o);
-      fo[k] = bad_frame ? qnan32 : db_of4(e.re + pp.re, e.im + pp.im, floor_pow, floor_db, ltab);
-      fo[M4 - k] = bad_frame ? qnan32 : db_of4(e.re - pp.re, e.im - pp.im, floor_pow, floor_db, ltab);   // k = 0 -> bin M
-    }
-    if (q == 0) fo[M4 / 2] = bad_frame ? qnan32 : db_of4(midr, midi, floor_pow, floor_db, ltab);
-    return;
-  }
-  // ---- fused modal-cloud aggregation (reference modalcloud.py:176-207): the frame's dB values never leave the CU.
-  // float32 dB (the reference's STFT output type) -> linear magnitude 10^(dB/20) in float64 -> LDS; then log bin b is
-  // the mean of its rows, added in ascending order, -> 20 log10(max(., 1e-30)) -> float32 at out[b * T + frame].
-  // Only the rows some log bin reads are converted: 20 Hz .. 20 kHz is rows 4 .. 3413 of 4097, a sixth of the
-  // conversions (the costliest part of the frame) is skipped.
-  {
+  const float qnan32 = __uint_as_float(0x7fc00000u);
+  // Log-bin mode: the hull [k_lo, k_hi) of the rows some log bin reads, and the linear value of a floored row.  Only the
+  // hull's rows are converted: 20 Hz .. 20 kHz is rows 4 .. 3413 of 4097, a sixth of the conversions (the costliest part
+  // of the frame) is skipped.
+  int k_lo = 0, k_hi = 0;
+  double floor_lin32 = 0.0;
+  __syncthreads();                                 // lb_range initialised
+  if (lb_nbins > 0) {
     int lo = F4, hi = 0;
     for (int bb = q; bb < lb_nbins; bb += TL5) {
       const int c = lb_count[bb];
@@ -238,50 +139,190 @@ __global__ __launch_bounds__(TL5) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     }
     atomicMin(&lb_range[0], lo);
     atomicMax(&lb_range[1], hi);
+    __syncthreads();
+    k_lo = ira::uniform(lb_range[0]);
+    k_hi = ira::uniform(lb_range[1]);
+    floor_lin32 = ira::uniform(exp10((double)floor_db * 0.05));
   }
-  __syncthreads();
-  const int k_lo = lb_range[0], k_hi = lb_range[1];
-  const double floor_lin32 = exp10((double)floor_db * 0.05);
+
+  for (int col = col0; col < col1; ++col) {
+    // The lane index passes through an empty asm statement in every frame, so that the compiler derives the lane's
+    // addresses, twiddle factors and masks inside the frame, as a one-frame kernel does.  Hoisted out of the loop they
+    // stay live across it, and the frame (122 of the 128 VGPRs that four waves per SIMD allow) has no room for them.
+    asm volatile("" : "+v"(q));
+    const int k1l = q & 15, n3l = q >> 4;          // step-2 role: (k1, n3)
+    const bool lower = q < TL4;                    // lanes whose step-1 / step-2 results go through the buffer first
+    const int64_t frame = fsel ? (int64_t)ira::uniform(fsel[col]) : (int64_t)col;
+    const float* fx = xs + frame * hop;
+    // The eight wave-uniform factors W_N^(256 i) of the post step, requested HERE: they compile to scalar loads, and placed
+    // at their use each one stalled its wave for a scalar-cache round trip (s_waitcnt lgkmcnt(0), which also drains the LDS
+    // queue) in the middle of the conversion loop.  Loaded per frame (their index passes through an empty asm statement):
+    // 32 scalar registers held across the loop would spill.
+    int u0 = 0;
+    asm volatile("" : "+s"(u0));
+    cdd wuni[8];
 #pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const int k = q + TL5 * i;
-    const bool need_a = k >= k_lo && k < k_hi, need_b = (M4 - k) >= k_lo && (M4 - k) < k_hi;
-    if (!need_a && !need_b) continue;
-    const cdd e = {0.5 * (zkr[i] + zpr[i]), 0.5 * (zki[i] - zpi[i])};
-    const cdd d = {0.5 * (zkr[i] - zpr[i]), 0.5 * (zki[i] + zpi[i])};
-    const cdd o = {d.im, -d.re};
-    const cdd wk = ira::cmul(wlane, wuni[i]);
-    const cdd pp = ira::cmul(wk, o);
-    if (IRA_ABL(ablate & 4)) {
-      if (need_a) exd[k] = e.re + pp.re;
-      if (need_b) exd[M4 - k] = e.im - pp.im;
+    for (int i = 0; i < 8; ++i) wuni[i] = tw[TL5 * i + u0];
+
+    // ---- step 1 -----------------------------------------------------------------------------------------------
+    cdd v[16];
+    {
+      float xa[16], xb[16];
+      double wa[16], wb[16];
+#pragma unroll
+      for (int n1 = 0; n1 < 16; ++n1) {
+        const int n = n1 * 256 + q;
+        if (IRA_ABL(ablate & 2)) { xa[n1] = (float)(n & 7) * 0.125f; xb[n1] = (float)(q & 3); }
+        else { const fpair5 p = *reinterpret_cast<const fpair5*>(fx + 2 * n); xa[n1] = p.a; xb[n1] = p.b; }
+        if (IRA_ABL(ablate & 1)) { wa[n1] = 0.5 + 1e-4 * n1; wb[n1] = 0.25; }
+        else { const dpair5 w = *reinterpret_cast<const dpair5*>(window + 2 * n); wa[n1] = w.a; wb[n1] = w.b; }
+      }
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int n1 = 0; n1 < 16; ++n1) v[n1] = {(double)xa[n1] * wa[n1], (double)xb[n1] * wb[n1]};
+    }
+    dft_dif<double, 16>(v);
+    ira::twiddle16<double, true>(v, tw[2 * q]);                 // W_M^(k1 q) = W_N^(2 q k1), k1 at v[brev(k1)]
+
+    // ---- E1: half-size exchange, lower lanes first --------------------------------------------------------------
+    cdd b[16];
+    if (lower) {
+#pragma unroll
+      for (int k1 = 0; k1 < 16; ++k1) ex[k1 * ROW4 + q] = v[brev_bits(k1, 4)];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int n2 = 0; n2 < 8; ++n2) b[n2] = ex[k1l * ROW4 + n2 * 16 + n3l];
+    __syncthreads();
+    if (!lower) {
+#pragma unroll
+      for (int k1 = 0; k1 < 16; ++k1) ex[k1 * ROW4 + (q - TL4)] = v[brev_bits(k1, 4)];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int n2 = 0; n2 < 8; ++n2) b[8 + n2] = ex[k1l * ROW4 + n2 * 16 + n3l];
+    __syncthreads();
+
+    // ---- step 2 and E2 -------------------------------------------------------------------------------------------
+    dft_dif<double, 16>(b);
+    ira::twiddle16<double, true>(b, tw[32 * n3l]);              // W_M^(16 k2 n3) = W_N^(32 n3 k2)
+    if (lower) {                                                 // n3 < 8
+#pragma unroll
+      for (int k2 = 0; k2 < 16; ++k2) ex[k1l + 16 * k2 + E2N4 * n3l] = b[brev_bits(k2, 4)];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int n3 = 0; n3 < 8; ++n3) v[n3] = ex[q + E2N4 * n3];
+    __syncthreads();
+    if (!lower) {
+#pragma unroll
+      for (int k2 = 0; k2 < 16; ++k2) ex[k1l + 16 * k2 + E2N4 * (n3l - 8)] = b[brev_bits(k2, 4)];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int n3 = 0; n3 < 8; ++n3) v[8 + n3] = ex[q + E2N4 * n3];
+    __syncthreads();
+
+    // ---- step 3: lane r = q holds Z[r + 256 k3] at v[brev(k3)] --------------------------------------------------------
+    dft_dif<double, 16>(v);
+
+    // ---- E3: the mirror partners only.  The post step pairs Z[k] with Z[M - k]; lane q keeps k = q + 256 i, i < 8, which
+    // it already holds (v[brev(i)]), and M - k = (256 - q) + 256 (15 - i) is entry k3 = 15 - i >= 8 of lane 256 - q: every
+    // lane publishes its upper eight values and reads eight of its partner's -- 256 bytes per lane through LDS and one
+    // barrier pair instead of the 512 bytes and two of the round-2 natural-order exchange (real parts, then imaginary
+    // parts, own values included).  Lane 0 pairs with itself: M - 256 i = 256 (16 - i), its own entry 16 - i; i = 0 pairs
+    // Z[0] with Z[0].
+    double zkr[8], zpr[8], zki[8], zpi[8], midr, midi;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) ex[j * TL5 + q] = v[brev_bits(8 + j, 4)];       // k3 = 8 + j
+    __syncthreads();
+    {
+      const int partner = (TL5 - q) & (TL5 - 1);
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        // partner entry k3 = 15 - i (slot 7 - i); lane 0: k3 = 16 - i (slot 8 - i), i = 0 -> Z[0] itself
+        const int slot = q == 0 ? 8 - i : 7 - i;
+        cdd zp = v[0];                                                             // Z[0] (lane 0, i = 0)
+        if (!(q == 0 && i == 0)) zp = ex[slot * TL5 + partner];
+        zkr[i] = v[brev_bits(i, 4)].re; zki[i] = v[brev_bits(i, 4)].im;
+        zpr[i] = zp.re; zpi[i] = zp.im;
+      }
+    }
+    {
+      const cdd mid = ex[0];                                                       // Z[2048]: lane 0, k3 = 8
+      midr = mid.re; midi = mid.im;
+    }
+    // A NaN (or infinite) sample anywhere in the frame makes every bin of numpy's rfft NaN (modalcloud.py:150): it shows
+    // in Z[0] = sum of the packed inputs (lane 0, first pair; 0 * NaN at the Hann end points is NaN too).  One check per
+    // frame, written by lane 0 for EVERY frame: the flag of a bad frame does not outlive it.
+    if (q == 0) frame_bad = !((zkr[0] - zkr[0]) + (zki[0] - zki[0]) == 0.0) ? 1 : 0;
+    __syncthreads();                                            // E3 fully read; frame_bad visible
+    const bool bad_frame = frame_bad != 0;
+
+    // ---- post -------------------------------------------------------------------------------------------------
+    const cdd wlane = tw[q];
+    if (lb_nbins <= 0) {
+      // no barrier at the loop's tail here: the next frame's first LDS write (E1; frame_bad is written later still)
+      // follows the barrier above, behind which this frame reads only the table
+      float* fo = os + (int64_t)col * F4;
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        const int k = q + TL5 * i;
+        const cdd e = {0.5 * (zkr[i] + zpr[i]), 0.5 * (zki[i] - zpi[i])};
+        const cdd d = {0.5 * (zkr[i] - zpr[i]), 0.5 * (zki[i] + zpi[i])};
+        const cdd o = {d.im, -d.re};
+        const cdd wk = ira::cmul(wlane, wuni[i]);              // W_N^k = W_N^q W_N^(256 i); second factor wave-uniform
+        const cdd pp = ira::cmul(wk, o);
+        fo[k] = bad_frame ? qnan32 : db_of4(e.re + pp.re, e.im + pp.im, floor_pow, floor_db, ltab);
+        fo[M4 - k] = bad_frame ? qnan32 : db_of4(e.re - pp.re, e.im - pp.im, floor_pow, floor_db, ltab);   // k = 0 -> bin M
+      }
+      if (q == 0) fo[M4 / 2] = bad_frame ? qnan32 : db_of4(midr, midi, floor_pow, floor_db, ltab);
       continue;
     }
-    if (need_a) exd[k] = lin_of4(e.re + pp.re, e.im + pp.im, floor_pow, floor_db, floor_lin32, ltab);
-    if (need_b) exd[M4 - k] = lin_of4(e.re - pp.re, e.im - pp.im, floor_pow, floor_db, floor_lin32, ltab);
-  }
-  if (q == 0 && M4 / 2 >= k_lo && M4 / 2 < k_hi) exd[M4 / 2] = lin_of4(midr, midi, floor_pow, floor_db, floor_lin32, ltab);
-  __syncthreads();
-  float* co = out + out_off[seg];
-  for (int bb = q; bb < lb_nbins; bb += TL5) {
-    const int c = lb_count[bb];
-    float val = qnan32;
-    if (c > 0) {
-      const double* r = exd + lb_kbase + lb_first[bb];
-      double acc = r[0];
-      for (int k0 = 1; k0 < c; k0 += 8) {
-        double v8[8];
+    // ---- fused modal-cloud aggregation (reference modalcloud.py:176-207): the frame's dB values never leave the CU.
+    // float32 dB (the reference's STFT output type) -> linear magnitude 10^(dB/20) in float64 -> LDS; then log bin b is
+    // the mean of its rows, added in ascending order, -> 20 log10(max(., 1e-30)) -> float32 at out[b * T + frame].
 #pragma unroll
-        for (int u = 0; u < 8; ++u) v8[u] = (k0 + u < c) ? r[k0 + u] : 0.0;
-#pragma unroll
-        for (int u = 0; u < 8; ++u)
-          if (k0 + u < c) acc += v8[u];
+    for (int i = 0; i < 8; ++i) {
+      const int k = q + TL5 * i;
+      const bool need_a = k >= k_lo && k < k_hi, need_b = (M4 - k) >= k_lo && (M4 - k) < k_hi;
+      if (!need_a && !need_b) continue;
+      const cdd e = {0.5 * (zkr[i] + zpr[i]), 0.5 * (zki[i] - zpi[i])};
+      const cdd d = {0.5 * (zkr[i] - zpr[i]), 0.5 * (zki[i] + zpi[i])};
+      const cdd o = {d.im, -d.re};
+      const cdd wk = ira::cmul(wlane, wuni[i]);
+      const cdd pp = ira::cmul(wk, o);
+      if (IRA_ABL(ablate & 4)) {
+        if (need_a) exd[k] = e.re + pp.re;
+        if (need_b) exd[M4 - k] = e.im - pp.im;
+        continue;
       }
-      // 20 log10 m through the table log2 (series to r^6: a few 1e-16 relative, invisible after the float32 rounding) --
-      // the library log10 was ~130 of the ~1800 instructions of every wave although only 240 lanes of a frame use it
-      val = (float)(6.0205999132796239 * ira::log2_table<6>(fmax(acc / (double)c, 1e-30), ltab));
+      if (need_a) exd[k] = lin_of4(e.re + pp.re, e.im + pp.im, floor_pow, floor_db, floor_lin32, ltab);
+      if (need_b) exd[M4 - k] = lin_of4(e.re - pp.re, e.im - pp.im, floor_pow, floor_db, floor_lin32, ltab);
     }
-    co[(int64_t)bb * T_out + col] = (bad_frame && c > 0) ? qnan32 : val;
+    if (q == 0 && M4 / 2 >= k_lo && M4 / 2 < k_hi) exd[M4 / 2] = lin_of4(midr, midi, floor_pow, floor_db, floor_lin32, ltab);
+    __syncthreads();
+    for (int bb = q; bb < lb_nbins; bb += TL5) {
+      const int c = lb_count[bb];
+      float val = qnan32;
+      if (c > 0) {
+        const double* r = exd + lb_kbase + lb_first[bb];
+        double acc = r[0];
+        for (int k0 = 1; k0 < c; k0 += 8) {
+          double v8[8];
+#pragma unroll
+          for (int u = 0; u < 8; ++u) v8[u] = (k0 + u < c) ? r[k0 + u] : 0.0;
+#pragma unroll
+          for (int u = 0; u < 8; ++u)
+            if (k0 + u < c) acc += v8[u];
+        }
+        // 20 log10 m through the table log2 (series to r^6: a few 1e-16 relative, invisible after the float32 rounding) --
+        // the library log10 was ~130 of the ~1800 instructions of every wave although only 240 lanes of a frame use it
+        val = (float)(6.0205999132796239 * ira::log2_table<6>(fmax(acc / (double)c, 1e-30), ltab));
+      }
+      os[(int64_t)bb * T_out + col] = (bad_frame && c > 0) ? qnan32 : val;
+    }
+    __syncthreads();                               // the sums have read the buffer the next frame's E1 writes
   }
 }
 
@@ -292,9 +333,11 @@ int32_t ira_stft5_launch(const float* x, const int64_t* off, const int32_t* nfra
                          const int64_t* out_off, const int32_t* frame_sel, const int64_t* sel_off, int32_t lb_nbins,
                          int32_t lb_kbase, const int32_t* lb_first, const int32_t* lb_count, hipStream_t st) {
   const double floor_lin = std::pow(10.0, floor_db / 20.0);
-  dim3 grid(max_frames, nseg);
+  int kfr = ira_tune_int("IRA_STFT5_K", KF5);
+  if (kfr < 1) kfr = 1;
+  dim3 grid((max_frames + kfr - 1) / kfr, nseg);
   stft5_kernel<<<grid, TL5, (size_t)ira_tune_int("IRA_STFT5_LDS_PAD", 0), st>>>(x, off, nframes, hop, static_cast<const double*>(window),
                                      static_cast<const cdd*>(tw), floor_lin, (float)floor_db, out, out_off, frame_sel,
-                                     sel_off, lb_nbins, lb_kbase, lb_first, lb_count, ira_tune_int("IRA_STFT5_ABLATE", 0));
+                                     sel_off, lb_nbins, lb_kbase, lb_first, lb_count, kfr, ira_tune_int("IRA_STFT5_ABLATE", 0));
   IRA_RETURN_LAUNCH();
 }
