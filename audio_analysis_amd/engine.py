@@ -8,14 +8,18 @@ single-channel drop-in functions in audio_analysis_amd.analyse.* call them with 
 """
 from __future__ import annotations
 
+import ctypes
 import os
-from dataclasses import dataclass
+from contextlib import contextmanager
+from dataclasses import dataclass, fields
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
 from . import _lib
 from ._lib import IraError, check
+from .engine_plan import (SMOOTH, Switches, conv_size, exclusive_cumsum, pair_bands, plan_band_irfft,  # noqa: F401
+                          plan_rfft)
 
 FIT_DOUBLES = 8
 EDC_SCRATCH_DOUBLES = 4096
@@ -24,6 +28,12 @@ EDC_TILE = 4096
 
 def _ptr(t) -> int:
     return 0 if t is None else int(t.data_ptr())
+
+
+def _unit_roots(count: int, period: int) -> np.ndarray:
+    """exp(-2 pi i k / period), k < count: float64 (count, 2), interleaved (re, im)."""
+    ang = -2.0 * np.pi * np.arange(count, dtype=np.float64) / float(period)
+    return np.stack([np.cos(ang), np.sin(ang)], axis=1)
 
 
 @dataclass
@@ -120,39 +130,114 @@ def get_engine() -> "Engine":
     return _ENGINE
 
 
-def conv_size(need: int, three_pow2: bool = True) -> int:
-    """Smallest Bluestein convolution size the library takes (ira_fft_split: 2^k, or 3 * 2^k when allowed) that holds
-    `need` distinct lags; at least 16."""
-    need = max(int(need), 16)
-    m = 1 << int(need - 1).bit_length()
-    if three_pow2 and m >= 128 and 3 * (m >> 2) >= need:
-        m = 3 * (m >> 2)
-    return m
-
-
 class Engine:
+    # ------------------------------------------------------------------ A/B switches and budgets
+    # Class defaults; assign on an engine to take the alternative path (tests/test_gpu_longfft.py checks every default
+    # path against its alternative).  The environment overrides of some of them are read in _init_state.
+    #
+    # A channel's transforms are its own.  Round 2 let two real signals of equal length from DIFFERENT channels share one
+    # complex transform (z = x1 + i*x2) and the odd band of one channel share an inverse with the odd band of another:
+    # cheaper by half, but then the last bits of a channel's spectrum depend on which channel happened to be its partner,
+    # i.e. on batch composition and shard boundaries (SURVEY.md section 8e asks for byte-identical records for every
+    # world size).  Now a single real signal of EVEN length rides a HALF-length complex transform instead (x[2m] + i
+    # x[2m+1]: the same saving), bands are paired only within one channel, and an odd band out takes the half-length
+    # inverse.  pair_across_channels = True restores round 2's pairing (A/B; results then agree to ~1e-16 of the larger
+    # signal, not bit for bit).  pair_real_ffts = False additionally forbids pairing the bands of one channel.
+    pair_real_ffts = True
+    pair_across_channels = False
+    # A real signal of EVEN (non-smooth) length L is transformed as the complex sequence x[2m] + i*x[2m+1] of length
+    # L/2 (half the Bluestein convolution size) and split with a twiddle.  Set False for an A/B.
+    half_real_ffts = True
+    # The untangling X[k] = E[k] + W^k O[k] of such a half-length transform happens where Z[k] and Z[n - k] already meet:
+    # in the second pass of the direct transform (smooth lengths), and in the dB / phase kernel for the Bluestein spectra of
+    # the fr / filter blocks (packed spectra).  False restores round 3's separate split passes (A/B).
+    fuse_half_split = True
+    # Band inverses of smooth lengths: jobs whose bands span few bins (third-octave bands below ~800 Hz of a 10 s file)
+    # skip the first pass and the n-point work array (ira_band_irfft_smooth, job_info_dev).  False = both passes for every
+    # job (A/B).
+    sparse_bands = True
+    # Lengths of the form 2^a 3^b 5^c that split into two factors <= 1024 (480000, 2^19, ...) take the direct two-pass
+    # mixed-radix transform (ira_rfft_smooth / ira_band_irfft_smooth) instead of Bluestein.  Set False for an A/B.
+    smooth_ffts = True
+    # Convolution sizes the Bluestein kernels take: 2^k and 3 * 2^k.  three_pow2_sizes = False restricts the choice to
+    # powers of two (round 2's behaviour; A/B).
+    three_pow2_sizes = True
+    # round 5: the band inverses can leave the energies of their signals' EDC tiles for ira_edc_fits, which then reads a
+    # band signal once less.  Measured (profiles/r05_tile_energies.txt, config 3): ira_edc_fits 6.66 -> 5.40 ms per step,
+    # but the second pass pays 1.6 ms for forming the partials (a serial tail of every tile): 28.2 -> 28.6 ms of device
+    # time.  OFF by default; IRA_BAND_TILE_ENERGIES=1 / this attribute is the A/B switch.
+    band_tile_energies = False
+    # Normal equations lose cond(A)^2 eps; above this cond(G) estimate the fit gets refinement steps (ira_ar_refine).
+    # Rank-deficient Gram matrices (Cholesky pivot <= 0) get the minimum-norm solution lstsq returns (ira_ar_minnorm):
+    # eigen-directions with lambda <= cut * lambda_max are dropped.  0 disables the fallback.
+    ar_minnorm_cut = 1e-12
+    # A/B: form the Gram matrix as a dense contraction on the FP64 matrix cores (IRA_AR_DENSE_GRAM) instead of the lag sums
+    ar_dense_gram = False
+    # A/B: the 256-thread solve kernel also for order <= 64 (default there since round 4: one wave per element, same bits)
+    ar_workgroup_solve = False
+    ar_refine_cond = 1e9          # on the estimate trace(G) ||G^-1|| (<= order * cond(G))
+    ar_refine_steps = 2
+    # Above this estimate (or when the float64 Cholesky breaks down) the normal equations are solved again in double-double
+    # arithmetic (ira_ar_exact): refinement needs cond(G) eps << 1.  0 disables the path (A/B).
+    ar_exact_cond = 1e13
+    # Chirp-filter spectra depend only on (length, M): they are PLAN data, like twiddle tables, and are kept in LRU pools
+    # of device slots -- one pool per (M, stream), all pools together within filter_cache_bytes -- so that repeated
+    # lengths (every step of a batch job, every band pair of a file) do not rebuild them.  A pool starts at twice the
+    # slots its first call needs and doubles when a call needs more; when the budget is full the pools used least
+    # recently are dropped.  filter_cache_bytes = 0 disables the cache.
+    filter_cache_bytes = 16 << 30
+    workspace_budget_bytes = 48 << 30   # cap for the Bluestein work + filter arrays of one chunk
+
     def __init__(self, device: Optional[str] = None):
         import torch
 
-        self.lib = _TimedLib(_lib.load(), self)
-        self.events = None          # list of (name, start_event, end_event) while timing is on
-        self.event_tag = ""
+        lib = _TimedLib(_lib.load(), self)
         if not torch.cuda.is_available():
             raise IraError("audio_analysis_amd needs an AMD GPU (torch.cuda.is_available() is False); "
                            "there is no CPU fallback for the product path.")
-        self.torch = torch
-        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-        self._tables: Dict[Tuple, object] = {}
+        self._init_state(torch, torch.device(device) if device is not None
+                         else torch.device("cuda", torch.cuda.current_device()), lib)
+
+    def _init_state(self, torch, device, lib) -> None:
+        """Every attribute an engine has, and every environment switch it reads (the whole of construction but for the
+        GPU check: tests/host_engine.py builds an engine on host memory through this)."""
+        self.torch, self.device, self.lib = torch, device, lib
+        self.events = None          # list of (name, start_event, end_event) while timing is on
+        self.event_tag = ""
+        self._tables: Dict[Tuple, object] = {}          # _cached: tables on the device, and host facts about sizes
         self._filter_pools: Dict[tuple, dict] = {}      # (M, stream) -> pool, see _filter_pool
         self._filter_tick = 0
-        self._ring = None
-        # round 5: the band inverses can leave the energies of their signals' EDC tiles for ira_edc_fits, which then reads a
-        # band signal once less.  Measured (profiles/r05_tile_energies.txt, config 3): ira_edc_fits 6.66 -> 5.40 ms per step,
-        # but the second pass pays 1.6 ms for forming the partials (a serial tail of every tile): 28.2 -> 28.6 ms of device
-        # time.  OFF by default; IRA_BAND_TILE_ENERGIES=1 / this attribute is the A/B switch.
-        self.band_tile_energies = os.environ.get("IRA_BAND_TILE_ENERGIES", "0") == "1"
-        if os.environ.get("IRA_WORKSPACE_MB"):            # tuning knob: long-FFT jobs per launch (see workspace_budget_bytes)
-            self.workspace_budget_bytes = int(float(os.environ["IRA_WORKSPACE_MB"]) * (1 << 20))
+        self._ring = self._ring_np = None               # pinned staging ring of to_dev, allocated by its first use
+        self._ring_pos = 0
+        self._fetch_arena = None                        # pinned arena of fetch, allocated by its first use
+        self._fetch_seg, self._fetch_pos, self._fetch_out = 0, 0, [0] * self._FETCH_SEGMENTS
+        self._side = None                               # side_stream()
+        self._lanes = None                              # block_streams()
+        self.last_band_info = ()
+        self.last_band_info_half = ()
+        env = os.environ.get
+        # IRA_STREAMS: how many lanes block_streams() deals the report blocks onto (1 = the caller's stream only)
+        self.num_lanes = max(1, min(4, int(env("IRA_STREAMS", "2"))))
+        # which report blocks go to which lane (pipeline.FullReport.submit; None = its measured default).  IRA_LANE_DEAL, e.g.
+        # "0,1|4,3,5,2", is the A/B switch of tools: 0 bands, 1 spectrum, 2 zplane, 3 decay, 4 modal, 5 stft
+        self.lane_deal = ([[int(v) for v in part.split(",")] for part in env("IRA_LANE_DEAL").split("|")]
+                          if env("IRA_LANE_DEAL") else None)
+        # IRA_LANE_PRIO (A/B only), e.g. "-1,0": HIP stream priorities of the lanes (lower = served first)
+        self._lane_prio = [int(v) for v in env("IRA_LANE_PRIO", "").split(",") if v.strip()]
+        if env("IRA_BAND_TILE_ENERGIES") is not None:
+            self.band_tile_energies = env("IRA_BAND_TILE_ENERGIES") == "1"
+        if env("IRA_WORKSPACE_MB"):                       # tuning knob: long-FFT jobs per launch (see workspace_budget_bytes)
+            self.workspace_budget_bytes = int(float(env("IRA_WORKSPACE_MB")) * (1 << 20))
+
+    @contextmanager
+    def tagged(self, tag: str):
+        """Name the timed launches enqueued inside the block `<call><tag>` (bench.py's per-call device times); the tag in
+        force before is back on ANY exit, so a refused call does not mislabel the launches after it."""
+        saved, self.event_tag = self.event_tag, tag
+        try:
+            yield
+        finally:
+            self.event_tag = saved
 
     # ------------------------------------------------------------------ plumbing
     @property
@@ -186,7 +271,6 @@ class Engine:
         if self._ring is None:
             self._ring = t.empty(self._RING_BYTES, dtype=t.uint8).pin_memory()
             self._ring_np = self._ring.numpy()
-            self._ring_pos = 0
         pos = (self._ring_pos + 63) & ~63
         if pos + nbytes > self._RING_BYTES:
             t.cuda.synchronize(self.device)  # every copy issued so far (on any stream) has left the ring before it wraps
@@ -200,15 +284,11 @@ class Engine:
         return src.to(self.device, non_blocking=True)
 
     def job_tables(self, *arrays):
-        """to_dev_pack under the name that says what the arrays are: the job tables of ONE call (offsets, lengths, indices ...
-        read only by the launches the calling method enqueues before it returns)."""
-        return self.to_dev_pack(*arrays)
-
-    def to_dev_pack(self, *arrays):
-        """Several small host arrays -> ONE write into the pinned staging ring and ONE asynchronous H2D copy; returns the
-        device views in order (None entries stay None).  A call's job tables (offsets, lengths, indices ...) used to be
-        one copy each: 65 copy-engine operations of ~5 us per report step (profiles/r02_*: __amd_rocclr_copyBuffer), each
-        serialised with the kernels of its stream."""
+        """The job tables of ONE call (offsets, lengths, indices ... read only by the launches the calling method enqueues
+        before it returns): several small host arrays -> ONE write into the pinned staging ring and ONE asynchronous H2D
+        copy; returns the device views in order (None entries stay None).  They used to be one copy each: 65 copy-engine
+        operations of ~5 us per report step (profiles/r02_*: __amd_rocclr_copyBuffer), each serialised with the kernels
+        of its stream."""
         t = self.torch
         items = [(i, np.ascontiguousarray(a)) for i, a in enumerate(arrays) if a is not None]
         total = sum(((a.nbytes + 15) & ~15) for _, a in items)
@@ -246,10 +326,8 @@ class Engine:
         tensor = tensor.contiguous()
         nbytes = int(tensor.numel()) * tensor.element_size()
         seg_bytes = self._FETCH_BYTES // self._FETCH_SEGMENTS
-        if getattr(self, "_fetch_arena", None) is None:
+        if self._fetch_arena is None:
             self._fetch_arena = t.empty(self._FETCH_BYTES, dtype=t.uint8).pin_memory()
-            self._fetch_seg, self._fetch_pos = 0, 0
-            self._fetch_out = [0] * self._FETCH_SEGMENTS
         pos = (self._fetch_pos + 63) & ~63
         seg = self._fetch_seg
         if nbytes <= seg_bytes and pos + nbytes > seg_bytes:
@@ -258,11 +336,8 @@ class Engine:
             if self._fetch_out[nxt] == 0:
                 seg, pos = nxt, 0
                 self._fetch_seg = nxt
-        if nbytes > seg_bytes or pos + nbytes > seg_bytes:
-            host = t.empty(tensor.shape, dtype=tensor.dtype).pin_memory()
-            host.copy_(tensor, non_blocking=True)
-            return HostFuture(host, tuple(tensor.shape))
-        if pos == 0 and self._fetch_out[seg] != 0:           # only reachable on the very first wrap with stale futures
+        if (nbytes > seg_bytes or pos + nbytes > seg_bytes
+                or (pos == 0 and self._fetch_out[seg] != 0)):    # (only reachable on the very first wrap with stale futures)
             host = t.empty(tensor.shape, dtype=tensor.dtype).pin_memory()
             host.copy_(tensor, non_blocking=True)
             return HostFuture(host, tuple(tensor.shape))
@@ -273,21 +348,12 @@ class Engine:
         host.copy_(tensor, non_blocking=True)
         return HostFuture(host, tuple(tensor.shape), self, seg)
 
-    _side = None
-
     def side_stream(self):
         """High-priority stream for the tiny peak-pick launch whose result the HOST needs before it can lay out a
         step: it overtakes whatever the main stream still has queued from the previous step."""
         if self._side is None:
             self._side = self.torch.cuda.Stream(device=self.device, priority=-1)
         return self._side
-
-    _lanes = None
-    num_lanes = max(1, min(4, int(os.environ.get("IRA_STREAMS", "2"))))
-    # which report blocks go to which lane (pipeline.FullReport.submit; None = its measured default).  IRA_LANE_DEAL, e.g.
-    # "0,1|4,3,5,2", is the A/B switch of tools: 0 bands, 1 spectrum, 2 zplane, 3 decay, 4 modal, 5 stft
-    lane_deal = ([[int(v) for v in part.split(",")] for part in os.environ["IRA_LANE_DEAL"].split("|")]
-                 if os.environ.get("IRA_LANE_DEAL") else None)
 
     def block_streams(self):
         """
@@ -302,8 +368,7 @@ class Engine:
         if self.num_lanes <= 1:
             return None
         if self._lanes is None or len(self._lanes) != self.num_lanes:
-            # IRA_LANE_PRIO (A/B only), e.g. "-1,0": HIP stream priorities of the lanes (lower = served first)
-            prio = [int(v) for v in os.environ.get("IRA_LANE_PRIO", "").split(",") if v.strip()]
+            prio = self._lane_prio
             self._lanes = tuple(self.torch.cuda.Stream(device=self.device, priority=(prio[i] if i < len(prio) else 0))
                                 for i in range(self.num_lanes))
         return self._lanes
@@ -311,9 +376,7 @@ class Engine:
     def upload(self, channels: Sequence[np.ndarray]) -> ChannelBatch:
         """Host float32 channels -> one flat device buffer (H2D)."""
         lens = np.array([int(c.size) for c in channels], dtype=np.int64)
-        off = np.zeros(len(channels), dtype=np.int64)
-        if len(channels) > 1:
-            off[1:] = np.cumsum(lens[:-1])
+        off = exclusive_cumsum(lens)
         flat = np.empty(int(lens.sum()), dtype=np.float32)
         for c, o, n in zip(channels, off, lens):
             if c.ndim != 1:
@@ -335,53 +398,57 @@ class Engine:
     def wrap(self, x_dev, off: np.ndarray, lens: np.ndarray) -> ChannelBatch:
         off = np.ascontiguousarray(off, dtype=np.int64)
         lens = np.ascontiguousarray(lens, dtype=np.int64)
-        d_off, d_len = self.to_dev_pack(off, lens)
+        d_off, d_len = self.job_tables(off, lens)
         b = ChannelBatch(x=x_dev, off=off, length=lens, off_dev=d_off, len_dev=d_len)
         b.ready = self.torch.cuda.Event()
         b.ready.record(self.torch.cuda.current_stream(self.device))
         return b
 
     # ------------------------------------------------------------------ tables (host NumPy -> device, cached)
-    def window(self, n: int, use_hann: bool, precision: int):
-        key = ("win", n, bool(use_hann), precision)
+    def _cached(self, key: tuple, make):
+        """Plan data (tables, and what the library answers about a size) is made once per engine: make() on first use."""
         if key not in self._tables:
-            w = np.hanning(n).astype(np.float64) if use_hann else np.ones(n, dtype=np.float64)
-            self._tables[key] = self._table_to_dev(w.astype(np.float32) if precision == 32 else w)
+            self._tables[key] = make()
         return self._tables[key]
 
-    def _table_to_dev(self, a: np.ndarray):
+    def _table_to_dev(self, a: np.ndarray, precision: int = 64):
         """Plan data (windows, twiddles): uploaded once and COMPLETELY before use -- tables are shared by every stream."""
-        tab = self.to_dev(a)
+        tab = self.to_dev(a.astype(np.float32) if precision == 32 else a)
         self.sync()
         return tab
 
+    def window(self, n: int, use_hann: bool, precision: int):
+        return self._cached(("win", n, bool(use_hann), precision), lambda: self._table_to_dev(
+            np.hanning(n).astype(np.float64) if use_hann else np.ones(n, dtype=np.float64), precision))
+
     def twiddle(self, n: int, precision: int):
         """exp(-2 pi i k / n), k < n/2, interleaved (re, im)."""
-        key = ("tw", n, precision)
-        if key not in self._tables:
-            k = np.arange(n // 2, dtype=np.float64)
-            ang = -2.0 * np.pi * k / float(n)
-            t = np.stack([np.cos(ang), np.sin(ang)], axis=1)
-            self._tables[key] = self._table_to_dev(t.astype(np.float32) if precision == 32 else t)
-        return self._tables[key]
+        return self._cached(("tw", n, precision), lambda: self._table_to_dev(_unit_roots(n // 2, n), precision))
 
     # ------------------------------------------------------------------ a2
+    def _peak_pick(self, x_dev, d_off, d_len, n: int, max_len: int):
+        """argmax|x| (int64) and max|x| (float32) of n segments, enqueued on the current stream: two device tensors."""
+        t = self.torch
+        pk, pa = self.empty(n, t.int64), self.empty(n, t.float32)
+        check(self.lib.ira_peak_index(_ptr(x_dev), _ptr(d_off), _ptr(d_len), n, max_len, _ptr(pk), _ptr(pa), self.stream),
+              "ira_peak_index")
+        return pk, pa
+
+    def _batch_peak_pick(self, b: ChannelBatch):
+        return self._peak_pick(b.x, b.off_dev, b.len_dev, b.count, int(b.length.max()) if b.count else 0)
+
     def peaks_begin(self, b: ChannelBatch) -> None:
         """Enqueue the peak pick of a batch on the high-priority side stream (behind the batch's upload only) and its
         result's copy into pinned memory, WITHOUT waiting: the host can do other work while a freshly uploaded batch is
         still on its way.  peaks() picks the result up."""
-        if b.peak is not None or getattr(b, "_peak_pending", None) is not None:
+        if b.peak is not None or b._peak_pending is not None:
             return
         t = self.torch
         side = self.side_stream()
         if b.ready is not None:
             side.wait_event(b.ready)
         with t.cuda.stream(side):
-            pk = self.empty(b.count, t.int64)
-            pa = self.empty(b.count, t.float32)
-            check(self.lib.ira_peak_index(_ptr(b.x), _ptr(b.off_dev), _ptr(b.len_dev), b.count,
-                                          int(b.length.max()) if b.count else 0, _ptr(pk), _ptr(pa), self.stream),
-                  "ira_peak_index")
+            pk, pa = self._batch_peak_pick(b)
             hk = t.empty(pk.shape, dtype=pk.dtype, pin_memory=True)
             ha = t.empty(pa.shape, dtype=pa.dtype, pin_memory=True)
             hk.copy_(pk, non_blocking=True)
@@ -392,20 +459,14 @@ class Engine:
 
     def peaks(self, b: ChannelBatch) -> np.ndarray:
         """argmax|x| per channel (first max wins), synchronises once and caches on the batch."""
-        pend = getattr(b, "_peak_pending", None)
-        if b.peak is None and pend is not None:
-            hk, ha, ev, _, _ = pend
+        if b.peak is None and b._peak_pending is not None:
+            hk, ha, ev, _, _ = b._peak_pending
             ev.synchronize()
             b.peak = hk.numpy()[: b.count].copy()
             b.peak_abs = ha.numpy()[: b.count].copy()
             b._peak_pending = None
         if b.peak is None:
-            t = self.torch
-            pk = self.empty(b.count, t.int64)
-            pa = self.empty(b.count, t.float32)
-            check(self.lib.ira_peak_index(_ptr(b.x), _ptr(b.off_dev), _ptr(b.len_dev), b.count,
-                                          int(b.length.max()) if b.count else 0, _ptr(pk), _ptr(pa), self.stream),
-                  "ira_peak_index")
+            pk, pa = self._batch_peak_pick(b)
             b.peak = pk.cpu().numpy()[: b.count].copy()
             b.peak_abs = pa.cpu().numpy()[: b.count].copy()
         return b.peak
@@ -418,9 +479,7 @@ class Engine:
         n = int(seg_off.size)
         if np.any(seg_len > 2047 * EDC_TILE):
             raise ValueError("segment too long for the EDC kernel (> 8.3 M samples)")
-        edc_off = np.zeros(n, dtype=np.int64)
-        if n > 1:
-            edc_off[1:] = np.cumsum(seg_len[:-1])
+        edc_off = exclusive_cumsum(seg_len)
         out = self.empty(int(seg_len.sum()), t.float32)
         out64 = self.empty(int(seg_len.sum()), t.float64) if want_f64 else None
         scratch = self.empty(n * EDC_SCRATCH_DOUBLES, t.float64)
@@ -458,15 +517,10 @@ class Engine:
         seg_len = np.ascontiguousarray(seg_len, dtype=np.int64)
         if np.any(seg_len > 2047 * EDC_TILE):
             raise ValueError("segment too long for the EDC kernel (> 8.3 M samples)")
-        nr, nc = len(ranges), len(cross)
-        edc_off = np.zeros(n, dtype=np.int64)
-        if n > 1:
-            edc_off[1:] = np.cumsum(seg_len[:-1])
-        fit = self.empty(n * max(nr, 1) * FIT_DOUBLES, t.float64)
-        cr = self.empty(n * max(nc, 1), t.float64)
+        edc_off = exclusive_cumsum(seg_len)
+        fit, cr, c_ranges, c_cross, views = self._fit_outputs(n, ranges, cross)
         out = self.empty(int(seg_len.sum()), t.float32) if want_edc else None
         scratch = self.empty(n * EDC_SCRATCH_DOUBLES, t.float64)
-        flat = [v for r in ranges for v in r]
         part, p_off, p_wgs, p_tiles = tiles if tiles is not None else (None, None, None, None)
         d_off, d_len, d_eoff, d_poff, d_pwgs, d_ptiles = self.job_tables(
             np.ascontiguousarray(seg_off, np.int64), seg_len, edc_off if want_edc else None,
@@ -474,13 +528,24 @@ class Engine:
             None if part is None else np.ascontiguousarray(p_wgs, np.int32),
             None if part is None else np.ascontiguousarray(p_tiles, np.int32))
         check(self.lib.ira_edc_fits(_ptr(x_dev), _ptr(d_off), _ptr(d_len), n, int(seg_len.max()) if n else 0,
-                                    float(eps), float(floor_db), float(t_mul), float(t_div), _lib.dbl_array(flat), nr,
-                                    int(min_points), _lib.dbl_array(list(cross)), nc, _ptr(fit), _ptr(cr), _ptr(out),
+                                    float(eps), float(floor_db), float(t_mul), float(t_div), c_ranges, len(ranges),
+                                    int(min_points), c_cross, len(cross), _ptr(fit), _ptr(cr), _ptr(out),
                                     _ptr(d_eoff), _ptr(scratch), _ptr(part), _ptr(d_poff), _ptr(d_pwgs), _ptr(d_ptiles),
                                     self.stream),
               "ira_edc_fits")
-        return (fit[: n * nr * FIT_DOUBLES].view(n, nr, FIT_DOUBLES) if nr else None,
-                cr[: n * nc].view(n, nc) if nc else None, out, edc_off)
+        return views + (out, edc_off)
+
+    def _fit_outputs(self, n: int, ranges: Sequence[Tuple[float, float]], cross: Sequence[float]):
+        """What ira_edc_fits and ira_curve_fits share: the record arrays fit (n, nranges, 8) and cr (n, ncross) (float64
+        device, at least one record each), the fit ranges and crossing levels as C double arrays, and the result views
+        (fits | None, cross | None)."""
+        t = self.torch
+        nr, nc = len(ranges), len(cross)
+        fit = self.empty(n * max(nr, 1) * FIT_DOUBLES, t.float64)
+        cr = self.empty(n * max(nc, 1), t.float64)
+        views = (fit[: n * nr * FIT_DOUBLES].view(n, nr, FIT_DOUBLES) if nr else None,
+                 cr[: n * nc].view(n, nc) if nc else None)
+        return fit, cr, _lib.dbl_array([v for r in ranges for v in r]), _lib.dbl_array(list(cross)), views
 
     # ------------------------------------------------------------------ ISO 3382-1 energy parameters
     def onset_index(self, b: ChannelBatch, rel_energy: float):
@@ -489,10 +554,9 @@ class Engine:
         Returns (onset int64 device (B,), peak int64 device (B,), |x[peak]| float32 device (B,))."""
         t = self.torch
         n = b.count
-        pk, pa, on = self.empty(n, t.int64), self.empty(n, t.float32), self.empty(n, t.int64)
+        pk, pa = self._batch_peak_pick(b)
+        on = self.empty(n, t.int64)
         max_len = int(b.length.max()) if n else 0
-        check(self.lib.ira_peak_index(_ptr(b.x), _ptr(b.off_dev), _ptr(b.len_dev), n, max_len, _ptr(pk), _ptr(pa),
-                                      self.stream), "ira_peak_index")
         check(self.lib.ira_onset_index(_ptr(b.x), _ptr(b.off_dev), _ptr(b.len_dev), n, max_len, _ptr(pk), _ptr(pa),
                                        float(rel_energy), _ptr(on), self.stream), "ira_onset_index")
         return on[:n], pk[:n], pa[:n]
@@ -529,21 +593,15 @@ class Engine:
                    rel_to_peak: bool = False, floor_db: float = -120.0, min_peak_above_floor: float = 0.0,
                    t_axis_dev=None):
         """Returns (fits (ncurves, nranges, 8) float64 device, cross (ncurves, ncross) float64 device)."""
-        t = self.torch
         n = int(off.size)
-        nr, nc = len(ranges), len(cross)
-        fit = self.empty(n * max(nr, 1) * FIT_DOUBLES, t.float64)
-        cr = self.empty(n * max(nc, 1), t.float64)
-        flat = [v for r in ranges for v in r]
+        fit, cr, c_ranges, c_cross, views = self._fit_outputs(n, ranges, cross)
         d_off, d_len = self.job_tables(off, lens)
         check(self.lib.ira_curve_fits(_ptr(y_dev), _ptr(d_off), _ptr(d_len), n,
                                       int(lens.max()) if n else 0, float(t_mul), float(t_div), _ptr(t_axis_dev),
-                                      _lib.dbl_array(flat), nr,
-                                      int(min_points), _lib.dbl_array(list(cross)), nc, 1 if rel_to_peak else 0,
+                                      c_ranges, len(ranges), int(min_points), c_cross, len(cross), 1 if rel_to_peak else 0,
                                       float(floor_db), float(min_peak_above_floor), _ptr(fit), _ptr(cr), self.stream),
               "ira_curve_fits")
-        return fit[: n * nr * FIT_DOUBLES].view(n, nr, FIT_DOUBLES) if nr else None, \
-            (cr[: n * nc].view(n, nc) if nc else None)
+        return views
 
     # ------------------------------------------------------------------ a11
     def stft_mag_db(self, x_dev, seg_off: np.ndarray, nframes: np.ndarray, n_fft: int, hop: int, use_hann: bool,
@@ -563,9 +621,7 @@ class Engine:
                                       frame_major)
         if frame_sel is not None:
             cols = np.array([int(s.size) for s in frame_sel], dtype=np.int32)
-            sel_off = np.zeros(n, dtype=np.int64)
-            if n > 1:
-                sel_off[1:] = np.cumsum(cols[:-1])
+            sel_off = exclusive_cumsum(cols)
             if cols.sum():
                 sel, sel_off_dev = self.job_tables(np.concatenate(frame_sel).astype(np.int32), sel_off)
             else:
@@ -574,19 +630,16 @@ class Engine:
             cols = np.ascontiguousarray(nframes, dtype=np.int32)
             sel = None
             sel_off_dev = None
-        out_off = np.zeros(n, dtype=np.int64)
         sizes = cols.astype(np.int64) * f
-        if n > 1:
-            out_off[1:] = np.cumsum(sizes[:-1])
+        out_off = exclusive_cumsum(sizes)
         out = self.empty(int(sizes.sum()), t.float32)
         d_off, d_cols, d_ooff = self.job_tables(seg_off, cols, out_off)
-        self.event_tag = f"[f{precision},n{n_fft}{',sel' if frame_sel is not None else ''}]"
         fn = self.lib.ira_stft_mag_db_tf if frame_major else self.lib.ira_stft_mag_db
-        check(fn(_ptr(x_dev), _ptr(d_off), _ptr(d_cols), n, int(cols.max()) if n else 0, int(n_fft), int(hop),
-                 _ptr(self.window(n_fft, use_hann, precision)), _ptr(self.twiddle(n_fft, precision)), int(precision),
-                 float(floor_db), _ptr(out), _ptr(d_ooff), _ptr(sel), _ptr(sel_off_dev), self.stream),
-              "ira_stft_mag_db_tf" if frame_major else "ira_stft_mag_db")
-        self.event_tag = ""
+        with self.tagged(f"[f{precision},n{n_fft}{',sel' if frame_sel is not None else ''}]"):
+            check(fn(_ptr(x_dev), _ptr(d_off), _ptr(d_cols), n, int(cols.max()) if n else 0, int(n_fft), int(hop),
+                     _ptr(self.window(n_fft, use_hann, precision)), _ptr(self.twiddle(n_fft, precision)), int(precision),
+                     float(floor_db), _ptr(out), _ptr(d_ooff), _ptr(sel), _ptr(sel_off_dev), self.stream),
+                  "ira_stft_mag_db_tf" if frame_major else "ira_stft_mag_db")
         return out, out_off, cols
 
     def stft_logbin(self, x_dev, seg_off: np.ndarray, nframes: np.ndarray, n_fft: int, hop: int, use_hann: bool,
@@ -597,18 +650,15 @@ class Engine:
         nbins = int(first.size)
         cols = np.ascontiguousarray(nframes, dtype=np.int32)
         sizes = cols.astype(np.int64) * nbins
-        out_off = np.zeros(n, dtype=np.int64)
-        if n > 1:
-            out_off[1:] = np.cumsum(sizes[:-1])
+        out_off = exclusive_cumsum(sizes)
         out = self.empty(int(sizes.sum()), t.float32)
         d_off, d_cols, d_ooff, d_f, d_c = self.job_tables(seg_off, cols, out_off, first.astype(np.int32),
                                                            count.astype(np.int32))
-        self.event_tag = f"[f64,n{n_fft}]"
-        check(self.lib.ira_stft_logbin(_ptr(x_dev), _ptr(d_off), _ptr(d_cols), n, int(cols.max()) if n else 0,
-                                       int(n_fft), int(hop), _ptr(self.window(n_fft, use_hann, 64)),
-                                       _ptr(self.twiddle(n_fft, 64)), 64, float(floor_db), int(k_base), _ptr(d_f),
-                                       _ptr(d_c), nbins, _ptr(out), _ptr(d_ooff), self.stream), "ira_stft_logbin")
-        self.event_tag = ""
+        with self.tagged(f"[f64,n{n_fft}]"):
+            check(self.lib.ira_stft_logbin(_ptr(x_dev), _ptr(d_off), _ptr(d_cols), n, int(cols.max()) if n else 0,
+                                           int(n_fft), int(hop), _ptr(self.window(n_fft, use_hann, 64)),
+                                           _ptr(self.twiddle(n_fft, 64)), 64, float(floor_db), int(k_base), _ptr(d_f),
+                                           _ptr(d_c), nbins, _ptr(out), _ptr(d_ooff), self.stream), "ira_stft_logbin")
         return out, out_off
 
     @staticmethod
@@ -634,9 +684,7 @@ class Engine:
             frames = [np.arange(int(c), dtype=np.int64) for c in nframes]
         cols = np.array([fr.size for fr in frames], dtype=np.int32)
         sizes = cols.astype(np.int64) * f
-        out_off = np.zeros(n, dtype=np.int64)
-        if n > 1:
-            out_off[1:] = np.cumsum(sizes[:-1])
+        out_off = exclusive_cumsum(sizes)
         total_frames = int(cols.sum())
         if total_frames == 0:
             return self.empty(1, t.float32), out_off, cols
@@ -665,78 +713,39 @@ class Engine:
         return (int(n_fft), int(precision)) in ((4096, 32), (8192, 64)) or Engine.stft_generic_needed(n_fft)
 
     # ------------------------------------------------------------------ a9/a17: arbitrary-length f64 DFTs
-    workspace_budget_bytes = 48 << 30   # cap for the Bluestein work + filter arrays of one chunk
-
-    # Convolution sizes the Bluestein kernels take: 2^k and 3 * 2^k.  three_pow2_sizes = False restricts the choice to
-    # powers of two (round 2's behaviour; A/B).
-    three_pow2_sizes = True
-
     def conv_size_for(self, need: int) -> int:
         """Smallest supported convolution size M >= need (a linear convolution of `need` distinct lags)."""
         return conv_size(need, self.three_pow2_sizes)
 
+    def _query_pair(self, name: str, *args, refusal_is_none: bool = False):
+        """(a, b) as the library entry point `name` answers them through two int32 pointers; a refusal raises, or is None."""
+        a, b = ctypes.c_int32(0), ctypes.c_int32(0)
+        rc = getattr(self.lib, name)(*args, ctypes.byref(a), ctypes.byref(b))
+        if rc != 0 and refusal_is_none:
+            return None
+        check(rc, name)
+        return a.value, b.value
+
+    def _two_pass_tables(self, key: tuple, split):
+        """The twiddle tables of a two-pass transform of n1 * n2 points, (n1, n2) = split(): exp(-2 pi i k / period) for
+        the n1-point and the n2-point column transforms and for the step between the passes (cached under key)."""
+        def make():
+            n1, n2 = split()
+            return tuple(self._table_to_dev(_unit_roots(count, period))
+                         for count, period in ((n1, n1), (n2, n2), (n2, n1 * n2)))
+
+        return self._cached(key, make)
+
     def long_tables(self, m: int):
-        key = ("long", int(m))
-        if key not in self._tables:
-            import ctypes
-            l1, l2 = ctypes.c_int32(0), ctypes.c_int32(0)
-            check(self.lib.ira_fft_split(int(m), ctypes.byref(l1), ctypes.byref(l2)), "ira_fft_split")
-            n1, n2 = l1.value, l2.value
-
-            def tab(count, period):
-                ang = -2.0 * np.pi * np.arange(count, dtype=np.float64) / float(period)
-                return self._table_to_dev(np.stack([np.cos(ang), np.sin(ang)], axis=1))
-
-            self._tables[key] = (tab(n1, n1), tab(n2, n2), tab(n2, m))
-        return self._tables[key]
-
-    # Lengths of the form 2^a 3^b 5^c that split into two factors <= 1024 (480000, 2^19, ...) take the direct two-pass
-    # mixed-radix transform (ira_rfft_smooth / ira_band_irfft_smooth) instead of Bluestein.  Set False for an A/B.
-    smooth_ffts = True
+        return self._two_pass_tables(("long", int(m)), lambda: self._query_pair("ira_fft_split", int(m)))
 
     def smooth_split(self, n: int):
-        """(n1, n2) if the library has a direct transform for length n, else None (cached)."""
-        key = ("smooth?", int(n))
-        if key not in self._tables:
-            import ctypes
-            a, b = ctypes.c_int32(0), ctypes.c_int32(0)
-            rc = self.lib.ira_fft_smooth_split(int(n), ctypes.byref(a), ctypes.byref(b)) if n < (1 << 31) else -3
-            self._tables[key] = (a.value, b.value) if rc == 0 else None
-        return self._tables[key] if self.smooth_ffts else None
+        """(n1, n2) if the library has a direct transform for length n, else None (cached); None when smooth_ffts is off."""
+        ask = lambda: self._query_pair("ira_fft_smooth_split", int(n), refusal_is_none=True) if n < (1 << 31) else None
+        return self._cached(("smooth?", int(n)), ask) if self.smooth_ffts else None
 
     def smooth_tables(self, n: int):
-        key = ("smooth", int(n))
-        if key not in self._tables:
-            n1, n2 = self.smooth_split(n)
-
-            def tab(count, period):
-                ang = -2.0 * np.pi * np.arange(count, dtype=np.float64) / float(period)
-                return self._table_to_dev(np.stack([np.cos(ang), np.sin(ang)], axis=1))
-
-            self._tables[key] = (tab(n1, n1), tab(n2, n2), tab(n2, n))
-        return self._tables[key]
-
-    def _chunks_of(self, idx: np.ndarray, bytes_per_job: int):
-        step = max(1, int(self.workspace_budget_bytes // max(1, bytes_per_job)))
-        for i in range(0, idx.size, step):
-            yield idx[i : i + step]
-
-    def _chunks_by_size(self, need: np.ndarray):
-        """Group element indices by the convolution size they need, then cut each group to the workspace budget."""
-        ms = np.array([self.conv_size_for(int(v)) for v in need], dtype=np.int64)
-        for m in sorted(set(ms.tolist())):
-            idx = np.nonzero(ms == m)[0]
-            per = 16 * m * 2                           # work + (worst case) one filter per element
-            step = max(1, int(self.workspace_budget_bytes // per))
-            for i in range(0, idx.size, step):
-                yield int(m), idx[i : i + step]
-
-    # Chirp-filter spectra depend only on (length, M): they are PLAN data, like twiddle tables, and are kept in LRU pools
-    # of device slots -- one pool per (M, stream), all pools together within filter_cache_bytes -- so that repeated
-    # lengths (every step of a batch job, every band pair of a file) do not rebuild them.  A pool starts at twice the
-    # slots its first call needs and doubles when a call needs more; when the budget is full the pools used least
-    # recently are dropped.  filter_cache_bytes = 0 disables the cache.
-    filter_cache_bytes = 16 << 30
+        return self._two_pass_tables(("smooth", int(n)), lambda: self.smooth_split(n))
 
     def _filter_pool(self, m: int, need_slots: int):
         """The pool for size m on the current stream with room for need_slots filters of one call, or None."""
@@ -825,91 +834,16 @@ class Engine:
                 i = k + 1
         return pool["buf"], slots[inv].astype(np.int32)
 
-    # A channel's transforms are its own.  Round 2 let two real signals of equal length from DIFFERENT channels share one
-    # complex transform (z = x1 + i*x2) and the odd band of one channel share an inverse with the odd band of another:
-    # cheaper by half, but then the last bits of a channel's spectrum depend on which channel happened to be its partner,
-    # i.e. on batch composition and shard boundaries (SURVEY.md section 8e asks for byte-identical records for every
-    # world size).  Now a single real signal of EVEN length rides a HALF-length complex transform instead (x[2m] + i
-    # x[2m+1]: the same saving), bands are paired only within one channel, and an odd band out takes the half-length
-    # inverse.  pair_across_channels = True restores round 2's pairing (A/B; results then agree to ~1e-16 of the larger
-    # signal, not bit for bit).  pair_real_ffts = False additionally forbids pairing the bands of one channel.
-    pair_real_ffts = True
-    pair_across_channels = False
-    # A real signal of EVEN (non-smooth) length L is transformed as the complex sequence x[2m] + i*x[2m+1] of length
-    # L/2 (half the Bluestein convolution size) and split with a twiddle.  Set False for an A/B.
-    half_real_ffts = True
-    # The untangling X[k] = E[k] + W^k O[k] of such a half-length transform happens where Z[k] and Z[n - k] already meet:
-    # in the second pass of the direct transform (smooth lengths), and in the dB / phase kernel for the Bluestein spectra of
-    # the fr / filter blocks (packed spectra).  False restores round 3's separate split passes (A/B).
-    fuse_half_split = True
-    # Band inverses of smooth lengths: jobs whose bands span few bins (third-octave bands below ~800 Hz of a 10 s file)
-    # skip the first pass and the n-point work array (ira_band_irfft_smooth, job_info_dev).  False = both passes for every
-    # job (A/B).
-    sparse_bands = True
-    last_band_info = ()
-    last_band_info_half = ()
+    _pair_bands = staticmethod(pair_bands)              # (its home is engine_plan; tests reach it here)
 
-    @staticmethod
-    def _pair_by_key(idx: np.ndarray, keys: np.ndarray):
-        """Pairs of entries of idx whose keys are equal; leftovers are paired with -1.  Order-stable.
-        (Array arithmetic: run lengths of the sorted keys, even positions of a run lead a pair -- the metrics pipeline calls
-        this for 256 channels per step, and a Python loop per entry was part of what bounds the bundle configuration.)"""
-        idx = np.asarray(idx, dtype=np.int64)
-        if idx.size == 0:
-            return np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int64)
-        order = idx[np.argsort(keys[idx], kind="stable")]
-        sk = keys[order]
-        new_run = np.r_[True, sk[1:] != sk[:-1]]
-        run_start = np.flatnonzero(new_run)
-        run_id = np.cumsum(new_run) - 1
-        pos = np.arange(order.size) - run_start[run_id]                  # position inside the run
-        run_len = np.diff(np.r_[run_start, order.size])[run_id]
-        lead = (pos % 2) == 0
-        has_partner = lead & (pos + 1 < run_len)
-        first = order[lead]
-        nxt = np.r_[order[1:], -1]
-        second = np.where(has_partner, nxt, -1)[lead]
-        return first.astype(np.int64), second.astype(np.int64)
+    def _switches(self) -> Switches:
+        """The A/B attributes the planner reads, as they stand now (a Switches field is an Engine attribute of its name)."""
+        return Switches(**{f.name: getattr(self, f.name) for f in fields(Switches)})
 
-    @staticmethod
-    def _pair_bands(keys: np.ndarray, width: np.ndarray):
-        """Like _pair_by_key over all entries, but a group of odd size leaves its entry of smallest `width` alone (the first
-        of them on a tie) and pairs the others in order."""
-        order = np.argsort(keys, kind="stable")
-        sk = keys[order]
-        starts = np.flatnonzero(np.r_[True, sk[1:] != sk[:-1]]) if order.size else np.zeros(0, dtype=np.int64)
-        sizes = np.diff(np.r_[starts, order.size])
-        if order.size and np.all(sizes == sizes[0]):
-            # every group has the same size (every channel of a report has the same bands): array arithmetic, same output
-            # order as the loop below (a group's pairs, then its lone entry)
-            g, sz = int(starts.size), int(sizes[0])
-            grp = order.reshape(g, sz)
-            if sz % 2 == 0:
-                return grp[:, 0::2].reshape(-1).astype(np.int64), grp[:, 1::2].reshape(-1).astype(np.int64)
-            lone_pos = np.argmin(width[grp], axis=1)                     # the first minimum, like argmin over the group
-            keep = np.ones((g, sz), dtype=bool)
-            keep[np.arange(g), lone_pos] = False
-            rest = grp[keep].reshape(g, sz - 1)
-            lone = grp[np.arange(g), lone_pos][:, None]
-            first = np.concatenate([rest[:, 0::2], lone], axis=1).reshape(-1)
-            second = np.concatenate([rest[:, 1::2], np.full((g, 1), -1, dtype=order.dtype)], axis=1).reshape(-1)
-            return first.astype(np.int64), second.astype(np.int64)
-        first, second = [], []
-        i = 0
-        while i < order.size:
-            j = i
-            while j < order.size and keys[order[j]] == keys[order[i]]:
-                j += 1
-            grp = order[i:j]
-            lone = -1
-            if grp.size % 2:
-                lone = int(grp[int(np.argmin(width[grp]))])
-                grp = grp[grp != lone]
-            first.extend(grp[0::2].tolist()); second.extend(grp[1::2].tolist())
-            if lone >= 0:
-                first.append(lone); second.append(-1)
-            i = j
-        return np.asarray(first, dtype=np.int64), np.asarray(second, dtype=np.int64)
+    def _launch_tables(self, tables: Dict[str, Optional[np.ndarray]], **more) -> Dict[str, object]:
+        """The job tables of one planned launch (and what the engine adds to them) in ONE upload: name -> device view."""
+        tables = dict(tables, **more)
+        return dict(zip(tables, self.job_tables(*tables.values())))
 
     def rfft_any(self, x_dev, xoff: np.ndarray, lengths: np.ndarray, use_hann: bool,
                  data_len: Optional[np.ndarray] = None, win_len: Optional[np.ndarray] = None):
@@ -933,148 +867,67 @@ class Engine:
         packed_ok: the caller's consumer is spectrum_mag_phase(packed=...) -- even-length elements that ride a half-length
         Bluestein transform may then stay PACKED: spec_off[e] holds the L/2 values Z = DFT(x[2m] + i x[2m+1]) instead of
         the L/2 + 1 bins, and the third return value marks them (int32 per element; None when nothing is packed).
+        Which element takes which transform, and every job table, is engine_plan.plan_rfft's; this is its launch loop.
         """
         t = self.torch
-        n = int(xoff.size)
         lengths = np.ascontiguousarray(lengths, dtype=np.int32)
         xoff = np.ascontiguousarray(xoff, dtype=np.int64)
-        padded = data_len is not None or win_len is not None
-        if padded:
+        if data_len is not None or win_len is not None:
             data_len = np.ascontiguousarray(lengths if data_len is None else data_len, dtype=np.int32)
             win_len = np.ascontiguousarray(lengths if win_len is None else win_len, dtype=np.int32)
-        bins = lengths.astype(np.int64) // 2 + 1
-        spec_off = np.zeros(n, dtype=np.int64)
-        if n > 1:
-            spec_off[1:] = np.cumsum(bins[:-1])
-        spec = self.empty(int(bins.sum()) * 2, t.float64)
-        # ---- smooth lengths: direct two-pass transform, one call per distinct length ------------------------------------
-        # Even lengths whose half is smooth too ride a HALF-length complex transform each (interleave mode); the rest one
-        # full-length transform each -- or, with pair_across_channels, two per transform as in round 2.
-        rest = np.ones(n, dtype=bool)
-        for L in np.unique(lengths):
-            full_ok = self.smooth_split(int(L)) is not None
-            half_ok = (int(L) % 2 == 0 and int(L) >= 128 and self.half_real_ffts and not self.pair_across_channels
-                       and self.smooth_split(int(L) // 2) is not None)
-            if not (full_ok or half_ok):
-                continue
-            grp = np.nonzero(lengths == L)[0]
-            rest[grp] = False
-            nt = int(L) // 2 if half_ok else int(L)                  # transform length
-            t1, t2, tf = self.smooth_tables(nt)
-            for idx in self._chunks_of(grp, 32 * nt):
-                if half_ok:
-                    j1, j2 = idx.astype(np.int64), np.full(idx.size, -1, dtype=np.int64)
-                elif self.pair_real_ffts and self.pair_across_channels and idx.size > 1:
-                    j1, j2 = self._pair_by_key(idx, lengths)
-                else:
-                    j1, j2 = idx.astype(np.int64), np.full(idx.size, -1, dtype=np.int64)
-                work = self.empty(int(j1.size) * 2 * nt, t.float64)
-                paired = j2 >= 0
-                safe = np.maximum(j2, 0)
-                a_x2 = a_so2 = a_zo = zpair = None
-                # round 4: with an even n1 the untangling of the half-length transform is part of its second pass
-                # (mirror-pair tiles, ira_rfft_smooth without zpair scratch); fuse_half_split = False is the A/B
-                fused = half_ok and self.fuse_half_split and self.smooth_split(nt)[0] % 2 == 0
-                if fused:
-                    pass
-                elif half_ok:
-                    a_x2 = (xoff[j1] + 1).astype(np.int64)
-                    a_so2 = spec_off[j1].astype(np.int64)
-                    a_zo = (np.arange(j1.size, dtype=np.int64) * nt)
-                    zpair = self.empty(int(j1.size) * 2 * nt, t.float64)
-                elif paired.any():
-                    a_x2 = np.where(paired, xoff[safe], -1).astype(np.int64)
-                    a_so2 = np.where(paired, spec_off[safe], 0).astype(np.int64)
-                    zoff = np.cumsum(np.where(paired, int(L), 0)) - np.where(paired, int(L), 0)
-                    zpair = self.empty(int(paired.sum()) * 2 * int(L), t.float64)
-                    a_zo = zoff.astype(np.int64)
-                a_dl = a_wl = a_dl2 = a_wl2 = None
-                if padded:
-                    a_dl, a_wl = data_len[j1], win_len[j1]
-                    if not half_ok:
-                        a_dl2, a_wl2 = data_len[safe], win_len[safe]
-                d_xo, d_so, d_x2, d_so2, d_zo, d_dl, d_wl, d_dl2, d_wl2 = self.job_tables(
-                    xoff[j1], spec_off[j1], a_x2, a_so2, a_zo, a_dl, a_wl, a_dl2, a_wl2)
-                check(self.lib.ira_rfft_smooth(_ptr(x_dev), _ptr(d_xo), nt, int(j1.size), 1 if use_hann else 0,
-                                               _ptr(t1), _ptr(t2), _ptr(tf), _ptr(work), _ptr(spec), _ptr(d_so),
-                                               _ptr(d_x2), _ptr(d_so2), _ptr(zpair), _ptr(d_zo), _ptr(d_dl), _ptr(d_wl),
-                                               _ptr(d_dl2), _ptr(d_wl2), 1 if half_ok else 0, self.stream), "ira_rfft_smooth")
-        packed = np.zeros(n, dtype=np.int32)
-        if not rest.any():
-            return spec, spec_off, None
-        rest_idx = np.nonzero(rest)[0]
-        # ---- everything else: Bluestein, grouped by the power-of-two convolution size ------------------------------------
-        # Jobs: "half" = one real signal of EVEN length carried as x[2m] + i*x[2m+1] (a complex transform of L/2: half
-        # the convolution size); "pair" = two signals of equal length as x1 + i*x2; "single".
-        use_half = self.half_real_ffts and not padded
-        lr = lengths[rest_idx]
-        is_half = ((lr % 2 == 0) & (lr >= 8)) if use_half else np.zeros(rest_idx.size, dtype=bool)
-        others = rest_idx[~is_half]
-        if self.pair_real_ffts and self.pair_across_channels and others.size > 1:
-            p1, p2 = self._pair_by_key(others, lengths)
-        else:
-            p1, p2 = others.astype(np.int64), np.full(others.size, -1, dtype=np.int64)
-        e1 = np.concatenate([rest_idx[is_half].astype(np.int64), p1])
-        e2 = np.concatenate([np.full(int(is_half.sum()), -1, dtype=np.int64), p2])
-        half = np.concatenate([np.ones(int(is_half.sum()), dtype=bool), np.zeros(p1.size, dtype=bool)])
-        jlen = np.where(half, lengths[e1] // 2, lengths[e1]).astype(np.int32)        # transform length of the job
-        # lags the convolution must keep apart: 2 l - 1 when all l outputs of a complex transform are wanted (half and
-        # paired jobs), l + l/2 for a single real signal (outputs k <= l/2 only)
-        jl64 = jlen.astype(np.int64)
-        need = np.where(half | (e2 >= 0), 2 * jl64 - 1, jl64 + jl64 // 2)
-        for lm, sel in self._chunks_by_size(need):
-            t1, t2, tf = self.long_tables(lm)
-            j1, j2, jh, jl = e1[sel], e2[sel], half[sel], jlen[sel]
-            bf, bidx = self._filters(jl, lm)
-            work = self.empty(int(sel.size) * 2 * lm, t.float64)
-            paired = j2 >= 0
-            two = paired | jh                                   # jobs that carry a second "signal"
-            safe = np.maximum(j2, 0)
-            a_x2 = a_so2 = a_zo = zpair = None
-            keep_packed = bool(packed_ok and self.fuse_half_split and jh.any() and not paired.any())
-            if keep_packed:
-                # the half-length transforms land in the spectrum array itself (L/2 values in the element's L/2 + 1 slots)
-                # and stay packed: the dB / phase kernel untangles them as it reads them
-                a_x2 = np.where(jh, xoff[j1] + 1, -1).astype(np.int64)
-                a_so2 = np.zeros(j1.size, dtype=np.int64)
-                a_zo = spec_off[j1].astype(np.int64)
-                zpair = spec
-                packed[j1[jh]] = 1
-            elif two.any():
-                a_x2 = np.where(jh, xoff[j1] + 1, np.where(paired, xoff[safe], -1)).astype(np.int64)
-                a_so2 = np.where(paired, spec_off[safe], 0).astype(np.int64)
-                zlen = np.where(two, jl.astype(np.int64), 0)
-                a_zo = (np.cumsum(zlen) - zlen).astype(np.int64)
-                zpair = self.empty(int(zlen.sum()) * 2, t.float64)
-            a_dl = a_wl = a_dl2 = a_wl2 = a_il = None
-            if padded:
-                a_dl, a_wl, a_dl2, a_wl2 = data_len[j1], win_len[j1], data_len[safe], win_len[safe]
-            elif jh.any():
-                a_dl = jl
-                a_wl = np.where(jh, lengths[j1], jl).astype(np.int32)       # the Hann window belongs to the REAL signal
-                a_il = jh.astype(np.int32)
-            d_xo, d_l, d_bi, d_so, d_x2, d_so2, d_zo, d_dl, d_wl, d_dl2, d_wl2, d_il = self.job_tables(
-                xoff[j1], jl, bidx, spec_off[j1], a_x2, a_so2, a_zo, a_dl, a_wl, a_dl2, a_wl2, a_il)
-            if not padded and a_dl is not None:
-                d_dl2, d_wl2 = d_dl, d_wl
-            check(self.lib.ira_rfft_any(_ptr(x_dev), _ptr(d_xo), _ptr(d_l), int(sel.size), 1 if use_hann else 0, lm,
-                                        _ptr(t1), _ptr(t2), _ptr(tf), _ptr(bf), _ptr(d_bi), _ptr(work), _ptr(spec),
-                                        _ptr(d_so), _ptr(d_x2), _ptr(d_so2), _ptr(zpair), _ptr(d_zo), int(jl.max()),
-                                        _ptr(d_dl), _ptr(d_wl), _ptr(d_dl2), _ptr(d_wl2), _ptr(d_il),
-                                        1 if keep_packed else 0, self.stream),
-                  "ira_rfft_any")
-        return spec, spec_off, (packed if (packed_ok and packed.any()) else None)
+        spec_off, launches, packed = plan_rfft(xoff, lengths, data_len, win_len, packed_ok, self._switches(),
+                                               self.smooth_split)
+        spec = self.empty(int((lengths.astype(np.int64) // 2 + 1).sum()) * 2, t.float64)
+        hann = 1 if use_hann else 0
+        for ln in launches:
+            work = self.empty(ln.work, t.float64)
+            zpair = spec if ln.packed else (self.empty(ln.zpair, t.float64) if ln.zpair else None)
+            if ln.family == SMOOTH:
+                t1, t2, tf = self.smooth_tables(ln.size)
+                d = self._launch_tables(ln.tables)
+                check(self.lib.ira_rfft_smooth(_ptr(x_dev), _ptr(d["xo"]), ln.size, ln.count, hann, _ptr(t1), _ptr(t2),
+                                               _ptr(tf), _ptr(work), _ptr(spec), _ptr(d["so"]), _ptr(d["x2"]),
+                                               _ptr(d["so2"]), _ptr(zpair), _ptr(d["zo"]), _ptr(d["dl"]), _ptr(d["wl"]),
+                                               _ptr(d["dl2"]), _ptr(d["wl2"]), 1 if ln.half else 0, self.stream),
+                      "ira_rfft_smooth")
+            else:
+                t1, t2, tf = self.long_tables(ln.size)
+                bf, bidx = self._filters(ln.lengths, ln.size)
+                d = self._launch_tables(ln.tables, bi=bidx)
+                if ln.second_pads_as_first:
+                    d["dl2"], d["wl2"] = d["dl"], d["wl"]
+                check(self.lib.ira_rfft_any(_ptr(x_dev), _ptr(d["xo"]), _ptr(d["l"]), ln.count, hann, ln.size, _ptr(t1),
+                                            _ptr(t2), _ptr(tf), _ptr(bf), _ptr(d["bi"]), _ptr(work), _ptr(spec),
+                                            _ptr(d["so"]), _ptr(d["x2"]), _ptr(d["so2"]), _ptr(zpair), _ptr(d["zo"]),
+                                            int(ln.lengths.max()), _ptr(d["dl"]), _ptr(d["wl"]), _ptr(d["dl2"]),
+                                            _ptr(d["wl2"]), _ptr(d["il"]), 1 if ln.packed else 0, self.stream),
+                      "ira_rfft_any")
+        return spec, spec_off, packed
 
     def band_tile_layout(self, nt: int, half_out: bool):
         """(tiles, workgroups) of the partial tile energies ira_band_irfft_smooth leaves per signal (ira.h; cached)."""
-        key = ("tiles", int(nt), bool(half_out))
-        if key not in self._tables:
-            import ctypes
-            a, b = ctypes.c_int32(0), ctypes.c_int32(0)
-            check(self.lib.ira_band_tile_layout(int(nt), 1 if half_out else 0, ctypes.byref(a), ctypes.byref(b)),
-                  "ira_band_tile_layout")
-            self._tables[key] = (a.value, b.value)
-        return self._tables[key]
+        return self._cached(("tiles", int(nt), bool(half_out)), lambda: self._query_pair(
+            "ira_band_tile_layout", int(nt), 1 if half_out else 0))
+
+    def _band_tile_blocks(self, launches, nentries: int):
+        """Where the smooth-length launches of a band_irfft call leave the partial tile energies of their signals: one
+        block of 2 x tiles x workgroups doubles per job, launch after launch in ONE buffer.  Returns (part float64
+        device | None, first double of every launch's blocks, (part_off, part_wgs, part_tiles) per entry)."""
+        part_off = np.full(nentries, -1, dtype=np.int64)
+        part_wgs = np.zeros(nentries, dtype=np.int32)
+        part_tiles = np.zeros(nentries, dtype=np.int32)
+        bases, total = [], 0
+        for ln in launches:
+            tiles, wgs = self.band_tile_layout(ln.size, ln.half)
+            bases.append(total)
+            blk = tiles * wgs
+            first = total + np.arange(ln.count, dtype=np.int64) * (2 * blk)
+            two = ln.partner >= 0
+            for entries, at in ((ln.jobs, first), (ln.partner[two], first[two] + blk)):
+                part_off[entries], part_wgs[entries], part_tiles[entries] = at, wgs, tiles
+            total += ln.count * 2 * blk
+        part = self.empty(total, self.torch.float64) if total else None
+        return part, bases, (part_off, part_wgs, part_tiles)
 
     def band_irfft(self, spec_dev, spec_off: np.ndarray, lengths: np.ndarray, band_params: np.ndarray,
                    freq_val: np.ndarray, y_dev, y_off: np.ndarray, want_tiles: bool = False):
@@ -1088,119 +941,44 @@ class Engine:
         want_tiles (round 5): the smooth-length inverses also leave the partial energies of every band signal's EDC tiles;
         returns (part float64 device, part_off int64 per entry (-1: none, e.g. Bluestein lengths), part_wgs and part_tiles
         int32 per entry) for edc_fits(tiles=...), else None.
+        The pairing, the launches and their job tables are engine_plan.plan_band_irfft's; this is its launch loop.
         """
         t = self.torch
         self.last_band_info = []          # the job_info records of this call's launches (tests, diagnostics) ...
         self.last_band_info_half = []     # ... and whether the launch was the half-length (single band) one
         lengths = np.ascontiguousarray(lengths, dtype=np.int32)
-        spec_off = np.ascontiguousarray(spec_off, dtype=np.int64)
-        y_off = np.ascontiguousarray(y_off, dtype=np.int64)
-        band_params = np.ascontiguousarray(band_params, dtype=np.float64).reshape(-1, 8)
-        freq_val = np.ascontiguousarray(freq_val, dtype=np.float64)
-        # pair key: same transform length AND same float64 bin step (AND same spectrum when cross-channel pairing is off)
-        cols = [lengths.astype(np.float64), freq_val]
-        if not self.pair_across_channels:
-            cols.append(spec_off.astype(np.float64))
-        _, key = np.unique(np.stack(cols, axis=1), axis=0, return_inverse=True)
-        if self.pair_real_ffts and self.sparse_bands:
-            # the band left over in a group of odd size is the NARROWEST one (round 4): alone it is a narrow job of the
-            # half-length inverse and skips the first pass, paired with a wide neighbour it would not
-            kind, width = band_params[:, 0], np.full(lengths.size, np.inf)
-            width[kind == 1.0] = band_params[kind == 1.0, 4]
-            width[kind == 3.0] = band_params[kind == 3.0, 4] - band_params[kind == 3.0, 1]
-            width[(kind != 1.0) & (kind != 2.0) & (kind != 3.0)] = 0.0
-            j1, j2 = self._pair_bands(key.reshape(-1), width)
-        elif self.pair_real_ffts:
-            j1, j2 = self._pair_by_key(np.arange(lengths.size), key.reshape(-1))
-        else:
-            j1, j2 = np.arange(lengths.size, dtype=np.int64), np.full(lengths.size, -1, dtype=np.int64)
-        jl = lengths[j1]
-        safe = np.maximum(j2, 0)
-        has2 = j2 >= 0
-        el_par = np.zeros((j1.size, 2, 8), dtype=np.float64)
-        el_par[:, 0, :] = band_params[j1]
-        el_par[has2, 1, :] = band_params[safe[has2]]
-        el_so2 = np.where(has2, spec_off[safe], spec_off[j1]).astype(np.int64)
-        el_y2 = np.where(has2, y_off[safe], -1).astype(np.int64)
-        rest = np.ones(j1.size, dtype=bool)
-        launches = []                                         # (jobs, half-length?, transform length) of the smooth family
-        for L in np.unique(jl):
-            full_ok = self.smooth_split(int(L)) is not None
-            half_ok = (int(L) % 2 == 0 and int(L) >= 128 and self.half_real_ffts
-                       and self.smooth_split(int(L) // 2) is not None)
-            for halves in (False, True):
-                # single bands take the half-length inverse when the length allows it, pairs the full-length one
-                if halves and not half_ok:
-                    continue
-                if not halves and not full_ok:
-                    continue
-                grp = np.nonzero((jl == L) & rest & ((~has2) if halves else (has2 | (not half_ok))))[0]
-                if grp.size == 0:
-                    continue
-                rest[grp] = False
-                nt = int(L) // 2 if halves else int(L)
-                for sel in self._chunks_of(grp, 16 * nt):
-                    launches.append((sel, halves, nt))
-        # partial tile energies: one block of 2 x tiles x workgroups doubles per job, launch after launch in ONE buffer
-        part = part_off = part_wgs = part_tiles = None
-        bases = [0] * len(launches)
+        launches = plan_band_irfft(np.ascontiguousarray(spec_off, dtype=np.int64), lengths,
+                                   np.ascontiguousarray(band_params, dtype=np.float64).reshape(-1, 8),
+                                   np.ascontiguousarray(freq_val, dtype=np.float64),
+                                   np.ascontiguousarray(y_off, dtype=np.int64), self._switches(), self.smooth_split)
+        part = tiles_out = None
         if want_tiles and self.band_tile_energies:
-            part_off = np.full(lengths.size, -1, dtype=np.int64)
-            part_wgs = np.zeros(lengths.size, dtype=np.int32)
-            part_tiles = np.zeros(lengths.size, dtype=np.int32)
-            total = 0
-            for li, (sel, halves, nt) in enumerate(launches):
-                tiles, wgs = self.band_tile_layout(nt, halves)
-                bases[li] = total
-                blk = tiles * wgs
-                first = total + np.arange(sel.size, dtype=np.int64) * (2 * blk)
-                part_off[j1[sel]] = first
-                part_wgs[j1[sel]] = wgs
-                part_tiles[j1[sel]] = tiles
-                two = has2[sel]
-                part_off[j2[sel][two]] = first[two] + blk
-                part_wgs[j2[sel][two]] = wgs
-                part_tiles[j2[sel][two]] = tiles
-                total += int(sel.size) * 2 * blk
-            part = self.empty(total, t.float64) if total else None
-        if True:
-            if True:
-                for li, (sel, halves, nt) in enumerate(launches):
-                    t1, t2, tf = self.smooth_tables(nt)
-                    work = self.empty(int(sel.size) * 2 * nt, t.float64)
-                    d_so, d_bp, d_fv, d_y1, d_y2, d_so2 = self.job_tables(
-                        spec_off[j1][sel], np.ascontiguousarray(el_par[sel]), np.ascontiguousarray(freq_val[j1][sel]),
-                        np.ascontiguousarray(y_off[j1][sel]), np.ascontiguousarray(el_y2[sel]),
-                        None if halves else np.ascontiguousarray(el_so2[sel]))
-                    # round 4: narrow bands skip the first pass (ira.h, job_info_dev); sparse_bands = False is the A/B
-                    info = self.empty(4 * int(sel.size), t.int32) if self.sparse_bands else None
-                    check(self.lib.ira_band_irfft_smooth(_ptr(spec_dev), _ptr(d_so), nt, int(sel.size), _ptr(d_bp),
-                                                         _ptr(d_fv), _ptr(t1), _ptr(t2), _ptr(tf), _ptr(work), _ptr(y_dev),
-                                                         _ptr(d_y1), _ptr(d_y2), _ptr(d_so2), 1 if halves else 0,
-                                                         _ptr(info), (_ptr(part) + 8 * bases[li]) if part is not None else None,
-                                                         self.stream), "ira_band_irfft_smooth")
-                    self.last_band_info.append(info)
-                    self.last_band_info_half.append(bool(halves))
-        tiles_out = (part, part_off, part_wgs, part_tiles) if part is not None else None
-        if not rest.any():
-            return tiles_out
-        rest_idx = np.nonzero(rest)[0]
-        for lm, sub in self._chunks_by_size(2 * jl[rest_idx].astype(np.int64) - 1):
-            sel = rest_idx[sub]
-            t1, t2, tf = self.long_tables(lm)
-            bf, bidx = self._filters(jl[sel], lm)
-            work = self.empty(int(sel.size) * 2 * lm, t.float64)
-            d_so, d_l = self.to_dev(spec_off[j1][sel]), self.to_dev(jl[sel])
-            d_bp = self.to_dev(np.ascontiguousarray(el_par[sel]))
-            d_fv = self.to_dev(np.ascontiguousarray(freq_val[j1][sel]))
-            d_bi = self.to_dev(bidx)
-            d_y1 = self.to_dev(np.ascontiguousarray(y_off[j1][sel]))
-            d_y2 = self.to_dev(np.ascontiguousarray(el_y2[sel]))
-            d_so2 = self.to_dev(np.ascontiguousarray(el_so2[sel]))
-            check(self.lib.ira_band_irfft(_ptr(spec_dev), _ptr(d_so), _ptr(d_l), int(sel.size), _ptr(d_bp), _ptr(d_fv),
-                                          lm, _ptr(t1), _ptr(t2), _ptr(tf), _ptr(bf), _ptr(d_bi), _ptr(work),
-                                          _ptr(y_dev), _ptr(d_y1), _ptr(d_y2), _ptr(d_so2), self.stream),
-                  "ira_band_irfft")
+            part, bases, per_entry = self._band_tile_blocks([ln for ln in launches if ln.family == SMOOTH],
+                                                            int(lengths.size))
+            if part is not None:
+                tiles_out = (part,) + per_entry
+        for li, ln in enumerate(launches):                  # (the smooth launches come first: li indexes bases)
+            work = self.empty(ln.work, t.float64)
+            if ln.family == SMOOTH:
+                t1, t2, tf = self.smooth_tables(ln.size)
+                d = self._launch_tables(ln.tables)
+                # round 4: narrow bands skip the first pass (ira.h, job_info_dev); sparse_bands = False is the A/B
+                info = self.empty(4 * ln.count, t.int32) if self.sparse_bands else None
+                check(self.lib.ira_band_irfft_smooth(_ptr(spec_dev), _ptr(d["so"]), ln.size, ln.count, _ptr(d["bp"]),
+                                                     _ptr(d["fv"]), _ptr(t1), _ptr(t2), _ptr(tf), _ptr(work), _ptr(y_dev),
+                                                     _ptr(d["y1"]), _ptr(d["y2"]), _ptr(d["so2"]), 1 if ln.half else 0,
+                                                     _ptr(info), (_ptr(part) + 8 * bases[li]) if part is not None else None,
+                                                     self.stream), "ira_band_irfft_smooth")
+                self.last_band_info.append(info)
+                self.last_band_info_half.append(ln.half)
+            else:
+                t1, t2, tf = self.long_tables(ln.size)
+                bf, bidx = self._filters(ln.lengths, ln.size)
+                d = self._launch_tables(ln.tables, bi=bidx)
+                check(self.lib.ira_band_irfft(_ptr(spec_dev), _ptr(d["so"]), _ptr(d["l"]), ln.count, _ptr(d["bp"]),
+                                              _ptr(d["fv"]), ln.size, _ptr(t1), _ptr(t2), _ptr(tf), _ptr(bf),
+                                              _ptr(d["bi"]), _ptr(work), _ptr(y_dev), _ptr(d["y1"]), _ptr(d["y2"]),
+                                              _ptr(d["so2"]), self.stream), "ira_band_irfft")
         return tiles_out
 
     def spectrum_mag_phase(self, spec_dev, spec_off: np.ndarray, lengths: np.ndarray, floor_db: float,
@@ -1263,8 +1041,8 @@ class Engine:
         ranks = np.ascontiguousarray(ranks, dtype=np.int64)
         nseg, nr = ranks.shape
         out = self.empty(nseg * nr, t.float64)
-        d_o, d_c = self.to_dev(np.ascontiguousarray(off, np.int64)), self.to_dev(np.ascontiguousarray(count, np.int32))
-        d_r = self.to_dev(ranks.reshape(-1))
+        d_o, d_c, d_r = self.job_tables(np.ascontiguousarray(off, np.int64), np.ascontiguousarray(count, np.int32),
+                                        ranks.reshape(-1))
         check(self.lib.ira_order_stats(_ptr(values_dev), _ptr(d_o), _ptr(d_c), int(nseg), _ptr(d_r), int(nr), _ptr(out),
                                        self.stream), "ira_order_stats")
         return out[: nseg * nr].view(nseg, nr)
@@ -1275,12 +1053,10 @@ class Engine:
         t = self.torch
         n = int(xoff.size)
         nframes = np.ascontiguousarray(nframes, dtype=np.int32)
-        out_off = np.zeros(n, dtype=np.int64)
-        if n > 1:
-            out_off[1:] = np.cumsum(nframes[:-1].astype(np.int64))
+        out_off = exclusive_cumsum(nframes)
         total = int(nframes.astype(np.int64).sum())
         ac, ed = self.empty(total, t.float32), self.empty(total, t.float32)
-        d_xo, d_nf, d_oo = self.to_dev(np.ascontiguousarray(xoff, np.int64)), self.to_dev(nframes), self.to_dev(out_off)
+        d_xo, d_nf, d_oo = self.job_tables(np.ascontiguousarray(xoff, np.int64), nframes, out_off)
         check(self.lib.ira_diffusion(_ptr(x_dev), _ptr(d_xo), _ptr(d_nf), n, int(nframes.max()), int(win), int(hop),
                                      int(max_lag), float(thr_rms), float(gauss_expected), _ptr(ac), _ptr(ed),
                                      _ptr(d_oo), self.stream), "ira_diffusion")
@@ -1292,13 +1068,11 @@ class Engine:
         t = self.torch
         n = int(loff.size)
         nframes = np.ascontiguousarray(nframes, dtype=np.int32)
-        out_off = np.zeros(n, dtype=np.int64)
-        if n > 1:
-            out_off[1:] = np.cumsum(nframes[:-1].astype(np.int64))
+        out_off = exclusive_cumsum(nframes)
         total = int(nframes.astype(np.int64).sum())
         c0, ia = self.empty(total, t.float32), self.empty(total, t.float32)
-        d_lo, d_ro = self.to_dev(np.ascontiguousarray(loff, np.int64)), self.to_dev(np.ascontiguousarray(roff, np.int64))
-        d_nf, d_oo = self.to_dev(nframes), self.to_dev(out_off)
+        d_lo, d_ro, d_nf, d_oo = self.job_tables(np.ascontiguousarray(loff, np.int64), np.ascontiguousarray(roff, np.int64),
+                                                 nframes, out_off)
         check(self.lib.ira_diffusion_stereo(_ptr(x_dev), _ptr(d_lo), _ptr(d_ro), _ptr(d_nf), n, int(nframes.max()),
                                             int(win), int(hop), int(max_lag), _ptr(c0), _ptr(ia), _ptr(d_oo),
                                             self.stream), "ira_diffusion_stereo")
@@ -1315,21 +1089,17 @@ class Engine:
         # reference's own expression (group_delay.py:113-124), instead of a sweep over every bin of every channel per call.
         bin_step = np.ascontiguousarray(bin_step, np.float64)
         known = np.empty(n, dtype=np.int32)
+        def nonuniform(nb, step, rate):
+            d = np.diff(2.0 * np.pi * ((np.arange(nb, dtype=np.float64) * step) / rate))
+            return int(d.size > 0 and not bool(np.all(d == d[0])))
+
         for i in range(n):
             key = (int(nbins[i]), float(bin_step[i]), float(sample_rate_hz))
-            f = self._gd_nonuniform.get(key)
-            if f is None:
-                w = 2.0 * np.pi * ((np.arange(key[0], dtype=np.float64) * key[1]) / key[2])
-                d = np.diff(w)
-                f = int(d.size > 0 and not bool(np.all(d == d[0])))
-                self._gd_nonuniform[key] = f
-            known[i] = f
+            known[i] = self._cached(("gd nonuniform",) + key, lambda: nonuniform(*key))
         d_o, d_n, d_v, flags = self.job_tables(np.ascontiguousarray(off, np.int64), nbins, bin_step, known)
         check(self.lib.ira_group_delay(_ptr(phase64_dev), _ptr(d_o), _ptr(d_n), n, int(nbins.max()), _ptr(d_v),
                                        float(sample_rate_hz), _ptr(flags), 1, _ptr(gd), self.stream), "ira_group_delay")
         return gd
-
-    _gd_nonuniform: dict = {}
 
     def spectrum_stats(self, mag_dev, off: np.ndarray, lengths: np.ndarray, freq_val: np.ndarray, f_min: float,
                        f_max: float, probe_hz: float = 1000.0):
@@ -1350,9 +1120,7 @@ class Engine:
         n = int(mag_off.size)
         nslices = np.ascontiguousarray(nslices, dtype=np.int32)
         sizes = nslices.astype(np.int64) * int(nsel)
-        out_off = np.zeros(n, dtype=np.int64)
-        if n > 1:
-            out_off[1:] = np.cumsum(sizes[:-1])
+        out_off = exclusive_cumsum(sizes)
         out = self.empty(int(sizes.sum()), t.float32)
         d_mo, d_ns, d_oo = self.job_tables(mag_off, nslices, out_off)
         check(self.lib.ira_waterfall_rel(_ptr(mag_dev), _ptr(d_mo), _ptr(d_ns), n, int(k_lo), int(nsel),
@@ -1369,12 +1137,10 @@ class Engine:
         nbins = int(first.size)
         nframes = np.ascontiguousarray(nframes, dtype=np.int32)
         sizes = nframes.astype(np.int64) * nbins
-        out_off = np.zeros(n, dtype=np.int64)
-        if n > 1:
-            out_off[1:] = np.cumsum(sizes[:-1])
+        out_off = exclusive_cumsum(sizes)
         out = self.empty(int(sizes.sum()), t.float32)
-        d_mo, d_nf, d_oo = self.to_dev(mag_off), self.to_dev(nframes), self.to_dev(out_off)
-        d_f, d_c = self.to_dev(first.astype(np.int32)), self.to_dev(count.astype(np.int32))
+        d_mo, d_nf, d_oo, d_f, d_c = self.job_tables(mag_off, nframes, out_off, first.astype(np.int32),
+                                                     count.astype(np.int32))
         check(self.lib.ira_logbin_aggregate(_ptr(mag_dev), _ptr(d_mo), _ptr(d_nf), n, int(nframes.max()), int(k_base),
                                             _ptr(d_f), _ptr(d_c), nbins, _ptr(out), _ptr(d_oo), int(frame_major_rows),
                                             self.stream), "ira_logbin_aggregate")
@@ -1398,7 +1164,8 @@ class Engine:
         d_xo, d_l, d_div = self.job_tables(np.ascontiguousarray(xoff, np.int64), lengths,
                                             np.ascontiguousarray(divisor, np.float64) if divisor is not None else None)
         flags = (1 if self.ar_dense_gram else 0) | (2 if self.ar_workgroup_solve else 0)   # IRA_AR_DENSE_GRAM | IRA_AR_WORKGROUP_SOLVE
-        check(self.lib.ira_ar_gram(0 if x_is_f64 else _ptr(x_dev), _ptr(x_dev) if x_is_f64 else 0, _ptr(d_xo),
+        x32, x64 = (0, _ptr(x_dev)) if x_is_f64 else (_ptr(x_dev), 0)      # the samples are float32 or float64
+        check(self.lib.ira_ar_gram(x32, x64, _ptr(d_xo),
                                    _ptr(d_l), _ptr(d_div), n, max_len, int(order), _ptr(part), flags, self.stream),
               "ira_ar_gram")
         check(self.lib.ira_ar_solve(_ptr(part), _ptr(d_l), n, max_len, int(order), float(ridge), _ptr(gs),
@@ -1408,7 +1175,7 @@ class Engine:
             # cond(G) eps is no longer small are solved again, in double-double arithmetic (ira_ar_exact)
             ddp = self.empty(n * int(self.lib.ira_ar_exact_doubles(int(order), max_len, 0)), t.float64)
             dds = self.empty(n * int(self.lib.ira_ar_exact_doubles(int(order), max_len, 1)), t.float64)
-            check(self.lib.ira_ar_exact(0 if x_is_f64 else _ptr(x_dev), _ptr(x_dev) if x_is_f64 else 0, _ptr(d_xo),
+            check(self.lib.ira_ar_exact(x32, x64, _ptr(d_xo),
                                         _ptr(d_l), _ptr(d_div), n, max_len, int(order), float(ridge), _ptr(part), _ptr(ddp),
                                         _ptr(dds), _ptr(coeffs), _ptr(info), float(self.ar_exact_cond), self.stream),
                   "ira_ar_exact")
@@ -1421,25 +1188,11 @@ class Engine:
             # conditional on the device: only elements whose pivots show cond(G) > threshold do any work
             nchunks = -(-(max_len - int(order)) // 4096)
             grad = self.empty(n * nchunks * (order + 1), t.float64)
-            check(self.lib.ira_ar_refine(0 if x_is_f64 else _ptr(x_dev), _ptr(x_dev) if x_is_f64 else 0, _ptr(d_xo),
+            check(self.lib.ira_ar_refine(x32, x64, _ptr(d_xo),
                                          _ptr(d_l), _ptr(d_div), n, max_len, int(order), _ptr(part), _ptr(gs),
                                          _ptr(coeffs), _ptr(info), _ptr(grad), float(self.ar_refine_cond),
                                          int(self.ar_refine_steps), flags, self.stream), "ira_ar_refine")
         return coeffs[: n * (order + 1)].view(n, order + 1), info[: n * 4].view(n, 4)
-
-    # Normal equations lose cond(A)^2 eps; above this cond(G) estimate the fit gets refinement steps (ira_ar_refine).
-    # Rank-deficient Gram matrices (Cholesky pivot <= 0) get the minimum-norm solution lstsq returns (ira_ar_minnorm):
-    # eigen-directions with lambda <= cut * lambda_max are dropped.  0 disables the fallback.
-    ar_minnorm_cut = 1e-12
-    # A/B: form the Gram matrix as a dense contraction on the FP64 matrix cores (IRA_AR_DENSE_GRAM) instead of the lag sums
-    ar_dense_gram = False
-    # A/B: the 256-thread solve kernel also for order <= 64 (default there since round 4: one wave per element, same bits)
-    ar_workgroup_solve = False
-    ar_refine_cond = 1e9          # on the estimate trace(G) ||G^-1|| (<= order * cond(G))
-    ar_refine_steps = 2
-    # Above this estimate (or when the float64 Cholesky breaks down) the normal equations are solved again in double-double
-    # arithmetic (ira_ar_exact): refinement needs cond(G) eps << 1.  0 disables the path (A/B).
-    ar_exact_cond = 1e13
 
     def poly_roots(self, coeffs_dev, npoly: int, ncoef: int, trail_eps: float = 1e-14):
         """Roots (npoly, ncoef-1, 2) float64 device + counts int32 device."""
@@ -1455,9 +1208,8 @@ class Engine:
         t = self.torch
         n = int(xoff.size)
         b = self.empty(n * (zero_order + 1), t.float64)
-        d_xo = self.to_dev(np.ascontiguousarray(xoff, np.int64))
-        d_l = self.to_dev(np.ascontiguousarray(lengths, np.int32))
-        d_div = self.to_dev(np.ascontiguousarray(divisor, np.float64)) if divisor is not None else None
+        d_xo, d_l, d_div = self.job_tables(np.ascontiguousarray(xoff, np.int64), np.ascontiguousarray(lengths, np.int32),
+                                            np.ascontiguousarray(divisor, np.float64) if divisor is not None else None)
         check(self.lib.ira_fir_numerator(_ptr(coeffs_dev), int(order), _ptr(x_dev), _ptr(d_xo), _ptr(d_l), _ptr(d_div),
                                          n, int(zero_order), _ptr(b), self.stream), "ira_fir_numerator")
         return b[: n * (zero_order + 1)].view(n, zero_order + 1)
@@ -1472,8 +1224,8 @@ class Engine:
         pmax = self.empty(n, t.float64)
         # device copies stay referenced until the launch is enqueued (a temporary would hand its block back to the
         # allocator, and the next to_dev would overwrite it before the kernel reads it)
-        d_yo, d_xo = self.to_dev(np.ascontiguousarray(yspec_off, np.int64)), self.to_dev(np.ascontiguousarray(xspec_off, np.int64))
-        d_nf = self.to_dev(n_fft)
+        d_yo, d_xo, d_nf = self.job_tables(np.ascontiguousarray(yspec_off, np.int64),
+                                           np.ascontiguousarray(xspec_off, np.int64), n_fft)
         check(self.lib.ira_deconv_divide(_ptr(yspec_dev), _ptr(d_yo), _ptr(xspec_dev), _ptr(d_xo), _ptr(d_nf), n,
                                          int(n_fft.max()), float(regularization_relative), _ptr(pmax), self.stream),
               "ira_deconv_divide")
@@ -1487,18 +1239,14 @@ class Engine:
         group = np.ascontiguousarray(group, dtype=np.int32)
         ngroups = int(group.max()) + 1 if n else 0
         mean, peak = self.empty(n, t.float32), self.empty(ngroups, t.int32)
-        d_ho, d_no, d_gr = self.to_dev(np.ascontiguousarray(h_off, np.int64)), self.to_dev(n_out), self.to_dev(group)
+        d_ho, d_no, d_gr = self.job_tables(np.ascontiguousarray(h_off, np.int64), n_out, group)
         check(self.lib.ira_deconv_finish(_ptr(h_dev), _ptr(d_ho), _ptr(d_no), _ptr(d_gr), n, ngroups,
                                          int(n_out.max()) if n else 0, 1 if remove_dc else 0, 1 if normalise_peak else 0,
                                          float(target_peak), _ptr(mean), _ptr(peak), self.stream), "ira_deconv_finish")
 
     def segment_peaks(self, x_dev, off: np.ndarray, lens: np.ndarray):
         """max|x| (float32 values as float64) of arbitrary segments."""
-        t = self.torch
         n = int(off.size)
-        pk = self.empty(n, t.int64)
-        pa = self.empty(n, t.float32)
-        d_o, d_l = self.to_dev(np.ascontiguousarray(off, np.int64)), self.to_dev(np.ascontiguousarray(lens, np.int64))
-        check(self.lib.ira_peak_index(_ptr(x_dev), _ptr(d_o), _ptr(d_l), n, int(np.max(lens)) if n else 0, _ptr(pk),
-                                      _ptr(pa), self.stream), "ira_peak_index")
+        d_o, d_l = self.job_tables(np.ascontiguousarray(off, np.int64), np.ascontiguousarray(lens, np.int64))
+        _, pa = self._peak_pick(x_dev, d_o, d_l, n, int(np.max(lens)) if n else 0)
         return pa.cpu().numpy()[:n].astype(np.float64)

@@ -15,7 +15,8 @@ rep.run(batch); rep.run(batch)
 calls = collections.Counter(); sizes = collections.Counter()
 orig = eng.to_dev
 def counted(a):
-    fr = traceback.extract_stack(limit=3)[0]
+    # the Engine method that asked for the copy: the nearest caller that is not one of the upload helpers
+    fr = next(f for f in reversed(traceback.extract_stack()[:-1]) if f.name not in ("job_tables", "_launch_tables"))
     calls[f"{fr.name}"] += 1; sizes[f"{fr.name}"] += np.asarray(a).nbytes
     return orig(a)
 eng.to_dev = counted
