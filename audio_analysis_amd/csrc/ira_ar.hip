@@ -1428,11 +1428,7 @@ extern "C" int32_t ira_ar_gram(const float* x_dev, const double* x64_dev, const 
     const int ngroups = (order + 1 + lpt - 1) / lpt;
     const size_t lds = sizeof(double) * ((size_t)lpt * ngroups + LAG_CHUNK);
     auto launch = [&](auto kernel) -> int32_t {
-      if (lds > 64 * 1024) {
-        hipError_t er = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (er != hipSuccess) return ira_hip_status(er);
-      }
+      IRA_TRY_HIP(allow_lds(kernel, lds));
       kernel<<<dim3(lchunks, 1, nb), LAG_THREADS, lds, (hipStream_t)stream>>>(
           x64_dev ? nullptr : x_dev, x64_dev, xoff_dev, len_dev, divisor_dev, order, lchunks,
           lag_record_doubles(max_len, order), partial_dev);
@@ -1470,11 +1466,7 @@ extern "C" int32_t ira_ar_solve(const double* partial_dev, const int32_t* len_de
   size_t lds = sizeof(double) * (size_t)order;
   if (order <= SV_LDS_P) lds += sizeof(double) * (size_t)order * order;
   else lds += sizeof(double) * sv_blocked_lds_doubles(order);        // panel + diagonal block of the blocked factorisation
-  if (lds > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&ar_solve_kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return ira_hip_status(e);
-  }
+  IRA_TRY_HIP(allow_lds(&ar_solve_kernel, lds));
   if (ar_wave_solve(flags, order)) {
     ar_solve_wave_kernel<<<nb, 64, 0, (hipStream_t)stream>>>(partial_dev, len_dev, order, ridge, coeffs_dev, info_dev,
                                                               lag_chunks(max_len, order), lag_record_doubles(max_len, order),
@@ -1547,20 +1539,12 @@ extern "C" int32_t ira_ar_refine(const float* x_dev, const double* x64_dev, cons
   const int nlag = order + 1, ngroups = (nlag + 3) / 4;
   const int nsub = ngroups >= LAG_THREADS ? 1 : LAG_THREADS / ngroups;
   const size_t lds_g = sizeof(double) * ((size_t)(order + 3) + 2 * LAG_CHUNK + nlag + (size_t)nsub * 4 * ngroups);
-  if (lds_g > 64 * 1024) {
-    hipError_t er = hipFuncSetAttribute(reinterpret_cast<const void*>(&ar_grad_kernel),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_g);
-    if (er != hipSuccess) return ira_hip_status(er);
-  }
+  IRA_TRY_HIP(allow_lds(&ar_grad_kernel, lds_g));
   const int nchunks = (int)(((int64_t)max_len - order + GR_CHUNK - 1) / GR_CHUNK);
   size_t lds_s = sizeof(double) * (size_t)order;
   if (order <= SV_LDS_P) lds_s += sizeof(double) * (size_t)order * order;
   else lds_s += sizeof(double) * sv_blocked_lds_doubles(order);
-  if (lds_s > 64 * 1024) {
-    hipError_t er = hipFuncSetAttribute(reinterpret_cast<const void*>(&ar_solve_kernel),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_s);
-    if (er != hipSuccess) return ira_hip_status(er);
-  }
+  IRA_TRY_HIP(allow_lds(&ar_solve_kernel, lds_s));
   hipStream_t st = (hipStream_t)stream;
   for (int it = 0; it < steps; ++it) {
     ar_grad_kernel<<<dim3(lchunks, 1, nb), LAG_THREADS, lds_g, st>>>(x64_dev ? nullptr : x_dev, x64_dev, xoff_dev, len_dev,

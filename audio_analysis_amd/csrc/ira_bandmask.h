@@ -71,6 +71,15 @@ __device__ __forceinline__ float highpass_f32(float f, double stop, double pass)
   if (f >= (float)pass) m = 1.0f;
   return m;
 }
+// a job's BandMask moved to scalar registers (ira::uniform: read once, before the tile loops)
+__device__ __forceinline__ BandMask uniform_band(const BandMask& p) {
+  BandMask b{};
+  b.kind = uniform(p.kind);
+  b.hp_x0 = uniform(p.hp_x0); b.hp_x1 = uniform(p.hp_x1);
+  b.lp_x0 = uniform(p.lp_x0); b.lp_x1 = uniform(p.lp_x1);
+  return b;
+}
+
 __device__ __forceinline__ float mask_at(const BandMask& b, float f) {
   const int kind = (int)b.kind;
   if (kind == 1) return lowpass_f32(f, b.lp_x0, b.lp_x1);

@@ -20,6 +20,19 @@ static inline int32_t ira_hip_status(hipError_t e) {
 // Launch epilogue: report launch-configuration errors without synchronising.
 #define IRA_RETURN_LAUNCH() return ira_hip_status(hipGetLastError())
 
+#define IRA_TRY_HIP(expr)                            \
+  do {                                               \
+    hipError_t _e = (expr);                          \
+    if (_e != hipSuccess) return ira_hip_status(_e); \
+  } while (0)
+
+// More than `above` bytes of dynamic LDS per workgroup need the opt-in (idempotent, host side only).
+template <typename K>
+hipError_t allow_lds(K kernel, size_t bytes, size_t above = 64 * 1024) {
+  if (bytes <= above) return hipSuccess;
+  return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+}
+
 // Tuning / ablation knobs (IRA_* environment variables) exist only in the TUNING build (-DIRA_TUNING_BUILD:
 // `python -m audio_analysis_amd.build --tuning` -> csrc/libira_tuning.so, never loaded by the product).  In the product
 // library these helpers are constants: it reads no environment variable and keeps no state between calls -- every entry
@@ -42,6 +55,17 @@ static inline constexpr int ira_tune_int(const char*, int dflt) { return dflt; }
 static inline constexpr const char* ira_tune_str(const char*) { return nullptr; }
 static inline constexpr bool ira_tune_flag(const char*) { return false; }
 #endif
+
+// Phase stamp (tuning build; `on` is an ablation bit or flag): var = the cycle counter once every access issued so far has
+// completed, fenced so that the scheduler moves nothing across it.
+#define IRA_STAMP(on, var)                                                                                                          \
+  do {                                                                                                                              \
+    if (IRA_ABL(on)) {                                                                                                              \
+      __builtin_amdgcn_sched_barrier(0);                                                                                            \
+      asm volatile("s_waitcnt lgkmcnt(0) vmcnt(0)\n\ts_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(var) :: "memory");               \
+      __builtin_amdgcn_sched_barrier(0);                                                                                            \
+    }                                                                                                                               \
+  } while (0)
 
 namespace ira {
 
@@ -89,6 +113,27 @@ __device__ __forceinline__ T uniform(T v) {
     __builtin_memcpy(&v, w, 8);
   }
   return v;
+}
+
+// ---- XCD-aware bijective workgroup remap (speed only) ---------------------------------------------------------------------
+// Workgroups of a 2-D grid are dealt round-robin over the 8 XCDs (each with its own L2).  The remapped linear index gives each
+// XCD a contiguous range of the grid instead, so that neighbouring workgroups -- which share samples, or the two halves of the
+// same 128-byte lines -- meet in one L2.
+__device__ __forceinline__ unsigned xcd_remap_linear() {
+  const unsigned nwg = gridDim.x * gridDim.y;
+  const unsigned orig = blockIdx.y * gridDim.x + blockIdx.x;
+  const unsigned q = nwg / 8, r = nwg % 8, xcd = orig % 8;
+  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + orig / 8;
+}
+__device__ __forceinline__ void xcd_remap(unsigned& bx, unsigned& by) {
+  const unsigned wg = xcd_remap_linear();
+  bx = wg % gridDim.x; by = wg / gridDim.x;
+}
+
+// One-wave team fence: the LDS instructions of a wave execute in order; only the compiler must not reorder across this.
+__device__ __forceinline__ void wave_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+  __builtin_amdgcn_wave_barrier();
 }
 
 // ---- wave-level reductions (64 lanes) ---------------------------------------------------------

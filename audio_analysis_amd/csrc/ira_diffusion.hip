@@ -355,11 +355,7 @@ extern "C" int32_t ira_diffusion(const float* x_dev, const int64_t* xoff_dev, co
   if (rc != IRA_OK || nb == 0 || max_frames == 0) return rc;
   const size_t lds = diff_lds_bytes(win, max_lag, false);
   if (lds > 150 * 1024) return IRA_E_SIZE;
-  if (lds > 48 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&diffusion_mono_kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return ira_hip_status(e);
-  }
+  IRA_TRY_HIP(allow_lds(&diffusion_mono_kernel, lds, 48 * 1024));
   diffusion_mono_kernel<<<dim3(max_frames, nb), DF_THREADS, lds, (hipStream_t)stream>>>(
       x_dev, xoff_dev, nframes_dev, win, hop, max_lag, thr_rms, gauss_expected, ac_dev, ed_dev, out_off_dev, pw_plan_of(win));
   IRA_RETURN_LAUNCH();
@@ -375,11 +371,7 @@ extern "C" int32_t ira_diffusion_stereo(const float* x_dev, const int64_t* loff_
   if (rc != IRA_OK || nb == 0 || max_frames == 0) return rc;
   const size_t lds = diff_lds_bytes(win, max_lag, true);
   if (lds > 150 * 1024) return IRA_E_SIZE;
-  if (lds > 48 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&diffusion_stereo_kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return ira_hip_status(e);
-  }
+  IRA_TRY_HIP(allow_lds(&diffusion_stereo_kernel, lds, 48 * 1024));
   diffusion_stereo_kernel<<<dim3(max_frames, nb), DF_THREADS, lds, (hipStream_t)stream>>>(
       x_dev, loff_dev, roff_dev, nframes_dev, win, hop, max_lag, corr0_dev, iacc_dev, out_off_dev, pw_plan_of(win));
   IRA_RETURN_LAUNCH();

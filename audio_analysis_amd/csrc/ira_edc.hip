@@ -1155,11 +1155,7 @@ extern "C" int32_t ira_edc_fits(const float* x_dev, const int64_t* off_dev, cons
   P.floor_db = floor_db; P.min_peak_above_floor = 0.0; P.t_mul = t_mul; P.t_div = t_div; P.t_axis = nullptr;
   hipStream_t st = (hipStream_t)stream;
   const int ntiles = (int)((max_len + EDC_TILE - 1) / EDC_TILE);
-  if (sizeof(EdcFitShared) > 64 * 1024) {   // > 64 KB of dynamic LDS needs the opt-in (idempotent, host-side only)
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(edc_fit_kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(EdcFitShared));
-    if (e != hipSuccess) return ira_hip_status(e);
-  }
+  IRA_TRY_HIP(allow_lds(edc_fit_kernel, sizeof(EdcFitShared)));
   if (tile_part_dev != nullptr && (part_off_dev == nullptr || part_wgs_dev == nullptr || part_tiles_dev == nullptr))
     return IRA_E_NULL;
   edc_sums_kernel<<<dim3(ntiles, nseg), EDC_THREADS, 0, st>>>(x_dev, off_dev, len_dev, scratch_dev,

@@ -1,6 +1,7 @@
 // In-register building blocks shared by the register-resident STFT (ira_stft2.hip) and the radix-16 passes of the
 // in-LDS FFT (ira_fft_lds.h): constant twiddles, R-point decimation-in-frequency DFTs on register arrays, and a
-// shallow power tree for per-butterfly twiddles.
+// shallow power tree for per-butterfly twiddles; and the per-bin split of a complex transform that carried two real signals
+// (ira_fftlong.hip, ira_fftsmooth.hip, ira_spectrum.hip).
 #pragma once
 #include "ira_common.h"
 
@@ -124,6 +125,41 @@ template <typename T, int LR, bool BREV>
 __device__ __forceinline__ void twiddle_r(cplx<T> (&v)[1 << LR], cplx<T> w) {
   if constexpr (LR == 4) twiddle16<T, BREV>(v, w);
   else twiddle8<T, BREV>(v, w);
+}
+
+// ---- two real signals in one complex transform ----------------------------------------------------------------------------
+// With Z = DFT_L(x1 + i x2) and zl = Z[(L - k) mod L]:
+//   X1[k] = (Z[k] + conj zl) / 2,   X2[k] = (Z[k] - conj zl) / (2i).
+template <typename T>
+struct cplx2 {
+  cplx<T> x1, x2;
+};
+template <typename T>
+__device__ __forceinline__ cplx2<T> hermitian_parts(cplx<T> zk, cplx<T> zl) {
+  const T h = (T)0.5;
+  return {{h * (zk.re + zl.re), h * (zk.im - zl.im)}, {h * (zk.im + zl.im), h * (zl.re - zk.re)}};
+}
+
+// Bin k = 0 .. L/2 of the two half spectra.  k = 0 and k = L/2 pair a bin with itself, so their imaginary parts come out
+// exactly zero like numpy's rfft.  The caller reads its job's offsets BEFORE this (the stores may alias the job tables).
+__device__ __forceinline__ void pair_split_bin(const cplx<double>* z, long long L, long long k, cplx<double>* x1,
+                                               cplx<double>* x2) {
+  const cplx2<double> x = hermitian_parts(z[k], z[k == 0 ? 0 : L - k]);
+  *x1 = x.x1;
+  *x2 = x.x2;
+}
+
+// Interleaved signal: z[m] = x[2m] + i x[2m+1], Z = DFT_L(z); bin k = 0 .. L of the real signal's spectrum of length 2L is
+//   X[k] = E[k] + W_2L^k O[k],  (E, O) = hermitian_parts(Z[k], Z[L-k])   (Z index mod L)
+// Returned, not stored: of the two kernels that use it one reads its output offset before the arithmetic and one after it, and
+// each keeps its order.
+__device__ __forceinline__ cplx<double> half_split_bin(const cplx<double>* z, long long L, long long k) {
+  const auto [ev, od] = hermitian_parts(z[k == L ? 0 : k], z[(k == 0 || k == L) ? 0 : L - k]);
+  double sn, cs;
+  sincospi(-(double)k / (double)L, &sn, &cs);                 // W_2L^k = exp(-i pi k / L)
+  cplx<double> x = {ev.re + (cs * od.re - sn * od.im), ev.im + (cs * od.im + sn * od.re)};
+  if (k == 0 || k == L) x.im = 0.0;                            // DC / Nyquist of a real signal
+  return x;
 }
 
 }  // namespace ira

@@ -206,14 +206,6 @@ struct Ctx {
   double fv;
 };
 
-__device__ __forceinline__ BandMask uniform_band(const BandMask& p) {
-  BandMask b{};
-  b.kind = ira::uniform(p.kind);
-  b.hp_x0 = ira::uniform(p.hp_x0); b.hp_x1 = ira::uniform(p.hp_x1);
-  b.lp_x0 = ira::uniform(p.lp_x0); b.lp_x1 = ira::uniform(p.lp_x1);
-  return b;
-}
-
 template <int MODE>
 __device__ __forceinline__ Ctx job_ctx(const Jobs& J, int e) {
   Ctx c{};
@@ -246,8 +238,8 @@ __device__ __forceinline__ Ctx job_ctx(const Jobs& J, int e) {
     c.o1 = ira::uniform(o1);
     c.o2 = J.spec_off2 ? ira::uniform(o2) : c.o1;
     c.two = c.o2 != c.o1;
-    c.b1 = uniform_band(b1);
-    c.b2 = uniform_band(b2);
+    c.b1 = ira::uniform_band(b1);
+    c.b2 = ira::uniform_band(b2);
     c.fv = ira::uniform(fv);
     ira::band_cuts(c.b1, c.b2, c.fv, (int)(c.L / 2), c.k1, c.k2);
     c.Lu = (unsigned)c.L;
@@ -333,16 +325,6 @@ __device__ __forceinline__ cd value_input(const Jobs& J, const Ctx& c, unsigned 
   }
 }
 
-// XCD-aware remap (speed only): give each XCD a contiguous range of (element, tile) pairs so that neighbouring
-// column tiles -- which touch the two halves of the same 128-byte lines -- meet in one L2.
-__device__ __forceinline__ void remap_xcd(unsigned& bx, unsigned& by) {
-  const unsigned gx = gridDim.x, nwg = gridDim.x * gridDim.y;
-  const unsigned orig = blockIdx.y * gx + blockIdx.x;
-  const unsigned q = nwg / 8, r = nwg % 8, xcd = orig % 8;
-  const unsigned wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + orig / 8;
-  bx = wg % gx; by = wg / gx;
-}
-
 // ---------------------------------------------------------------------------------------------------------
 // K1: columns forward.  grid (N2 / C, nb); LDS C * (N1 + 1) complex.
 // ---------------------------------------------------------------------------------------------------------
@@ -351,7 +333,7 @@ __global__ __launch_bounds__(FL_THREADS) __attribute__((amdgpu_waves_per_eu(4, 4
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   cd* lds = reinterpret_cast<cd*>(smem_raw);
   unsigned bx, by;
-  remap_xcd(bx, by);
+  ira::xcd_remap(bx, by);   // (element, tile) pairs: neighbouring column tiles touch the two halves of the same lines
   const int e = (int)by + J.e0;
   const Ctx ctx = job_ctx<MODE>(J, e);
   const long long L = ctx.L;
@@ -523,7 +505,7 @@ __global__ __launch_bounds__(FL_THREADS) __attribute__((amdgpu_waves_per_eu(4, 4
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   cd* lds = reinterpret_cast<cd*>(smem_raw);
   unsigned bx, by;
-  remap_xcd(bx, by);
+  ira::xcd_remap(bx, by);
   const int e = (int)by + J.e0;
   const unsigned N2 = 1u << g.log2n2;
   const long long M = g.m;
@@ -605,7 +587,7 @@ __global__ __launch_bounds__(FL_THREADS) __attribute__((amdgpu_waves_per_eu(4, 4
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   cd* lds = reinterpret_cast<cd*>(smem_raw);
   unsigned bx, by;
-  remap_xcd(bx, by);
+  ira::xcd_remap(bx, by);
   const int e = (int)by + J.e0;
   // the job's length and output offsets, once (scalar registers; see Ctx)
   long long L, out1, out2 = -1;
@@ -692,9 +674,7 @@ __global__ __launch_bounds__(FL_THREADS) __attribute__((amdgpu_waves_per_eu(4, 4
   }
 }
 
-// Two real signals per transform: with Z = DFT(x1 + i x2),
-//   X1[k] = (Z[k] + conj Z[L-k]) / 2,   X2[k] = (Z[k] - conj Z[L-k]) / (2i),   k = 0 .. L/2.
-// k = 0 and k = L/2 pair a bin with itself, so their imaginary parts come out exactly zero like numpy's rfft.
+// Two real signals per transform: Z = DFT(x1 + i x2) -> the two half spectra (ira::pair_split_bin).
 __global__ __launch_bounds__(256) void pair_split_kernel(Jobs J) {
   const int e = blockIdx.y;
   if (J.x2off[e] < 0 || (J.interleave && J.interleave[e])) return;
@@ -703,13 +683,10 @@ __global__ __launch_bounds__(256) void pair_split_kernel(Jobs J) {
   if (k > L / 2) return;
   const cd* z = J.zpair + J.zpair_off[e];
   const long long o1 = J.spec_out_off[e], o2 = J.spec_out_off2[e];      // before the stores (see Ctx)
-  const cd zk = z[k], zl = z[k == 0 ? 0 : L - k];
-  J.spec_out[o1 + k] = {0.5 * (zk.re + zl.re), 0.5 * (zk.im - zl.im)};
-  J.spec_out[o2 + k] = {0.5 * (zk.im + zl.im), 0.5 * (zl.re - zk.re)};
+  ira::pair_split_bin(z, L, k, J.spec_out + o1 + k, J.spec_out + o2 + k);
 }
 
-// Interleaved jobs: z[m] = x[2m] + i x[2m+1], Z = DFT_L(z); the real signal's spectrum of length 2L is
-//   X[k] = E[k] + W_2L^k O[k],  E = (Z[k] + conj Z[L-k]) / 2,  O = (Z[k] - conj Z[L-k]) / (2i),  k = 0 .. L  (Z index mod L)
+// Interleaved jobs: the half-length transform untangled into the real signal's spectrum (ira::half_split_bin).
 __global__ __launch_bounds__(256) void half_split_kernel(Jobs J) {
   const int e = blockIdx.y;
   if (!J.interleave[e]) return;
@@ -717,14 +694,7 @@ __global__ __launch_bounds__(256) void half_split_kernel(Jobs J) {
   const long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (k > L) return;
   const cd* z = J.zpair + J.zpair_off[e];
-  const cd zk = z[k == L ? 0 : k], zl = z[(k == 0 || k == L) ? 0 : L - k];
-  const cd ev = {0.5 * (zk.re + zl.re), 0.5 * (zk.im - zl.im)};
-  const cd od = {0.5 * (zk.im + zl.im), 0.5 * (zl.re - zk.re)};
-  double sn, cs;
-  sincospi(-(double)k / (double)L, &sn, &cs);                 // W_2L^k = exp(-i pi k / L)
-  cd x = {ev.re + (cs * od.re - sn * od.im), ev.im + (cs * od.im + sn * od.re)};
-  if (k == 0 || k == L) x.im = 0.0;                            // DC / Nyquist of a real signal
-  J.spec_out[J.spec_out_off[e] + k] = x;
+  J.spec_out[J.spec_out_off[e] + k] = ira::half_split_bin(z, L, k);
 }
 
 // M = N1 x N2.  The column passes (K1, K3) touch C adjacent columns of every row, i.e. C*16-byte pieces at a stride
@@ -797,19 +767,6 @@ int32_t make_plan(int32_t m, const void* t1, const void* t2, const void* tf, Pla
   p->lds_rows = ((size_t)R * N2 + ira::TW_SPLIT_ENTRIES) * sizeof(cd);
   return IRA_OK;
 }
-
-template <typename K>
-hipError_t allow_lds(K kernel, size_t bytes) {
-  if (bytes <= 64 * 1024) return hipSuccess;
-  return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                             (int)bytes);
-}
-
-#define IRA_TRY_HIP(expr)                          \
-  do {                                             \
-    hipError_t _e = (expr);                        \
-    if (_e != hipSuccess) return ira_hip_status(_e); \
-  } while (0)
 
 template <int IN, int OUT>
 int32_t run_convolution(const Plan& p, const Jobs& J, cd* work, int nb, hipStream_t st) {

@@ -262,7 +262,6 @@ __device__ __forceinline__ int dif_slot(int k, const PassTab& T) {
   return slot;
 }
 
-using BandMaskS = ira::BandMask;
 
 struct SJobs {
   // forward: one or two real signals per job
@@ -285,7 +284,7 @@ struct SJobs {
   // inverse: masked spectra -> band signals
   const cd* spec;
   const int64_t* sp_off; const int64_t* sp_off2;
-  const BandMaskS* bands;
+  const ira::BandMask* bands;
   const double* freq_val;
   float* y;
   const int64_t* y1_off; const int64_t* y2_off;
@@ -335,19 +334,11 @@ struct SCtx {
   int nd1, nd2, lw1, lw2;           // SM_SIGNAL: samples actually read / Hann window lengths of the two signals
   const cd* sp1; const cd* sp2;     // SM_SPECTRUM: the two spectra
   bool two;                         // SM_SPECTRUM: the two bands come from two different spectra
-  BandMaskS b1, b2;
+  ira::BandMask b1, b2;
   ira::MaskCuts k1, k2;             // first bins past each mask edge (ira_bandmask.h)
   int s1_lo, s1_hi, s2_lo, s2_hi;   // bins where band 1 / band 2 can be non-zero
   double fv;
 };
-
-__device__ __forceinline__ BandMaskS uniform_band(const BandMaskS& p) {
-  BandMaskS b{};
-  b.kind = ira::uniform(p.kind);
-  b.hp_x0 = ira::uniform(p.hp_x0); b.hp_x1 = ira::uniform(p.hp_x1);
-  b.lp_x0 = ira::uniform(p.lp_x0); b.lp_x1 = ira::uniform(p.lp_x1);
-  return b;
-}
 
 // (all loads first, then the moves to scalar registers: ONE round trip)
 template <int MODE>
@@ -381,13 +372,13 @@ __device__ __forceinline__ SCtx smooth_ctx(const SmoothPlan& P, const SJobs& J, 
   } else {
     const long long o1 = J.sp_off[e];
     const long long o2 = J.sp_off2 ? (long long)J.sp_off2[e] : -1ll;
-    const BandMaskS b1 = J.bands[2 * e], b2 = J.bands[2 * e + 1];
+    const ira::BandMask b1 = J.bands[2 * e], b2 = J.bands[2 * e + 1];
     const double fv = J.freq_val[e];
     c.o1 = ira::uniform(o1);
     c.o2 = J.sp_off2 ? ira::uniform(o2) : c.o1;
     c.two = c.o2 != c.o1;
-    c.b1 = uniform_band(b1);
-    c.b2 = uniform_band(b2);
+    c.b1 = ira::uniform_band(b1);
+    c.b2 = ira::uniform_band(b2);
     c.fv = ira::uniform(fv);
     ira::band_cuts(c.b1, c.b2, c.fv, J.half_out ? (int)n : (int)(n / 2), c.k1, c.k2);   // highest bin of the half spectrum
     ira::band_support(c.b1, c.k1, c.s1_lo, c.s1_hi);
@@ -546,18 +537,8 @@ __global__ __launch_bounds__(256) void band_compact_kernel(SmoothPlan P, SJobs J
 constexpr int SM_U = 8;     // independent loads in flight per thread (pass 2)
 constexpr int SM_UC = 5;    // (pass 1: a fetch is up to four doubles; 640 x 2 columns = 5 x 256: ONE round of loads)
 
-// XCD-aware remap (speed only): workgroups are dealt round-robin over the 8 XCDs, each with its own L2.  Neighbouring
-// column tiles read/write different 32-byte pieces of the SAME 128-byte lines; give each XCD a contiguous range of
-// (job, tile) pairs so that those pieces meet in one L2.
-__device__ __forceinline__ void smooth_remap(unsigned& bx, unsigned& by) {
-  const unsigned gx = gridDim.x, nwg = gridDim.x * gridDim.y;
-  const unsigned orig = blockIdx.y * gx + blockIdx.x;
-  const unsigned q = nwg / 8, r = nwg % 8, xcd = orig % 8;
-  const unsigned wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + orig / 8;
-  bx = wg % gx; by = wg / gx;
-}
-
-#define SM_STAMP(var) do { if (IRA_ABL(P.stamp)) { __builtin_amdgcn_sched_barrier(0); asm volatile("s_waitcnt lgkmcnt(0) vmcnt(0)\n\ts_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(var) :: "memory"); __builtin_amdgcn_sched_barrier(0); } } while (0)
+// The kernels below take their (job, tile) pair through ira::xcd_remap: neighbouring column tiles read / write different
+// 32-byte pieces of the SAME 128-byte lines, and the remap makes those pieces meet in one L2.
 
 // ---- pass 1: columns.  grid (N2 / C, jobs) ------------------------------------------------------------------------------
 template <int MODE, bool HALF = false>
@@ -568,11 +549,11 @@ __global__ __launch_bounds__(SM_THREADS, ((MODE == SM_SIGNAL || !HALF) ? 6 : 5))
   const int LD = P.ld1;                                    // column stride in LDS
   cd* twl = a + (size_t)C * LD;                            // SM_TW entries
   unsigned bx, by;
-  smooth_remap(bx, by);
+  ira::xcd_remap(bx, by);
   const int e = (int)by, tid = threadIdx.x;
   const int n2_0 = (int)bx * C;
   unsigned long long s0 = 0, s1 = 0, s2 = 0, s3 = 0;
-  SM_STAMP(s0);
+  IRA_STAMP(P.stamp, s0);
   if (MODE == SM_SPECTRUM && J.info != nullptr && ira::uniform(J.info[SM_SPARSE_INFO * e]) != 0) return;   // narrow job: no pass 1
   const SCtx ctx = smooth_ctx<MODE>(P, J, e);
   const cd twv = twiddle_lds_fetch(P.t1, N1, tid);        // issued first: shares the round trip of the tile loads below
@@ -616,10 +597,10 @@ __global__ __launch_bounds__(SM_THREADS, ((MODE == SM_SIGNAL || !HALF) ? 6 : 5))
   }
   twiddle_lds_put(twl, twv, tid);
   __syncthreads();
-  SM_STAMP(s1);
+  IRA_STAMP(P.stamp, s1);
   const cd* r = a;
   if (!(IRA_ABL(P.ablate & 8))) lds_fft_dif_inplace(a, LD, P.p1, twl, tid, C);
-  SM_STAMP(s2);
+  IRA_STAMP(P.stamp, s2);
   cd* w = work + (long long)e * P.n;
   const int C2 = P.c2;
   // SM_SIGNAL with HALF = the MIRROR-PAIR layout of the intermediate (SmoothPlan::pairs): position j of a column stands for
@@ -657,7 +638,7 @@ __global__ __launch_bounds__(SM_THREADS, ((MODE == SM_SIGNAL || !HALF) ? 6 : 5))
     }
   }
   if (IRA_ABL(P.stamp)) {
-    SM_STAMP(s3);
+    IRA_STAMP(P.stamp, s3);
     if (tid == 0 && blockIdx.x == gridDim.x / 2 && blockIdx.y == gridDim.y / 2)
       printf("SMOOTH cols<%d> N1 %d C %d: input %llu  fft %llu  twiddle+store %llu cycles\n", MODE, N1, C, s1 - s0, s2 - s1, s3 - s2);
   }
@@ -730,13 +711,13 @@ __global__ __launch_bounds__(SM_THREADS) void smooth_rows_kernel(SmoothPlan P, S
   const int LD = P.ld2;                                    // column stride in LDS
   cd* twl = a + (size_t)C * LD;
   unsigned bx, by;
-  smooth_remap(bx, by);
+  ira::xcd_remap(bx, by);
   const int e = (int)by, tid = threadIdx.x;
   const int k1_0 = (int)bx * C;
   const cd* w = work + (long long)e * P.n;
   if (OUT == SM_OUT_BANDS && J.info != nullptr && ira::uniform(J.info[SM_SPARSE_INFO * e]) != 0) return;   // narrow job: see below
   unsigned long long s0 = 0, s1 = 0, s2 = 0, s3 = 0;
-  SM_STAMP(s0);
+  IRA_STAMP(P.stamp, s0);
   // the job's output offsets, once (scalar registers; see SCtx)
   bool paired = false;
   long long out1 = 0, out2 = -1;
@@ -785,10 +766,10 @@ __global__ __launch_bounds__(SM_THREADS) void smooth_rows_kernel(SmoothPlan P, S
   }
   twiddle_lds_put(twl, twv, tid);
   __syncthreads();
-  SM_STAMP(s1);
+  IRA_STAMP(P.stamp, s1);
   const cd* r = a;
   if (!(IRA_ABL(P.ablate & 16))) lds_fft_dif_inplace(a, LD, P.p2, twl, tid, C);
-  SM_STAMP(s2);
+  IRA_STAMP(P.stamp, s2);
   const long long n = P.n;
   if (OUT == SM_OUT_SPEC_PAIRS) {
     // The tile holds Z = DFT_n(x[2m] + i x[2m+1]) on rows a and b = the mirror of a (tile 0: rows 0 and n1/2, each its own
@@ -814,8 +795,7 @@ __global__ __launch_bounds__(SM_THREADS) void smooth_rows_kernel(SmoothPlan P, S
       const int k2m = self0 ? (k2 == 0 ? 0 : N2 - k2) : N2 - 1 - k2;
       const int cm = p == 0 ? c : 1 - c;
       const cd zk = r[c * LD + dif_slot(k2, P.p2)], zl = r[cm * LD + dif_slot(k2m, P.p2)];
-      const cd ev = {0.5 * (zk.re + zl.re), 0.5 * (zk.im - zl.im)};
-      const cd od = {0.5 * (zk.im + zl.im), 0.5 * (zl.re - zk.re)};
+      const auto [ev, od] = ira::hermitian_parts(zk, zl);
       cd x = {ev.re + (cs * od.re - sn * od.im), ev.im + (cs * od.im + sn * od.re)};
       if (k == 0) x.im = 0.0;                                              // DC of a real signal
       J.spec_out[out1 + k] = x;
@@ -849,7 +829,7 @@ __global__ __launch_bounds__(SM_THREADS) void smooth_rows_kernel(SmoothPlan P, S
   }
   if (OUT == SM_OUT_BANDS && J.tile_part != nullptr) band_tile_partials(P, J, r, LD, k1_0, e, bx, out2 >= 0, tid);
   if (IRA_ABL(P.stamp)) {
-    SM_STAMP(s3);
+    IRA_STAMP(P.stamp, s3);
     if (tid == 0 && blockIdx.x == gridDim.x / 2 && blockIdx.y == gridDim.y / 2)
       printf("SMOOTH rows<%d> N2 %d C %d: load %llu  fft %llu  output %llu cycles\n", OUT, N2, C, s1 - s0, s2 - s1, s3 - s2);
   }
@@ -870,7 +850,7 @@ __global__ __launch_bounds__(SM_THREADS, 5) void smooth_rows_sparse_kernel(Smoot
   cd* twl = a + (size_t)C * LD;
   cd* rt = twl + SM_TW;                                    // per-row tables: C rows of SM_SPARSE_R + SM_TW entries
   unsigned bx, by;
-  smooth_remap(bx, by);
+  ira::xcd_remap(bx, by);
   const int e = (int)by, tid = threadIdx.x;
   const int32_t* inf = J.info + (size_t)SM_SPARSE_INFO * e;
   const int i_narrow = inf[0], i_lo = inf[1], i_w = inf[2], i_q = inf[3];
@@ -986,7 +966,7 @@ __global__ __launch_bounds__(SM_THREADS, 5) void smooth_rows_sparse_kernel(Smoot
   if (J.tile_part != nullptr) band_tile_partials(P, J, r, LD, k1_0, e, bx, out2 >= 0, tid);
 }
 
-// split of Z = DFT(x1 + i x2) into the two half spectra (same convention as pair_split_kernel in ira_fftlong.hip)
+// split of Z = DFT(x1 + i x2) into the two half spectra (ira::pair_split_bin)
 __global__ __launch_bounds__(256) void smooth_pair_split_kernel(SmoothPlan P, SJobs J) {
   const int e = blockIdx.y;
   if (J.x2off == nullptr || J.x2off[e] < 0) return;
@@ -995,14 +975,10 @@ __global__ __launch_bounds__(256) void smooth_pair_split_kernel(SmoothPlan P, SJ
   if (k > L / 2) return;
   const cd* z = J.zpair + J.zpair_off[e];
   const long long o1 = J.spec_off[e], o2 = J.spec_off2[e];      // before the stores (see SCtx)
-  const cd zk = z[k], zl = z[k == 0 ? 0 : L - k];
-  J.spec_out[o1 + k] = {0.5 * (zk.re + zl.re), 0.5 * (zk.im - zl.im)};
-  J.spec_out[o2 + k] = {0.5 * (zk.im + zl.im), 0.5 * (zl.re - zk.re)};
+  ira::pair_split_bin(z, L, k, J.spec_out + o1 + k, J.spec_out + o2 + k);
 }
 
-// Interleaved jobs: z[m] = x[2m] + i x[2m+1], Z = DFT_L(z); the real signal's spectrum of length 2L is
-//   X[k] = E[k] + W_2L^k O[k],  E = (Z[k] + conj Z[L-k]) / 2,  O = (Z[k] - conj Z[L-k]) / (2i),  k = 0 .. L  (Z index mod L)
-// (same convention as half_split_kernel in ira_fftlong.hip)
+// Interleaved jobs: the half-length transform untangled into the real signal's spectrum (ira::half_split_bin)
 __global__ __launch_bounds__(256) void smooth_half_split_kernel(SmoothPlan P, SJobs J) {
   const int e = blockIdx.y;
   const long long L = P.n;
@@ -1010,14 +986,7 @@ __global__ __launch_bounds__(256) void smooth_half_split_kernel(SmoothPlan P, SJ
   if (k > L) return;
   const cd* z = J.zpair + J.zpair_off[e];
   const long long o1 = J.spec_off[e];                           // before the store (see SCtx)
-  const cd zk = z[k == L ? 0 : k], zl = z[(k == 0 || k == L) ? 0 : L - k];
-  const cd ev = {0.5 * (zk.re + zl.re), 0.5 * (zk.im - zl.im)};
-  const cd od = {0.5 * (zk.im + zl.im), 0.5 * (zl.re - zk.re)};
-  double sn, cs;
-  sincospi(-(double)k / (double)L, &sn, &cs);                 // W_2L^k = exp(-i pi k / L)
-  cd x = {ev.re + (cs * od.re - sn * od.im), ev.im + (cs * od.im + sn * od.re)};
-  if (k == 0 || k == L) x.im = 0.0;                            // DC / Nyquist of a real signal
-  J.spec_out[o1 + k] = x;
+  J.spec_out[o1 + k] = ira::half_split_bin(z, L, k);
 }
 
 // ---- planning ------------------------------------------------------------------------------------------------------------
@@ -1176,14 +1145,6 @@ int32_t make_smooth_plan(int32_t n, const void* t1, const void* t2, const void* 
   return IRA_OK;
 }
 
-template <typename K>
-hipError_t allow(K kernel, size_t bytes) {
-  if (bytes <= 64 * 1024) return hipSuccess;
-  return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-}
-
-#define SM_TRY(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) return ira_hip_status(_e); } while (0)
-
 }  // namespace
 
 // n = n1 * n2 with both factors <= 1024 and n = 2^a 3^b 5^c: IRA_OK and the split; otherwise IRA_E_UNSUPPORTED (use the
@@ -1231,14 +1192,14 @@ extern "C" int32_t ira_rfft_smooth(const float* x_dev, const int64_t* xoff_dev, 
   const size_t l1 = ((size_t)P.c1 * P.ld1 + SM_TW) * sizeof(cd), l2 = ((size_t)P.c2 * P.ld2 + SM_TW) * sizeof(cd);
   cd* work = reinterpret_cast<cd*>(work_dev);
   if (pairs) {
-    SM_TRY(allow(smooth_cols_kernel<SM_SIGNAL, true>, l1));
-    SM_TRY(allow(smooth_rows_kernel<SM_OUT_SPEC_PAIRS>, l2));
+    IRA_TRY_HIP(allow_lds(smooth_cols_kernel<SM_SIGNAL, true>, l1));
+    IRA_TRY_HIP(allow_lds(smooth_rows_kernel<SM_OUT_SPEC_PAIRS>, l2));
     smooth_cols_kernel<SM_SIGNAL, true><<<dim3(P.n2 / P.c1, nb), SM_THREADS, l1, st>>>(P, J, work);
     smooth_rows_kernel<SM_OUT_SPEC_PAIRS><<<dim3(P.n1 / 2, nb), SM_THREADS, l2, st>>>(P, J, work);
     IRA_RETURN_LAUNCH();
   }
-  SM_TRY(allow(smooth_cols_kernel<SM_SIGNAL>, l1));
-  SM_TRY(allow(smooth_rows_kernel<SM_OUT_SPEC>, l2));
+  IRA_TRY_HIP(allow_lds(smooth_cols_kernel<SM_SIGNAL>, l1));
+  IRA_TRY_HIP(allow_lds(smooth_rows_kernel<SM_OUT_SPEC>, l2));
   smooth_cols_kernel<SM_SIGNAL><<<dim3(P.n2 / P.c1, nb), SM_THREADS, l1, st>>>(P, J, work);
   smooth_rows_kernel<SM_OUT_SPEC><<<dim3(P.n1 / P.c2, nb), SM_THREADS, l2, st>>>(P, J, work);
   if (interleave)
@@ -1274,25 +1235,25 @@ extern "C" int32_t ira_band_irfft_smooth(const double* spec_dev, const int64_t* 
   SmoothPlan P;
   const int32_t rc = make_smooth_plan(n, t1_dev, t2_dev, tf_dev, &P);
   if (rc != IRA_OK) return rc;
-  static_assert(sizeof(BandMaskS) == 8 * sizeof(double), "band parameter record is 8 doubles");
+  static_assert(sizeof(ira::BandMask) == 8 * sizeof(double), "band parameter record is 8 doubles");
   SJobs J{};
   J.spec = reinterpret_cast<const cd*>(spec_dev); J.sp_off = spec_off_dev; J.sp_off2 = spec_off2_dev;
-  J.bands = reinterpret_cast<const BandMaskS*>(band_params_dev); J.freq_val = freq_val_dev;
+  J.bands = reinterpret_cast<const ira::BandMask*>(band_params_dev); J.freq_val = freq_val_dev;
   J.y = y_dev; J.y1_off = y1_off_dev; J.y2_off = y2_off_dev;
   J.half_out = half_out ? 1 : 0;
   J.tile_part = tile_part_dev;
   if (half_out && spec_off2_dev != nullptr) return IRA_E_UNSUPPORTED;       // one band of one spectrum per job
   hipStream_t st = (hipStream_t)stream;
   const size_t l1 = ((size_t)P.c1 * P.ld1 + SM_TW) * sizeof(cd), l2 = ((size_t)P.c2 * P.ld2 + SM_TW) * sizeof(cd);
-  SM_TRY(allow(smooth_cols_kernel<SM_SPECTRUM, false>, l1));
-  SM_TRY(allow(smooth_cols_kernel<SM_SPECTRUM, true>, l1));
-  SM_TRY(allow(smooth_rows_kernel<SM_OUT_BANDS>, l2));
+  IRA_TRY_HIP(allow_lds(smooth_cols_kernel<SM_SPECTRUM, false>, l1));
+  IRA_TRY_HIP(allow_lds(smooth_cols_kernel<SM_SPECTRUM, true>, l1));
+  IRA_TRY_HIP(allow_lds(smooth_rows_kernel<SM_OUT_BANDS>, l2));
   cd* work = reinterpret_cast<cd*>(work_dev);
   if (job_info_dev != nullptr && P.sparse_q > 0) {
     // narrow jobs: compact + one fused pass; the two regular passes below return at once for them (and these for the rest)
     J.info = job_info_dev;
     const size_t ls = l2 + (size_t)P.c2 * (SM_SPARSE_R + SM_TW) * sizeof(cd);
-    SM_TRY(allow(smooth_rows_sparse_kernel, ls));
+    IRA_TRY_HIP(allow_lds(smooth_rows_sparse_kernel, ls));
     const unsigned cb = (unsigned)(((long long)(P.sparse_q + 1) * P.n2 + 255) / 256);     // a cluster + its padding
     if (half_out) band_compact_kernel<true><<<dim3(cb, nb), 256, 0, st>>>(P, J, work);
     else band_compact_kernel<false><<<dim3(cb, nb), 256, 0, st>>>(P, J, work);

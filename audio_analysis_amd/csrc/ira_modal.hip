@@ -180,11 +180,7 @@ extern "C" int32_t ira_logbin_aggregate(const float* mag_dev, const int64_t* mag
     // rows the bins can touch: first/count live on the device, so take everything from k_base to the last row
     const int k_span = frame_major_rows - k_base;
     const size_t lds = sizeof(double) * (size_t)k_span;
-    if (lds > 64 * 1024) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&logbin_tf_kernel),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (e != hipSuccess) return ira_hip_status(e);
-    }
+    IRA_TRY_HIP(allow_lds(&logbin_tf_kernel, lds));
     logbin_tf_kernel<<<dim3(max_frames, nb), LBT_THREADS, lds, (hipStream_t)stream>>>(
         mag_dev, mag_off_dev, nframes_dev, frame_major_rows, k_base, k_span, first_dev, count_dev, nbins, out_dev,
         out_off_dev);

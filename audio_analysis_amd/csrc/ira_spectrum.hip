@@ -4,7 +4,7 @@
 // Compiled with -ffp-contract=off (the unwrap correction arithmetic mirrors NumPy's operation by operation).
 #include <cmath>
 
-#include "ira_common.h"
+#include "ira_fft_reg.h"
 #include "ira_log.h"
 
 namespace {
@@ -89,7 +89,7 @@ __global__ __launch_bounds__(256) void mag_phase_kernel(const cd* __restrict__ s
   const float floor_db32 = (float)(20.0 * log10(floor_lin));
   // packed element: s holds Z = DFT_l(x[2m] + i x[2m+1]), l = L/2 values (ira_rfft_any, keep_packed), and bin k of the real
   // signal's spectrum is formed here, where Z[k] and Z[l - k] are two contiguous streams -- the formulas of
-  // half_split_kernel (ira_fftlong.hip) without its pass over memory
+  // ira::half_split_bin (ira_fft_reg.h) without half_split_kernel's pass over memory
   const bool pk = packed != nullptr && ira::uniform(packed[e]) != 0;
   const long long l = (long long)L[e] / 2;
   // W_2l^k = exp(-i pi k / l) along a thread's bins (a grid stride apart) by rotation from an exactly reduced start value: two
@@ -104,8 +104,7 @@ __global__ __launch_bounds__(256) void mag_phase_kernel(const cd* __restrict__ s
     cd v;
     if (pk) {
       const cd zk = s[k == l ? 0 : k], zl = s[(k == 0 || k == l) ? 0 : l - k];
-      const cd ev = {0.5 * (zk.re + zl.re), 0.5 * (zk.im - zl.im)};
-      const cd od = {0.5 * (zk.im + zl.im), 0.5 * (zl.re - zk.re)};
+      const auto [ev, od] = ira::hermitian_parts(zk, zl);
       v = {ev.re + (cs * od.re - sn * od.im), ev.im + (cs * od.im + sn * od.re)};
       if (k == 0 || k == l) v.im = 0.0;                            // DC / Nyquist of a real signal
       const double nc = cs * rc - sn * rs;

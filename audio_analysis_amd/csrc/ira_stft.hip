@@ -116,11 +116,7 @@ int32_t launch_stft(const float* x, const int64_t* off, const int32_t* nframes, 
   auto kern = stft_kernel<T, true>;
   if constexpr (sizeof(T) == sizeof(double))     // float32 always has room for a column: no untiled float32 instance
     if (!tiled) kern = stft_kernel<T, false>;
-  if (lds > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)lds);
-    if (e != hipSuccess) return ira_hip_status(e);
-  }
+  IRA_TRY_HIP(allow_lds(kern, lds));
   const double floor_lin = std::pow(10.0, floor_db / 20.0);
   dim3 grid((max_frames + tb - 1) / tb, nseg);
   kern<<<grid, STFT_THREADS, lds, st>>>(x, off, nframes, log2n, hop, static_cast<const T*>(window),

@@ -76,12 +76,8 @@ struct Cfg {
 // other's global-load and LDS latencies.  Two-wave teams use the workgroup barrier.
 template <int TW>
 __device__ __forceinline__ void team_sync() {
-  if (TW == 1) {
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-  } else {
-    __syncthreads();
-  }
+  if (TW == 1) ira::wave_sync();
+  else __syncthreads();
 }
 
 template <typename T, int TW, int NT, int FS>
@@ -93,13 +89,9 @@ __global__ __launch_bounds__(64 * TW * NT) void stft2_kernel(
   using C = Cfg<T, TW>;
   constexpr int TB = NT * FS;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-  // XCD-aware remap (speed only): workgroups are dealt round-robin over the 8 XCDs, each with its own L2.
-  // Give every XCD a CONTIGUOUS range of (segment, frame-group) pairs so that neighbouring frame groups -- which
-  // write adjacent 64-byte halves of the same output lines and re-read 7/8 of each other's samples -- share an L2.
-  const unsigned gx = gridDim.x, nwg = gridDim.x * gridDim.y;
-  const unsigned orig = blockIdx.y * gx + blockIdx.x;
-  const unsigned xq = nwg / 8, xr = nwg % 8, xcd = orig % 8;
-  const unsigned wg = (xcd < xr ? xcd * (xq + 1) : xr * (xq + 1) + (xcd - xr) * xq) + orig / 8;   // bijective
+  // (segment, frame-group) pairs through the XCD-aware remap: neighbouring frame groups -- which write adjacent 64-byte
+  // halves of the same output lines and re-read 7/8 of each other's samples -- share an L2.
+  const unsigned gx = gridDim.x, wg = ira::xcd_remap_linear();
   const int seg = (int)(wg / gx);
   const int T_out = nframes[seg];
   const int col0 = (int)(wg % gx) * TB;
@@ -126,7 +118,6 @@ __global__ __launch_bounds__(64 * TW * NT) void stft2_kernel(
 
   // diagnostic (ablate bit 256): per-phase cycle stamps of wave 0 of workgroup (0,0), written over out[0..7]
   unsigned long long st[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-#define IRA_STAMP(i) do { if (IRA_ABL(ablate & 256)) { unsigned long long t_; __builtin_amdgcn_sched_barrier(0); asm volatile("s_waitcnt lgkmcnt(0) vmcnt(0)\n\ts_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_) :: "memory"); __builtin_amdgcn_sched_barrier(0); st[i] = t_; } } while (0)
   static_assert(FS == 1 || FS == 2, "FS == 2 holds frame 0's outputs in registers while frame 1 runs");
   float keep_lo[FS == 2 ? C::NPAIR : 1], keep_hi[FS == 2 ? C::NPAIR : 1], keep_mid = 0.f;
   float lo[C::NPAIR], hi[C::NPAIR], mid = 0.f;
@@ -145,7 +136,7 @@ __global__ __launch_bounds__(64 * TW * NT) void stft2_kernel(
     const int64_t frame = live ? (frame_sel ? (int64_t)frame_sel[sel_off[seg] + col] : (int64_t)col) : 0;
     const float* fx = xs + frame * hop;
 
-    if (fs == FS - 1) IRA_STAMP(0);
+    if (fs == FS - 1) IRA_STAMP(ablate & 256, st[0]);
     // ---- step 1: two 16-point DFTs over n1 straight from global memory ------------------------------------
 #pragma unroll 1
     for (int h = 0; h < 2; ++h) {
@@ -177,7 +168,7 @@ __global__ __launch_bounds__(64 * TW * NT) void stft2_kernel(
     }
     team_sync<TW>();
 
-    if (fs == FS - 1) IRA_STAMP(1);
+    if (fs == FS - 1) IRA_STAMP(ablate & 256, st[1]);
     // ---- step 2: two 16-point DFTs over n2, half by half (see Cfg::PAD1) ---------------------------------------------
     {
       cplx<T> p[16];
@@ -188,12 +179,12 @@ __global__ __launch_bounds__(64 * TW * NT) void stft2_kernel(
         const int k1 = bb / C::R3, n3 = bb % C::R3;
         cplx<T> b2[16];
         // read E1[k1][n2*R3 + n3]: within 8 (16) lanes n3 is consecutive, the next k1 row sits 48 banks further
-        if (h == 1) IRA_STAMP(8);
+        if (h == 1) IRA_STAMP(ablate & 256, st[8]);
 #pragma unroll
         for (int n2 = 0; n2 < 16; ++n2) b2[n2] = ex[k1 * C::ROW1 + n2 * C::R3 + n3];
-        if (h == 1) IRA_STAMP(9);
+        if (h == 1) IRA_STAMP(ablate & 256, st[9]);
         dft_dif<T, 16>(b2);
-        if (h == 1) IRA_STAMP(10);
+        if (h == 1) IRA_STAMP(ablate & 256, st[10]);
         team_sync<TW>();   // every lane's E1 reads of this half are done before the rows are overwritten
         // exchange 2 write: row (k1*16 + k2), stride R3 + 1 complex; half h only touches rows of its own k1 range
 #pragma unroll
@@ -201,12 +192,12 @@ __global__ __launch_bounds__(64 * TW * NT) void stft2_kernel(
           const cplx<T> a = b2[brev_bits(k2, 4)];
           ex[(k1 * 16 + k2) * C::ROW2 + n3] = (k2 == 0) ? a : ira::cmul(a, p[k2]);
         }
-        if (h == 1) IRA_STAMP(11);
+        if (h == 1) IRA_STAMP(ablate & 256, st[11]);
       }
     }
     team_sync<TW>();
 
-    if (fs == FS - 1) IRA_STAMP(2);
+    if (fs == FS - 1) IRA_STAMP(ablate & 256, st[2]);
     // ---- step 3: R3-point DFTs over n3; lane ends up holding Z[k1 + 16*k2 + 256*k3] for its rows r = k1*16 + k2 -----
     cplx<T> z3[C::H3][C::R3];
 #pragma unroll
@@ -229,7 +220,7 @@ __global__ __launch_bounds__(64 * TW * NT) void stft2_kernel(
     }
     team_sync<TW>();
 
-    if (fs == FS - 1) IRA_STAMP(3);
+    if (fs == FS - 1) IRA_STAMP(ablate & 256, st[3]);
     // ---- post: X[k], X[M-k] from (Z[k], Z[M-k]) -------------------------------------------------------------------------
 #pragma unroll
     for (int i = 0; i < C::NPAIR; ++i) {
@@ -260,7 +251,7 @@ __global__ __launch_bounds__(64 * TW * NT) void stft2_kernel(
         mid = qn;
       }
     }
-    if (fs == FS - 1) IRA_STAMP(4);
+    if (fs == FS - 1) IRA_STAMP(ablate & 256, st[4]);
     if (FS == 2 && fs == 0) {
 #pragma unroll
       for (int i = 0; i < (FS == 2 ? C::NPAIR : 1); ++i) { keep_lo[i] = lo[i]; keep_hi[i] = hi[i]; }
@@ -269,7 +260,7 @@ __global__ __launch_bounds__(64 * TW * NT) void stft2_kernel(
     team_sync<TW>();   // exchange buffer is reused by the next frame
   }
 
-  IRA_STAMP(5);
+  IRA_STAMP(ablate & 256, st[5]);
   __syncthreads();   // every team is done with its exchange buffer: the tile may overwrite them
   // ---- all teams' columns into one [F][TB+1] float tile (aliases the exchange buffers) ------------------------------------
   float* tile = reinterpret_cast<float*>(smem_raw);
@@ -291,7 +282,7 @@ __global__ __launch_bounds__(64 * TW * NT) void stft2_kernel(
     }
   }
   __syncthreads();
-  IRA_STAMP(6);
+  IRA_STAMP(ablate & 256, st[6]);
   const int ncol = (T_out - col0 < TB) ? T_out - col0 : TB;
   float* o = out + out_off[seg];
   constexpr int NTHR = 64 * TW * NT;
@@ -313,12 +304,11 @@ __global__ __launch_bounds__(64 * TW * NT) void stft2_kernel(
     }
   }
   if ((IRA_ABL(ablate & 256)) && wg == 1 && tid == 0) {
-    IRA_STAMP(7);
+    IRA_STAMP(ablate & 256, st[7]);
     printf("STAMPS step1 %llu step2 %llu step3 %llu post %llu keep %llu barrier %llu tile+store %llu | step2(h=1): reads %llu dft16 %llu tw+writes %llu\n",
            st[1] - st[0], st[2] - st[1], st[3] - st[2], st[4] - st[3], st[5] - st[4], st[6] - st[5], st[7] - st[6],
            st[9] - st[8], st[10] - st[9], st[11] - st[10]);
   }
-#undef IRA_STAMP
 }
 
 template <typename T, int TW, int NT, int FS>
@@ -333,11 +323,7 @@ int32_t launch2(const float* x, const int64_t* off, const int32_t* nframes, int3
   const size_t lds = lds_main + (sizeof(T) == 8 ? LOGTAB_N * sizeof(LogTabEntry) : 0);
   if (lds > 160 * 1024) return IRA_E_SIZE;
   auto kern = stft2_kernel<T, TW, NT, FS>;
-  if (lds > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)lds);
-    if (e != hipSuccess) return ira_hip_status(e);
-  }
+  IRA_TRY_HIP(allow_lds(kern, lds));
   const double floor_lin = std::pow(10.0, floor_db / 20.0);
   const int ablate = ira_tune_int("IRA_STFT2_ABLATE", 0);
   dim3 grid((max_frames + TB - 1) / TB, nseg);

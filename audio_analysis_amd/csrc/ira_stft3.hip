@@ -34,6 +34,7 @@ using ira::brev_bits;
 using ira::cplx;
 using ira::dft_dif;
 using ira::powers16;
+using ira::wave_sync;
 
 typedef cplx<float> cf;
 
@@ -43,12 +44,6 @@ constexpr int E2N3 = 272;    // E2 half: n3' stride (complex)
 constexpr int EXC = 1072;    // complex slots per team: max(16*66, 15 + 240 + 3*272 + 1, 2048 floats / 2)
 static_assert(EXC >= 16 * ROWH && EXC >= 15 + 16 * 15 + 3 * E2N3 + 1 && EXC * 2 >= M3, "exchange buffer too small");
 constexpr int NT = 16;       // one-wave teams per workgroup: four waves per SIMD, <= 128 VGPRs each
-
-__device__ __forceinline__ void wave_sync() {
-  // One-wave team: LDS instructions of a wave execute in order; only the compiler must not reorder across this.
-  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-}
 
 // 10 log10((re^2 + im^2) / 4) floored at floor_db.  The quarter belongs to the untangling below, which works on UN-halved
 // sums (32 multiplies by 0.5 fewer per frame); the floor is ONE v_max in the dB domain (numpy.maximum(|X|, 10^(floor/20))
@@ -109,61 +104,33 @@ __device__ __forceinline__ void powers16_exact(const cf* __restrict__ tw, unsign
   }
 }
 
-__global__ __launch_bounds__(64 * NT) void stft3_kernel(
-    const float* __restrict__ x, const int64_t* __restrict__ off, const int32_t* __restrict__ nframes, int hop,
-    const float* __restrict__ window, const cf* __restrict__ tw, float floor_lin, float floor_db,
-    float* __restrict__ out, const int64_t* __restrict__ out_off, const int32_t* __restrict__ frame_sel,
-    const int64_t* __restrict__ sel_off, int ablate, unsigned win_lds_off) {
-  constexpr int TB3 = NT;   // one frame per team -> NT output columns per workgroup
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-  // XCD-aware bijective remap: each XCD (own L2) gets a contiguous range of (segment, frame group) pairs, so the
-  // groups that share 7/8 of their samples and adjacent halves of the same output lines meet in one L2.
-  const unsigned gx = gridDim.x, nwg = gridDim.x * gridDim.y;
-  const unsigned orig = blockIdx.y * gx + blockIdx.x;
-  const unsigned xq = nwg / 8, xr = nwg % 8, xcd = orig % 8;
-  const unsigned wg = (xcd < xr ? xcd * (xq + 1) : xr * (xq + 1) + (xcd - xr) * xq) + orig / 8;
-  if ((IRA_ABL(ablate & 48)) && orig < 256u) {
-    // diagnostic: stagger the first round of workgroups so that co-resident ones are out of phase
-    const unsigned slot = (IRA_ABL(ablate & 16)) ? ((orig >> 3) & 1u) : ((orig >> 3) & 3u);
-    for (unsigned i = 0; i < slot * (unsigned)IRA_ABL(ablate >> 8); ++i) __builtin_amdgcn_s_sleep(100);
-  }
-  const int seg = (int)(wg / gx);
-  const int T_out = nframes[seg];
-  const int col0 = (int)(wg % gx) * TB3;
-  if (col0 >= T_out) return;
-  const int tid = threadIdx.x;
-  const int team = __builtin_amdgcn_readfirstlane(tid >> 6), q = tid & 63;
-  cf* ex = reinterpret_cast<cf*>(smem_raw) + (size_t)team * EXC;
-  unsigned long long st[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-#define IRA_STAMP(i) do { if (IRA_ABL(ablate & 128)) { unsigned long long t_; __builtin_amdgcn_sched_barrier(0); asm volatile("s_waitcnt lgkmcnt(0) vmcnt(0)\n\ts_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_) :: "memory"); __builtin_amdgcn_sched_barrier(0); st[i] = t_; } } while (0)
-  IRA_STAMP(0);
-  float* exf = reinterpret_cast<float*>(ex);
-  // The Hann window (16 KB) is the same for every frame: one copy in LDS per workgroup instead of 16 KB of L1 traffic
-  // per frame (the frame loads were L1-bound, DESIGN.md 4.1).  Lives behind the exchange buffers / tile.
-  float* winl = reinterpret_cast<float*>(smem_raw + win_lds_off);
-  for (int i = tid; i < 2 * M3; i += 64 * NT) winl[i] = window[i];
-  __syncthreads();
-
-  const int col = col0 + team;
-  // Columns past the end transform frame 0 and are dropped at the store (a per-load select makes hipcc branch
-  // around every load).
-  const int64_t frame = (col < T_out) ? (frame_sel ? (int64_t)frame_sel[sel_off[seg] + col] : (int64_t)col) : 0;
-  const float* fx = x + off[seg] + frame * hop;
-  if (IRA_ABL(ablate & 64)) fx = x + ((size_t)(wg * TB3 + team) * 4096u) % (size_t)(30720000u - 8192u);   // diagnostic: disjoint frames
+// Steps 1 to 3 of one frame with the exchanges E1 and E2 (see the head of this file), by one wave through its exchange buffer
+// ex: afterwards lane q holds Z[q + 64 hh + 256 k3] in z3[hh][brev3(k3)].  load_half(h, xa, xb) fetches the sixteen sample pairs
+// x[2n], x[2n + 1], n = n1 * 128 + q + 64 h, of half h.  Shared by the (F, T) and the frame-major kernel, which therefore
+// produce the same float32 values (test_frame_major_stft_is_the_exact_transpose).
+// Tuning build: flat_window replaces the window reads by constants (timing only); AB & 128 reads every twiddle from the table.
+template <int AB, typename LoadHalf>
+__device__ __forceinline__ void frame_steps(LoadHalf&& load_half, bool flat_window, const float* winl, const cf* __restrict__ tw,
+                                            cf* ex, int q, cf (&z3)[4][8]) {
   const int k1l = q & 15, n3a = q >> 4;
+  auto powers = [&](unsigned idx, cf (&p)[16]) {
+    if (AB & 128) powers16_exact(tw, idx, p);
+    else powers16<float>(tw[idx], p);
+  };
 
-  // ---- step 1 -------------------------------------------------------------------------------------------------
+  // ---- step 1 -----------------------------------------------------------------------------------------------------
   cf a1[16];   // half h = 1, held in registers until E1 is free again
 #pragma unroll
   for (int h = 0; h < 2; ++h) {
     const int m = q + 64 * h;
     float xa[16], xb[16], wa[16], wb[16];
     // all loads first, one wait (left alone hipcc serialises them behind vmcnt(1) waits)
+    load_half(h, xa, xb);
 #pragma unroll
     for (int n1 = 0; n1 < 16; ++n1) {
-      const int n = n1 * 128 + m;
-      if (IRA_ABL(ablate & 1)) { xa[n1] = (float)n; xb[n1] = (float)(n + 1); } else { xa[n1] = fx[2 * n]; xb[n1] = fx[2 * n + 1]; }
-      if (IRA_ABL(ablate & 2)) { wa[n1] = 0.5f; wb[n1] = 0.25f; } else { wa[n1] = winl[2 * n]; wb[n1] = winl[2 * n + 1]; }
+      const unsigned n = (unsigned)(n1 * 128 + m);
+      if (flat_window) { wa[n1] = 0.5f; wb[n1] = 0.25f; }
+      else { wa[n1] = winl[2u * n]; wb[n1] = winl[2u * n + 1u]; }
     }
     __builtin_amdgcn_sched_barrier(0);
     cf v[16];
@@ -171,7 +138,7 @@ __global__ __launch_bounds__(64 * NT) void stft3_kernel(
     for (int n1 = 0; n1 < 16; ++n1) v[n1] = {xa[n1] * wa[n1], xb[n1] * wb[n1]};
     dft_dif<float, 16>(v);
     cf p[16];
-    powers16<float>(tw[2 * m], p);                      // W_M^m = W_N^(2m)
+    powers((unsigned)(2 * m), p);                         // W_M^m = W_N^(2m)
     if (h == 0) {
 #pragma unroll
       for (int k1 = 0; k1 < 16; ++k1) {
@@ -187,7 +154,6 @@ __global__ __launch_bounds__(64 * NT) void stft3_kernel(
     }
   }
   wave_sync();
-  IRA_STAMP(1);
 
   // ---- E1 -> step-2 operands: n2 = 0..7 come from half 0, n2 = 8..15 from half 1 ------------------------------------
   cf b2[2][16];
@@ -206,18 +172,17 @@ __global__ __launch_bounds__(64 * NT) void stft3_kernel(
   wave_sync();
 
   // ---- step 2 and E2 (half hb = n3 in [4hb, 4hb + 4)) -> step-3 operands ---------------------------------------------
-  cf z3[4][8];
   {
     cf p[16];
     dft_dif<float, 16>(b2[0]);
-    powers16<float>(tw[32 * n3a], p);                    // W_M^(16 n3) = W_N^(32 n3)
+    powers((unsigned)(32 * n3a), p);                      // W_M^(16 n3) = W_N^(32 n3)
 #pragma unroll
     for (int k2 = 0; k2 < 16; ++k2) {
       const cf a = b2[0][brev_bits(k2, 4)];
       ex[k1l + 16 * k2 + E2N3 * n3a] = (k2 == 0) ? a : ira::cmul(a, p[k2]);
     }
     dft_dif<float, 16>(b2[1]);
-    powers16<float>(tw[32 * (n3a + 4)], p);
+    powers((unsigned)(32 * (n3a + 4)), p);
 #pragma unroll
     for (int k2 = 1; k2 < 16; ++k2) b2[1][brev_bits(k2, 4)] = ira::cmul(b2[1][brev_bits(k2, 4)], p[k2]);
   }
@@ -239,9 +204,13 @@ __global__ __launch_bounds__(64 * NT) void stft3_kernel(
   // ---- step 3: lane holds Z[r + 256 k3], r = q + 64 hh -----------------------------------------------------------------
 #pragma unroll
   for (int hh = 0; hh < 4; ++hh) dft_dif<float, 8>(z3[hh]);
+}
 
-  // ---- E3: real parts, then imaginary parts, natural order ------------------------------------------------------------
-  float zkr[16], zpr[16], zki[16], zpi[16], midr, midi;
+// E3 through LDS: natural order, real parts then imaginary parts through one 2048-float buffer; the lane gets Z[k] and its
+// mirror partner Z[M - k] for k = q + 64 i, and Z[M / 2].  (The caller fences before the buffer is written again.)
+__device__ __forceinline__ void mirror_exchange_lds(const cf (&z3)[4][8], float* exf, int q, float (&zkr)[16], float (&zpr)[16],
+                                                    float (&zki)[16], float (&zpi)[16], float& midr, float& midi) {
+  __builtin_assume((unsigned)q < 64u);
 #pragma unroll
   for (int hh = 0; hh < 4; ++hh)
 #pragma unroll
@@ -267,6 +236,62 @@ __global__ __launch_bounds__(64 * NT) void stft3_kernel(
     zpi[i] = exf[(M3 - k) & (M3 - 1)];
   }
   midi = exf[M3 / 2];
+}
+
+
+__global__ __launch_bounds__(64 * NT) void stft3_kernel(
+    const float* __restrict__ x, const int64_t* __restrict__ off, const int32_t* __restrict__ nframes, int hop,
+    const float* __restrict__ window, const cf* __restrict__ tw, float floor_lin, float floor_db,
+    float* __restrict__ out, const int64_t* __restrict__ out_off, const int32_t* __restrict__ frame_sel,
+    const int64_t* __restrict__ sel_off, int ablate, unsigned win_lds_off) {
+  constexpr int TB3 = NT;   // one frame per team -> NT output columns per workgroup
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  // XCD-aware remap: each XCD (own L2) gets a contiguous range of (segment, frame group) pairs, so the groups that share
+  // 7/8 of their samples and adjacent halves of the same output lines meet in one L2.
+  const unsigned gx = gridDim.x, wg = ira::xcd_remap_linear();
+  if (const unsigned orig = blockIdx.y * gx + blockIdx.x; (IRA_ABL(ablate & 48)) && orig < 256u) {
+    // diagnostic: stagger the first round of workgroups so that co-resident ones are out of phase
+    const unsigned slot = (IRA_ABL(ablate & 16)) ? ((orig >> 3) & 1u) : ((orig >> 3) & 3u);
+    for (unsigned i = 0; i < slot * (unsigned)IRA_ABL(ablate >> 8); ++i) __builtin_amdgcn_s_sleep(100);
+  }
+  const int seg = (int)(wg / gx);
+  const int T_out = nframes[seg];
+  const int col0 = (int)(wg % gx) * TB3;
+  if (col0 >= T_out) return;
+  const int tid = threadIdx.x;
+  const int team = __builtin_amdgcn_readfirstlane(tid >> 6), q = tid & 63;
+  cf* ex = reinterpret_cast<cf*>(smem_raw) + (size_t)team * EXC;
+  unsigned long long st[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  IRA_STAMP(ablate & 128, st[0]);
+  float* exf = reinterpret_cast<float*>(ex);
+  // The Hann window (16 KB) is the same for every frame: one copy in LDS per workgroup instead of 16 KB of L1 traffic
+  // per frame (the frame loads were L1-bound, DESIGN.md 4.1).  Lives behind the exchange buffers / tile.
+  float* winl = reinterpret_cast<float*>(smem_raw + win_lds_off);
+  for (int i = tid; i < 2 * M3; i += 64 * NT) winl[i] = window[i];
+  __syncthreads();
+
+  const int col = col0 + team;
+  // Columns past the end transform frame 0 and are dropped at the store (a per-load select makes hipcc branch
+  // around every load).
+  const int64_t frame = (col < T_out) ? (frame_sel ? (int64_t)frame_sel[sel_off[seg] + col] : (int64_t)col) : 0;
+  const float* fx = x + off[seg] + frame * hop;
+  if (IRA_ABL(ablate & 64)) fx = x + ((size_t)(wg * TB3 + team) * 4096u) % (size_t)(30720000u - 8192u);   // diagnostic: disjoint frames
+  // ---- steps 1 to 3 -------------------------------------------------------------------------------------------
+  cf z3[4][8];
+  frame_steps<0>(
+      [&](int h, float (&xa)[16], float (&xb)[16]) {
+#pragma unroll
+        for (int n1 = 0; n1 < 16; ++n1) {
+          const int n = n1 * 128 + q + 64 * h;
+          if (IRA_ABL(ablate & 1)) { xa[n1] = (float)n; xb[n1] = (float)(n + 1); } else { xa[n1] = fx[2 * n]; xb[n1] = fx[2 * n + 1]; }
+        }
+      },
+      IRA_ABL(ablate & 2), winl, tw, ex, q, z3);
+  IRA_STAMP(ablate & 128, st[1]);
+
+  // ---- E3 ----------------------------------------------------------------------------------------------------------
+  float zkr[16], zpr[16], zki[16], zpi[16], midr, midi;
+  mirror_exchange_lds(z3, exf, q, zkr, zpr, zki, zpi, midr, midi);
 
   // ---- post: X[k] = E + P, X[M-k] = conj(E - P) with E = (Zk + conj Zp)/2, P = W_N^k (-i)(Zk - conj Zp)/2 ---------------
   const cf wlane = tw[q];
@@ -291,10 +316,10 @@ __global__ __launch_bounds__(64 * NT) void stft3_kernel(
       mid = qn;
     }
   }
-  IRA_STAMP(2);
+  IRA_STAMP(ablate & 128, st[2]);
 
   __syncthreads();
-  IRA_STAMP(3);   // every team is done with its exchange buffer: the tile may overwrite them
+  IRA_STAMP(ablate & 128, st[3]);   // every team is done with its exchange buffer: the tile may overwrite them
   float* tile = reinterpret_cast<float*>(smem_raw);      // [F][TB + 1]
 #pragma unroll
   for (int i = 0; i < 16; ++i) {
@@ -304,7 +329,7 @@ __global__ __launch_bounds__(64 * NT) void stft3_kernel(
   }
   if (q == 0) tile[(M3 / 2) * (TB3 + 1) + team] = mid;
   __syncthreads();
-  IRA_STAMP(4);
+  IRA_STAMP(ablate & 128, st[4]);
 
   const int ncol = (T_out - col0 < TB3) ? T_out - col0 : TB3;
   float* o = out + out_off[seg];
@@ -329,11 +354,11 @@ __global__ __launch_bounds__(64 * NT) void stft3_kernel(
     __builtin_amdgcn_sched_barrier(0);
     asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t5) :: "memory");          // stores issued, not yet acknowledged
     asm volatile("s_waitcnt vmcnt(0)\n\ts_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t6) :: "memory");
+    const unsigned nwg = gx * gridDim.y;
     if ((wg == nwg / 2 || wg == nwg / 2 + 1) && q == 0 && (team == 0 || team == NT - 1))
-      printf("STAMP wg %u team %d: step1(load+dft) %llu  steps2-3+post %llu  barrier1 %llu  tile %llu  store-issue %llu  store-ack %llu\n",
+      printf("STAMP wg %u team %d: steps1-3 %llu  E3+post %llu  barrier1 %llu  tile %llu  store-issue %llu  store-ack %llu\n",
              wg, team, st[1] - st[0], st[2] - st[1], st[3] - st[2], st[4] - st[3], t5 - st[4], t6 - t5);
   }
-#undef IRA_STAMP
 }
 
 }  // namespace
@@ -347,10 +372,7 @@ int32_t ira_stft3_launch(const float* x, const int64_t* off, const int32_t* nfra
   constexpr size_t lds_main = ((lds_ex > lds_tile ? lds_ex : lds_tile) + 15) & ~(size_t)15;
   constexpr size_t lds = lds_main + (size_t)2 * M3 * sizeof(float);          // + the window copy
   static_assert(lds <= 160 * 1024, "one workgroup must fit the CU's LDS");
-  const hipError_t attr = lds <= 64 * 1024 ? hipSuccess
-                                            : hipFuncSetAttribute(reinterpret_cast<const void*>(&stft3_kernel),
-                                                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (attr != hipSuccess) return ira_hip_status(attr);
+  IRA_TRY_HIP(allow_lds(&stft3_kernel, lds));
   const double floor_lin = std::pow(10.0, floor_db / 20.0);
   const int ablate = ira_tune_int("IRA_STFT3_ABLATE", 0);   // diagnostics
   dim3 grid((max_frames + TB3 - 1) / TB3, nseg);
@@ -488,98 +510,12 @@ __global__ __launch_bounds__(64 * NT) void stft6_kernel(
         *reinterpret_cast<f4*>(tail + 4 * (q + 64 * (u & 3))) = v4;
       }
     }
-    const int k1l = q & 15, n3a = q >> 4;
     const cf wlane = tw[(unsigned)q];
 
-    // ---- step 1 ---------------------------------------------------------------------------------------------------
-    cf a1[16];
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const int m = q + 64 * h;
-      float xa[16], xb[16], wa[16], wb[16];
-      load_half(fx, q, h, xa, xb);                         // (all loads first, one wait)
-#pragma unroll
-      for (int n1 = 0; n1 < 16; ++n1) {
-        const unsigned n = (unsigned)(n1 * 128 + m);
-        if (AB & 2) { wa[n1] = 0.5f; wb[n1] = 0.25f; }
-        else { wa[n1] = winl[2u * n]; wb[n1] = winl[2u * n + 1u]; }
-      }
-      __builtin_amdgcn_sched_barrier(0);
-      cf v[16];
-#pragma unroll
-      for (int n1 = 0; n1 < 16; ++n1) v[n1] = {xa[n1] * wa[n1], xb[n1] * wb[n1]};
-      dft_dif<float, 16>(v);
-      cf p[16];
-      if (AB & 128) powers16_exact(tw, (unsigned)(2 * m), p);
-      else powers16<float>(tw[(unsigned)(2 * m)], p);      // W_M^m = W_N^(2m)
-      if (h == 0) {
-#pragma unroll
-        for (int k1 = 0; k1 < 16; ++k1) {
-          const cf a = v[brev_bits(k1, 4)];
-          ex[k1 * ROWH + q] = (k1 == 0) ? a : ira::cmul(a, p[k1]);
-        }
-      } else {
-#pragma unroll
-        for (int k1 = 0; k1 < 16; ++k1) {
-          const cf a = v[brev_bits(k1, 4)];
-          a1[k1] = (k1 == 0) ? a : ira::cmul(a, p[k1]);
-        }
-      }
-    }
-    wave_sync();
-
-    // ---- E1 -> step-2 operands ----------------------------------------------------------------------------------------
-    cf b2[2][16];
-#pragma unroll
-    for (int hb = 0; hb < 2; ++hb)
-#pragma unroll
-      for (int n2 = 0; n2 < 8; ++n2) b2[hb][n2] = ex[k1l * ROWH + n2 * 8 + n3a + 4 * hb];
-    wave_sync();
-#pragma unroll
-    for (int k1 = 0; k1 < 16; ++k1) ex[k1 * ROWH + q] = a1[k1];
-    wave_sync();
-#pragma unroll
-    for (int hb = 0; hb < 2; ++hb)
-#pragma unroll
-      for (int n2 = 0; n2 < 8; ++n2) b2[hb][8 + n2] = ex[k1l * ROWH + n2 * 8 + n3a + 4 * hb];
-    wave_sync();
-
-    // ---- step 2 and E2 ---------------------------------------------------------------------------------------------------
+    // ---- steps 1 to 3 ------------------------------------------------------------------------------------------------
     cf z3[4][8];
-    {
-      cf p[16];
-      dft_dif<float, 16>(b2[0]);
-      if (AB & 128) powers16_exact(tw, (unsigned)(32 * n3a), p);
-      else powers16<float>(tw[(unsigned)(32 * n3a)], p);
-#pragma unroll
-      for (int k2 = 0; k2 < 16; ++k2) {
-        const cf a = b2[0][brev_bits(k2, 4)];
-        ex[k1l + 16 * k2 + E2N3 * n3a] = (k2 == 0) ? a : ira::cmul(a, p[k2]);
-      }
-      dft_dif<float, 16>(b2[1]);
-      if (AB & 128) powers16_exact(tw, (unsigned)(32 * (n3a + 4)), p);
-      else powers16<float>(tw[(unsigned)(32 * (n3a + 4))], p);
-#pragma unroll
-      for (int k2 = 1; k2 < 16; ++k2) b2[1][brev_bits(k2, 4)] = ira::cmul(b2[1][brev_bits(k2, 4)], p[k2]);
-    }
-    wave_sync();
-#pragma unroll
-    for (int hh = 0; hh < 4; ++hh)
-#pragma unroll
-      for (int n3 = 0; n3 < 4; ++n3) z3[hh][n3] = ex[k1l + 16 * (n3a + 4 * hh) + E2N3 * n3];
-    wave_sync();
-#pragma unroll
-    for (int k2 = 0; k2 < 16; ++k2) ex[k1l + 16 * k2 + E2N3 * n3a] = b2[1][brev_bits(k2, 4)];
-    wave_sync();
-#pragma unroll
-    for (int hh = 0; hh < 4; ++hh)
-#pragma unroll
-      for (int n3 = 0; n3 < 4; ++n3) z3[hh][4 + n3] = ex[k1l + 16 * (n3a + 4 * hh) + E2N3 * n3];
-    wave_sync();
-
-    // ---- step 3 ---------------------------------------------------------------------------------------------------------
-#pragma unroll
-    for (int hh = 0; hh < 4; ++hh) dft_dif<float, 8>(z3[hh]);
+    frame_steps<AB>([&](int h, float (&xa)[16], float (&xb)[16]) { load_half(fx, q, h, xa, xb); }, (AB & 2) != 0, winl, tw,
+                    ex, q, z3);
 
     // ---- E3: the mirror partner Z[M - k] of every bin the lane holds.  After step 3 the lane already holds Z[q + 64 i'],
     // i' = hh + 4 k3 < 32, in natural order; the partner of k = q + 64 i (i < 16) is register 31 - i of lane (64 - q) & 63 --
@@ -590,31 +526,7 @@ __global__ __launch_bounds__(64 * NT) void stft6_kernel(
     // the same float32 values as before.  AB & 32 (tuning build) keeps the LDS form as the A/B.
     float zkr[16], zpr[16], zki[16], zpi[16], midr, midi;
     if (AB & 32) {
-#pragma unroll
-      for (int hh = 0; hh < 4; ++hh)
-#pragma unroll
-        for (int k3 = 0; k3 < 8; ++k3) exf[q + 64 * hh + 256 * k3] = z3[hh][brev_bits(k3, 3)].re;
-      wave_sync();
-#pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        const int k = q + 64 * i;
-        zkr[i] = exf[k];
-        zpr[i] = exf[(M3 - k) & (M3 - 1)];
-      }
-      midr = exf[M3 / 2];
-      wave_sync();
-#pragma unroll
-      for (int hh = 0; hh < 4; ++hh)
-#pragma unroll
-        for (int k3 = 0; k3 < 8; ++k3) exf[q + 64 * hh + 256 * k3] = z3[hh][brev_bits(k3, 3)].im;
-      wave_sync();
-#pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        const int k = q + 64 * i;
-        zki[i] = exf[k];
-        zpi[i] = exf[(M3 - k) & (M3 - 1)];
-      }
-      midi = exf[M3 / 2];
+      mirror_exchange_lds(z3, exf, q, zkr, zpr, zki, zpi, midr, midi);
       wave_sync();                                          // the next frame's step 1 writes this buffer again
     } else {
       // (the permutes are issued inside the post loop below, bin pair by bin pair: holding all 64 partner values beside the
@@ -702,9 +614,7 @@ int32_t ira_stft6_launch(const float* x, const int64_t* off, const int32_t* nfra
   const int stagger = ira_tune_int("IRA_STFT6_STAGGER", 0);
 #define IRA_LAUNCH6(AB)                                                                                                   \
   do {                                                                                                                    \
-    const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&stft6_kernel<AB>),                         \
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                    \
-    if (attr != hipSuccess) return ira_hip_status(attr);                                                                  \
+    IRA_TRY_HIP(allow_lds(&stft6_kernel<AB>, lds, 0));   /* whatever the size */                                          \
     stft6_kernel<AB><<<grid, 64 * NT, lds, st>>>(x, off, nframes, hop, static_cast<const float*>(window),                 \
                                                  static_cast<const cf*>(tw), (float)floor_lin, (float)floor_db, out,      \
                                                  out_off, frame_sel, sel_off, gx, (unsigned)tiles, (unsigned)lds_main,    \

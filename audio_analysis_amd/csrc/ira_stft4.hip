@@ -100,14 +100,12 @@ __global__ __launch_bounds__(TL5) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
   __shared__ ira::LogTabEntry ltab[ira::LOGTAB_N];
   __shared__ int lb_range[2];
   __shared__ int frame_bad;
-  // XCD-aware remap: the workgroups of one XCD (orig % 8) take a contiguous run of chunks, so that neighbouring chunks,
-  // whose frames overlap, share an L2
-  const unsigned gx = gridDim.x, nwg = gridDim.x * gridDim.y;
-  const unsigned orig = blockIdx.y * gx + blockIdx.x;
-  const unsigned xq = nwg / 8, xr = nwg % 8, xcd = orig % 8;
-  const unsigned wg = (xcd < xr ? xcd * (xq + 1) : xr * (xq + 1) + (xcd - xr) * xq) + orig / 8;
-  const int seg = (int)(wg / gx);
-  const int col0 = (int)(wg % gx) * kfr;
+  // XCD-aware remap: the workgroups of one XCD take a contiguous run of chunks, so that neighbouring chunks, whose frames
+  // overlap, share an L2
+  unsigned bx, by;
+  ira::xcd_remap(bx, by);
+  const int seg = (int)by;
+  const int col0 = (int)bx * kfr;
   const int T_out = ira::uniform(nframes[seg]);
   if (col0 >= T_out) return;                       // the whole workgroup, before its first barrier
   const int col1 = T_out - col0 < kfr ? T_out : col0 + kfr;

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Runs ONE report block over a synthetic batch a few times -- the program rocprofv3 (--kernel-trace --stats / --pmc) wraps
-when a single kernel family is studied.   python3 tools/block_probe.py --block modal|decay|bands|bands3rd|spectrum|stft|zplane|gd|diffusion"""
+when a single kernel family is studied.   python3 tools/block_probe.py --block modal|decay|bands|bands3rd|spectrum|stft|stft_ft|zplane|gd|diffusion"""
 import argparse, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -38,6 +38,7 @@ run = {
     "bands3rd": lambda: rt60bands.rt60_bands_device(eng, b, 48000, replace(s.rt60_bands, band_mode="third")),
     "spectrum": lambda: frequency_response.spectrum_device(eng, b, 48000, s.frequency_response, "spectrum", want_phase=True),
     "stft": lambda: spectrogram.spectrogram_device(eng, b, 48000, s.spectrogram, frame_major=True),
+    "stft_ft": lambda: spectrogram.spectrogram_device(eng, b, 48000, s.spectrogram, frame_major=False),
     "zplane": lambda: zplane.zplane_device(eng, b, 48000, s.zplane),
     "gd": lambda: group_delay.summary_statistics_device(eng, group_delay.group_delay_device(eng, b, 48000, s.group_delay), 48000, s.group_delay),
     "diffusion": lambda: diffusion.diffusion_device(eng, b, 48000, s.diffusion),
