@@ -42,6 +42,8 @@ SOURCES = {
     "ira_diffusion.hip": ["-ffp-contract=off"],
     # float64 energy products and sums round one operation at a time, like NumPy's
     "ira_energy.hip": ["-ffp-contract=off"],
+    # float64 lag sums of exact float32 products (explicit fma there rounds like multiply-then-add)
+    "ira_xcorr.hip": ["-ffp-contract=off"],
 }
 COMMON = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function"]
 

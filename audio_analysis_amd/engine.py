@@ -61,7 +61,7 @@ class _TimedLib:
     time can be read back after a synchronise (bench.py's roofline uses this).
     """
     _PLAIN = {"ira_error_string", "ira_abi_version", "ira_ar_partial_doubles", "ira_ar_exact_doubles",
-              "ira_energy_scratch_doubles"}
+              "ira_energy_scratch_doubles", "ira_xcorr_scratch_doubles"}
 
     def __init__(self, lib, eng):
         self._lib, self._eng, self._cache = lib, eng, {}
@@ -586,6 +586,38 @@ class Engine:
                                           max_len, _ptr(d_lim), nlim, _ptr(scratch), _ptr(out), self.stream),
               "ira_energy_windows")
         return out[: nseg * (nlim + 2)].view(nseg, nlim + 2)
+
+    # ------------------------------------------------------------------ ISO 3382-1 inter-channel cross-correlation
+    def xcorr_windows(self, x_dev, l_off: np.ndarray, r_off: np.ndarray, seg_len: np.ndarray, lchan_of_seg: np.ndarray,
+                      rchan_of_seg: np.ndarray, onset_dev, limits: np.ndarray, max_lag: int):
+        """Partitioned float64 lag sums between the two channels of stereo pairs (ira_xcorr_windows).  Segment j: left
+        channel seg_len[j] samples at l_off[j] of x_dev, right channel at r_off[j]; it starts at
+        o = min(onset_dev[lchan_of_seg[j]], onset_dev[rchan_of_seg[j]]), taken on the device; limits (nseg, nlim) int64
+        ascending sample counts from o.  Returns (nseg, nlim + 1, 2 max_lag + 3) float64 device: per partition
+        C(-max_lag .. +max_lag), El, Er."""
+        t = self.torch
+        l_off = np.ascontiguousarray(l_off, dtype=np.int64)
+        r_off = np.ascontiguousarray(r_off, dtype=np.int64)
+        seg_len = np.ascontiguousarray(seg_len, dtype=np.int64)
+        nseg = int(l_off.size)
+        limits = np.ascontiguousarray(limits, dtype=np.int64)
+        if limits.ndim != 2 or limits.shape[0] != nseg or r_off.size != nseg or seg_len.size != nseg:
+            raise ValueError("l_off, r_off, seg_len must be (nseg,) and limits (nseg, nlim)")
+        nlim, max_lag = int(limits.shape[1]), int(max_lag)
+        max_len = int(seg_len.max()) if nseg else 0
+        nsc = int(self.lib.ira_xcorr_scratch_doubles(nseg, max_len, nlim, max_lag))
+        check(min(nsc, 0), "ira_xcorr_scratch_doubles")
+        nrec = 2 * max_lag + 3
+        scratch = self.empty(nsc, t.float64)
+        out = self.empty(nseg * (nlim + 1) * nrec, t.float64)
+        d_lo, d_ro, d_len, d_lc, d_rc, d_lim = self.job_tables(
+            l_off, r_off, seg_len, np.ascontiguousarray(lchan_of_seg, np.int32),
+            np.ascontiguousarray(rchan_of_seg, np.int32), limits.reshape(-1))
+        with self.tagged(f"[T{max_lag}]"):
+            check(self.lib.ira_xcorr_windows(_ptr(x_dev), _ptr(d_lo), _ptr(d_ro), _ptr(d_len), _ptr(d_lc), _ptr(d_rc),
+                                             _ptr(onset_dev), nseg, max_len, _ptr(d_lim), nlim, max_lag, _ptr(scratch),
+                                             _ptr(out), self.stream), "ira_xcorr_windows")
+        return out[: nseg * (nlim + 1) * nrec].view(nseg, nlim + 1, nrec)
 
     # ------------------------------------------------------------------ a4/a5/a16
     def curve_fits(self, y_dev, off: np.ndarray, lens: np.ndarray, t_mul: float, t_div: float,

@@ -33,7 +33,7 @@ extern "C" {
 #define IRA_E_FORMAT (-5)     /* a file is not RIFF/WAVE (host-side ingest entry points only) */
 #define IRA_E_HIP_BASE (-1000)
 
-#define IRA_ABI_VERSION 9   /* bumped whenever an exported signature or a scratch-size constant changes */
+#define IRA_ABI_VERSION 10  /* bumped whenever an exported signature or a scratch-size constant changes */
 
 int32_t ira_abi_version(void);
 const char* ira_error_string(int32_t code);
@@ -555,6 +555,29 @@ int64_t ira_energy_scratch_doubles(int32_t nseg, int64_t max_len, int32_t nlim);
 int32_t ira_energy_windows(const float* x_dev, const int64_t* base_off_dev, const int64_t* base_len_dev,
                            const int32_t* chan_of_seg_dev, const int64_t* onset_dev, int32_t nseg, int64_t max_len,
                            const int64_t* limits_dev, int32_t nlim, double* scratch_dev, double* out_dev, void* stream);
+
+/* ---- ISO 3382-1 Annex B inter-channel cross-correlation: IACC_E, IACC_L, IACC_A -------------------------------------
+ * Nothing in the reference computes these (its only two-channel quantity is the short-time series of the diffusion
+ * block); both entry points replace no reference function.  Host side: audio_analysis_amd/analyse/iacc.py
+ * (`python -m analyse.iacc`).
+ * ira_xcorr_windows: segment j is one signal row of a stereo pair: left channel len_dev[j] samples at x_dev + l_off_dev[j],
+ *   right channel as many at x_dev + r_off_dev[j].  o = min(onset_dev[lchan_of_seg_dev[j]], onset_dev[rchan_of_seg_dev[j]])
+ *   is taken on the device (band rows of a pair share its broadband onsets), L = len - o, n counts from o.  With the
+ *   segment's nlim (1..4) ascending sample limits limits_dev[j * nlim + k] the partitions are [0, N_1), ..., [N_nlim, L),
+ *   and out_dev[(j * (nlim + 1) + i) * (2 T + 3) + ...] holds for partition i, T = max_lag (1..IRA_XCORR_MAX_LAG):
+ *     C(tau) = sum_n l[o + n] r[o + n + tau], tau = -T .. T in this order (r = 0 outside the file: the right channel is read
+ *     across partition boundaries and in front of the onset, never wrapped), then El = sum_n l[o + n]^2, Er = sum_n r[o + n]^2.
+ *   Float64 products and sums of the exact float32 samples, in an order that depends on the segment's length, onset and
+ *   limits alone (bit-identical whatever the batch, the segment's place in it or its alignment); no atomics.
+ *   max_len >= every len (< 2^31); nseg <= 65535; scratch_dev holds as many doubles as the size call returns
+ *   (IRA_E_SIZE, negative, for arguments out of range; the size call is host only).  Argument errors are reported
+ *   before anything is launched. */
+#define IRA_XCORR_MAX_LAG 128
+int64_t ira_xcorr_scratch_doubles(int32_t nseg, int64_t max_len, int32_t nlim, int32_t max_lag);
+int32_t ira_xcorr_windows(const float* x_dev, const int64_t* l_off_dev, const int64_t* r_off_dev, const int64_t* len_dev,
+                          const int32_t* lchan_of_seg_dev, const int32_t* rchan_of_seg_dev, const int64_t* onset_dev,
+                          int32_t nseg, int64_t max_len, const int64_t* limits_dev, int32_t nlim, int32_t max_lag,
+                          double* scratch_dev, double* out_dev, void* stream);
 
 #ifdef __cplusplus
 }
