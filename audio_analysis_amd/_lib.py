@@ -13,7 +13,7 @@ _LIB_PATH = Path(__file__).resolve().parent / "csrc" / "libira.so"
 _lib = None
 # must equal IRA_ABI_VERSION of include/ira.h: a stale .so called with this file's prototypes would read shifted
 # arguments or undersized scratch (memory corruption on the GPU instead of a clean error)
-ABI_VERSION = 10
+ABI_VERSION = 11
 
 c_f32p = C.c_void_p
 c_i64p = C.c_void_p
@@ -82,6 +82,10 @@ PROTOTYPES = {
     "ira_energy_windows": (i32, [vp, vp, vp, vp, vp, i32, C.c_int64, vp, i32, vp, vp, vp]),
     "ira_xcorr_scratch_doubles": (C.c_int64, [i32, C.c_int64, i32, i32]),
     "ira_xcorr_windows": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, C.c_int64, vp, i32, i32, vp, vp, vp]),
+    "ira_lundeby_scratch_doubles": (C.c_int64, [i32, i32]),
+    "ira_block_energy": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp]),
+    "ira_lundeby_estimate": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, vp, i32, vp, vp, vp, vp]),
+    "ira_edc_truncated": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, f64, f64, vp, vp, vp]),
 }
 
 

@@ -44,6 +44,8 @@ SOURCES = {
     "ira_energy.hip": ["-ffp-contract=off"],
     # float64 lag sums of exact float32 products (explicit fma there rounds like multiply-then-add)
     "ira_xcorr.hip": ["-ffp-contract=off"],
+    # float64 block energies, regression sums and suffix sums round one operation at a time
+    "ira_lundeby.hip": ["-ffp-contract=off"],
 }
 COMMON = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function"]
 

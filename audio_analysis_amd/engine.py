@@ -9,6 +9,7 @@ single-channel drop-in functions in audio_analysis_amd.analyse.* call them with 
 from __future__ import annotations
 
 import ctypes
+import math
 import os
 from contextlib import contextmanager
 from dataclasses import dataclass, fields
@@ -34,6 +35,49 @@ def _unit_roots(count: int, period: int) -> np.ndarray:
     """exp(-2 pi i k / period), k < count: float64 (count, 2), interleaved (re, im)."""
     ang = -2.0 * np.pi * np.arange(count, dtype=np.float64) / float(period)
     return np.stack([np.cos(ang), np.sin(ang)], axis=1)
+
+
+LUNDEBY_DOUBLES = 16          # IRA_LUNDEBY_DOUBLES
+LUNDEBY_MAX_BLOCKS = 4096     # IRA_LUNDEBY_MAX_BLOCKS
+LUNDEBY_STAGE = 4096          # samples a workgroup of the two sample passes stages; the largest block size
+LUNDEBY_MAX_LEN = 2047 * 4096
+
+
+def lundeby_layout(base_off, base_len, chan_of_seg, blk_size, nblk, first_m) -> Dict[str, object]:
+    """Host side of the Lundeby row tables (pure NumPy): the tables in the kernels' types, every row's table offset
+    blk_off = j * (max nb + 1), table_doubles = nseg * (max nb + 1) (what ira_lundeby_scratch_doubles answers) and
+    max_chunks = max over the rows of ceil((nb + 1) / (4096 // B)), the grid width of the two sample passes.
+    ValueError for tables the kernels would refuse."""
+    base_off = np.ascontiguousarray(base_off, dtype=np.int64).reshape(-1)
+    n = int(base_off.size)
+    tabs = dict(base_off=base_off, base_len=np.ascontiguousarray(base_len, dtype=np.int64).reshape(-1),
+                chan_of_seg=np.ascontiguousarray(chan_of_seg, dtype=np.int32).reshape(-1),
+                blk_size=np.ascontiguousarray(blk_size, dtype=np.int32).reshape(-1),
+                nblk=np.ascontiguousarray(nblk, dtype=np.int32).reshape(-1),
+                first_m=np.ascontiguousarray(first_m, dtype=np.int32).reshape(-1))
+    if any(v.size != n for v in tabs.values()):
+        raise ValueError("base_off, base_len, chan_of_seg, blk_size, nblk and first_m must have one entry per row")
+    if n > 65535:
+        raise ValueError("at most 65535 rows per launch")
+    b, nb = tabs["blk_size"].astype(np.int64), tabs["nblk"].astype(np.int64)
+    if n and (b.min() < 1 or b.max() > LUNDEBY_STAGE):
+        raise ValueError(f"block sizes must be 1 .. {LUNDEBY_STAGE} samples")
+    if n and (nb.min() < 0 or nb.max() > LUNDEBY_MAX_BLOCKS):
+        raise ValueError(f"block counts must be 0 .. {LUNDEBY_MAX_BLOCKS}")
+    if n and tabs["first_m"].min() < 1:
+        raise ValueError("first_m must be at least 1 block")
+    if n and (tabs["base_len"].min() < 0 or tabs["base_len"].max() > LUNDEBY_MAX_LEN or np.any(nb * b > tabs["base_len"])):
+        raise ValueError(f"rows must hold their nb * B samples and at most {LUNDEBY_MAX_LEN}")
+    if n and tabs["chan_of_seg"].min() < 0:
+        raise ValueError("chan_of_seg must index the start array")
+    stride = int(nb.max()) + 1 if n else 1
+    tabs["blk_off"] = np.arange(n, dtype=np.int64) * stride
+    tabs["nseg"] = n
+    tabs["stride"] = stride
+    tabs["table_doubles"] = n * stride
+    per_chunk = LUNDEBY_STAGE // np.maximum(b, 1)
+    tabs["max_chunks"] = int(np.max(-(-(nb + 1) // per_chunk))) if n else 1
+    return tabs
 
 
 @dataclass
@@ -619,15 +663,81 @@ class Engine:
                                              _ptr(out), self.stream), "ira_xcorr_windows")
         return out[: nseg * (nlim + 1) * nrec].view(nseg, nlim + 1, nrec)
 
+    # ------------------------------------------------------------------ ISO 3382-1 noise handling (Lundeby)
+    def lundeby_rows(self, base_off: np.ndarray, base_len: np.ndarray, chan_of_seg: np.ndarray, blk_size: np.ndarray,
+                     nblk: np.ndarray, first_m: np.ndarray) -> Dict[str, object]:
+        """The row tables block_energy, lundeby_estimate and edc_truncated share, checked on the host (lundeby_layout:
+        ValueError before anything is uploaded or launched) and uploaded once.  Row j: base_len[j] samples at base_off[j] of
+        the sample buffer, read from the start index of channel chan_of_seg[j] on; blk_size / nblk / first_m: B, nb, m0."""
+        lay = lundeby_layout(base_off, base_len, chan_of_seg, blk_size, nblk, first_m)
+        dev = self.job_tables(lay["base_off"], lay["base_len"], lay["chan_of_seg"], lay["blk_size"], lay["nblk"],
+                              lay["first_m"], lay["blk_off"])
+        lay["dev"] = dev
+        return lay
+
+    def block_energy(self, x_dev, rows, start_dev):
+        """Float64 block energies (ira_block_energy): row j's nb + 1 values (the last one its partial tail block) at
+        rows["blk_off"][j] of the returned device array."""
+        t = self.torch
+        n = rows["nseg"]
+        blk = self.empty(rows["table_doubles"], t.float64)
+        if n:
+            d_off, d_len, d_ch, d_b, d_nb, _, d_boff = rows["dev"]
+            check(self.lib.ira_block_energy(_ptr(x_dev), _ptr(d_off), _ptr(d_len), _ptr(d_ch), _ptr(start_dev), _ptr(d_b),
+                                            _ptr(d_nb), _ptr(d_boff), n, rows["max_chunks"], _ptr(blk), self.stream),
+                  "ira_block_energy")
+        return blk
+
+    def lundeby_estimate(self, rows, start_dev, blk_dev, compensate: bool = True):
+        """Cross-point estimate per row (ira_lundeby_estimate).  Returns (records (nseg, LUNDEBY_DOUBLES) float64 device,
+        curve lengths int64 device (nseg,), per-block suffix energies float64 device laid out like blk_dev)."""
+        t = self.torch
+        n = rows["nseg"]
+        rec = self.empty(n * LUNDEBY_DOUBLES, t.float64)
+        lens = self.empty(n, t.int64)
+        suffix = self.empty(rows["table_doubles"], t.float64)
+        if n:
+            _, d_len, d_ch, d_b, d_nb, d_m, d_boff = rows["dev"]
+            check(self.lib.ira_lundeby_estimate(_ptr(d_len), _ptr(d_ch), _ptr(start_dev), _ptr(d_b), _ptr(d_nb), _ptr(d_m),
+                                                _ptr(d_boff), n, _ptr(blk_dev), 1 if compensate else 0, _ptr(rec),
+                                                _ptr(lens), _ptr(suffix), self.stream), "ira_lundeby_estimate")
+        return rec[: n * LUNDEBY_DOUBLES].view(n, LUNDEBY_DOUBLES), lens[:n], suffix
+
+    def edc_truncated(self, x_dev, rows, start_dev, rec_dev, lens_dev, suffix_dev, eps: float, floor_db: float, edc_dev,
+                      edc_off: np.ndarray) -> None:
+        """The truncated, compensated float32 dB curve of every row (ira_edc_truncated) at edc_off[j] of edc_dev (float32
+        device); nothing is written at or after the row's curve length.  edc_dev may be the sample buffer itself for a row
+        whose curve replaces its own samples (edc_off[j] = the address of the row's start index)."""
+        n = rows["nseg"]
+        edc_off = np.ascontiguousarray(edc_off, dtype=np.int64)
+        if edc_off.shape != (n,):
+            raise ValueError("edc_off must be (nseg,)")
+        if not (float(eps) >= 0.0) or math.isnan(float(floor_db)):
+            raise ValueError("eps must be >= 0 and floor_db a number")
+        if n:
+            d_off, d_len, d_ch, d_b, d_nb, _, d_boff = rows["dev"]
+            d_eoff, = self.job_tables(edc_off)
+            check(self.lib.ira_edc_truncated(_ptr(x_dev), _ptr(d_off), _ptr(d_len), _ptr(d_ch), _ptr(start_dev), _ptr(d_b),
+                                             _ptr(d_nb), _ptr(d_boff), n, rows["max_chunks"], _ptr(rec_dev), _ptr(lens_dev),
+                                             _ptr(suffix_dev), float(eps), float(floor_db), _ptr(edc_dev), _ptr(d_eoff),
+                                             self.stream), "ira_edc_truncated")
+
     # ------------------------------------------------------------------ a4/a5/a16
     def curve_fits(self, y_dev, off: np.ndarray, lens: np.ndarray, t_mul: float, t_div: float,
                    ranges: Sequence[Tuple[float, float]], min_points: int, cross: Sequence[float] = (),
                    rel_to_peak: bool = False, floor_db: float = -120.0, min_peak_above_floor: float = 0.0,
-                   t_axis_dev=None):
-        """Returns (fits (ncurves, nranges, 8) float64 device, cross (ncurves, ncross) float64 device)."""
+                   t_axis_dev=None, lens_dev=None):
+        """Returns (fits (ncurves, nranges, 8) float64 device, cross (ncurves, ncross) float64 device).
+        lens_dev (int64 device, (ncurves,)): the curves' lengths as a kernel left them on the device; they need not visit
+        the host.  lens then only bounds them from above (it picks the workgroup size, which fixes the order of the
+        regression sums)."""
         n = int(off.size)
         fit, cr, c_ranges, c_cross, views = self._fit_outputs(n, ranges, cross)
-        d_off, d_len = self.job_tables(off, lens)
+        if lens_dev is None:
+            d_off, d_len = self.job_tables(off, lens)
+        else:
+            d_off, = self.job_tables(off)
+            d_len = lens_dev
         check(self.lib.ira_curve_fits(_ptr(y_dev), _ptr(d_off), _ptr(d_len), n,
                                       int(lens.max()) if n else 0, float(t_mul), float(t_div), _ptr(t_axis_dev),
                                       c_ranges, len(ranges), int(min_points), c_cross, len(cross), 1 if rel_to_peak else 0,

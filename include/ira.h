@@ -33,7 +33,7 @@ extern "C" {
 #define IRA_E_FORMAT (-5)     /* a file is not RIFF/WAVE (host-side ingest entry points only) */
 #define IRA_E_HIP_BASE (-1000)
 
-#define IRA_ABI_VERSION 10  /* bumped whenever an exported signature or a scratch-size constant changes */
+#define IRA_ABI_VERSION 11  /* bumped whenever an exported signature or a scratch-size constant changes */
 
 int32_t ira_abi_version(void);
 const char* ira_error_string(int32_t code);
@@ -578,6 +578,55 @@ int32_t ira_xcorr_windows(const float* x_dev, const int64_t* l_off_dev, const in
                           const int32_t* lchan_of_seg_dev, const int32_t* rchan_of_seg_dev, const int64_t* onset_dev,
                           int32_t nseg, int64_t max_len, const int64_t* limits_dev, int32_t nlim, int32_t max_lag,
                           double* scratch_dev, double* out_dev, void* stream);
+
+/* ---- ISO 3382-1 noise handling: Lundeby cross-point, truncated and compensated Schroeder integration ------------------
+ * Nothing in the reference estimates a noise floor (its decay fits integrate to the last sample of the file); the four
+ * entry points below replace no reference function.  Host side and the algorithm they carry out, step by step:
+ * audio_analysis_amd/analyse/lundeby.py (`python -m analyse.lundeby`).
+ * Rows: row j is base_len[j] - s samples from x_dev + base_off[j] + s, s = start_dev[chan_of_seg[j]] read on the device (the
+ *   band rows of a channel share its broadband start index), L = base_len[j] - s.  blk_size_dev[j] = B (1..4096) and
+ *   nblk_dev[j] = nb (<= IRA_LUNDEBY_MAX_BLOCKS) are the host's; a row whose nb != L / B, or whose L exceeds 2047 * 4096
+ *   samples, is treated as a row without blocks (status IRA_LUNDEBY_TOO_SHORT), never read out of bounds.  The row's table
+ *   of nb + 1 doubles lies at blk_off_dev[j] of blk_dev and of suffix_dev (ira_lundeby_scratch_doubles(nseg, max nb) doubles
+ *   each hold every row at a stride of max nb + 1; IRA_E_SIZE, negative, for arguments out of range; host only).
+ *   max_chunks >= ceil((nb + 1) / (4096 / B)) for every row sizes the grids of the two sample passes.  nseg <= 65535.
+ *   Argument errors are reported before anything is launched.  Float64 sums in an order that depends on the row's own B and
+ *   L alone: results are bit-identical whatever the batch, the row's place in it or its alignment; no atomics.
+ * ira_block_energy: blk[j] = sum of float64(y)^2 over block j < nb; blk[nb] = the same over the partial tail block (0 if
+ *   there is none).
+ * ira_lundeby_estimate: steps 2 to 6 of the algorithm; first_m_dev[j] = m0 (intervals of the preliminary pass, in blocks);
+ *   compensate = 1 adds the compensation energy C, 0 truncates only.  rec_dev: IRA_LUNDEBY_DOUBLES doubles per row:
+ *     [0] status (IRA_LUNDEBY_* bits) [1] Ln dB [2] t1 samples [3] slope dB per sample [4] intercept dB [5] C
+ *     [6] rounds [7] m1 [8] kmax [9] k0 [10] k1 [11] preliminary cross-point [12] final cross-point (samples) [13] max M
+ *     [14] edc[0] (energy, C included) [15] blocks the curve covers;  [1..15] are NaN on an error status (bits 1 to 16).
+ *   len_out_dev[j] (int64): samples of the curve: t1; L with IRA_LUNDEBY_NO_FLOOR; 0 on an error status.
+ *   suffix_dev: per block of the curve the energy behind it inside the curve, plus C.
+ * ira_edc_truncated: edc[i] = (reverse sum inside i's block) + suffix[block] for i < len_dev[j] (edc[0] is rec[14] to
+ *   the bit), then the chain of ira_edc_db: max(., eps) / max(edc[0], eps) -> 10 log10 -> max(., floor_db) -> float32 at
+ *   edc_dev + edc_off_dev[j].  Nothing is written at or after len_dev[j].  A row may be written over its own samples
+ *   (edc_dev + edc_off_dev[j] == x_dev + base_off[j] + s). */
+#define IRA_LUNDEBY_DOUBLES 16
+#define IRA_LUNDEBY_MAX_BLOCKS 4096
+#define IRA_LUNDEBY_SILENT 1
+#define IRA_LUNDEBY_TOO_SHORT 2
+#define IRA_LUNDEBY_NO_RANGE 4
+#define IRA_LUNDEBY_SLOPE 8
+#define IRA_LUNDEBY_NON_FINITE 16
+#define IRA_LUNDEBY_NO_FLOOR 32
+int64_t ira_lundeby_scratch_doubles(int32_t nseg, int32_t max_nblk);
+int32_t ira_block_energy(const float* x_dev, const int64_t* base_off_dev, const int64_t* base_len_dev,
+                         const int32_t* chan_of_seg_dev, const int64_t* start_dev, const int32_t* blk_size_dev,
+                         const int32_t* nblk_dev, const int64_t* blk_off_dev, int32_t nseg, int32_t max_chunks,
+                         double* blk_dev, void* stream);
+int32_t ira_lundeby_estimate(const int64_t* base_len_dev, const int32_t* chan_of_seg_dev, const int64_t* start_dev,
+                             const int32_t* blk_size_dev, const int32_t* nblk_dev, const int32_t* first_m_dev,
+                             const int64_t* blk_off_dev, int32_t nseg, const double* blk_dev, int32_t compensate,
+                             double* rec_dev, int64_t* len_out_dev, double* suffix_dev, void* stream);
+int32_t ira_edc_truncated(const float* x_dev, const int64_t* base_off_dev, const int64_t* base_len_dev,
+                          const int32_t* chan_of_seg_dev, const int64_t* start_dev, const int32_t* blk_size_dev,
+                          const int32_t* nblk_dev, const int64_t* blk_off_dev, int32_t nseg, int32_t max_chunks,
+                          const double* rec_dev, const int64_t* len_dev, const double* suffix_dev, double eps,
+                          double floor_db, float* edc_dev, const int64_t* edc_off_dev, void* stream);
 
 #ifdef __cplusplus
 }
