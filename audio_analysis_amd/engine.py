@@ -663,6 +663,33 @@ class Engine:
                                              _ptr(out), self.stream), "ira_xcorr_windows")
         return out[: nseg * (nlim + 1) * nrec].view(nseg, nlim + 1, nrec)
 
+    # ------------------------------------------------------------------ IEC 60268-16 modulation transfer sums
+    def mtf_sums(self, x_dev, seg_off: np.ndarray, seg_len: np.ndarray, w: np.ndarray):
+        """Float64 modulation transfer sums of the squared signal (ira_mtf_sums).  Row j: seg_len[j] samples at seg_off[j] of
+        x_dev; w (nseg, nf) float64 modulation frequencies in turns per sample (frequency / sample rate, per row), nf <= 16,
+        0 <= w <= 0.5.  Returns (nseg, 2 nf + 1) float64 device: E = sum x^2, then A_i = sum x[n]^2 cos(2 pi w_i n) and
+        B_i = sum x[n]^2 sin(2 pi w_i n) per frequency, n counted from the row's first sample."""
+        t = self.torch
+        seg_off = np.ascontiguousarray(seg_off, dtype=np.int64)
+        seg_len = np.ascontiguousarray(seg_len, dtype=np.int64)
+        nseg = int(seg_off.size)
+        w = np.ascontiguousarray(w, dtype=np.float64)
+        if w.ndim != 2 or w.shape[0] != nseg or seg_len.size != nseg:
+            raise ValueError("seg_off, seg_len must be (nseg,) and w (nseg, nf)")
+        nf = int(w.shape[1])
+        if not np.all((w >= 0.0) & (w <= 0.5)):
+            raise ValueError("modulation frequencies must lie in 0 .. 0.5 turns per sample")
+        max_len = int(seg_len.max()) if nseg else 0
+        nsc = int(self.lib.ira_mtf_scratch_doubles(nseg, max_len, nf))
+        check(min(nsc, 0), "ira_mtf_scratch_doubles")
+        nrec = 2 * nf + 1
+        scratch = self.empty(nsc, t.float64)
+        out = self.empty(nseg * nrec, t.float64)
+        d_off, d_len, d_w = self.job_tables(seg_off, seg_len, w.reshape(-1))
+        check(self.lib.ira_mtf_sums(_ptr(x_dev), _ptr(d_off), _ptr(d_len), _ptr(d_w), nseg, max_len, nf, _ptr(scratch),
+                                    _ptr(out), self.stream), "ira_mtf_sums")
+        return out[: nseg * nrec].view(nseg, nrec)
+
     # ------------------------------------------------------------------ ISO 3382-1 noise handling (Lundeby)
     def lundeby_rows(self, base_off: np.ndarray, base_len: np.ndarray, chan_of_seg: np.ndarray, blk_size: np.ndarray,
                      nblk: np.ndarray, first_m: np.ndarray) -> Dict[str, object]:

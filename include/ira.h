@@ -33,7 +33,7 @@ extern "C" {
 #define IRA_E_FORMAT (-5)     /* a file is not RIFF/WAVE (host-side ingest entry points only) */
 #define IRA_E_HIP_BASE (-1000)
 
-#define IRA_ABI_VERSION 11  /* bumped whenever an exported signature or a scratch-size constant changes */
+#define IRA_ABI_VERSION 12  /* bumped whenever an exported signature or a scratch-size constant changes */
 
 int32_t ira_abi_version(void);
 const char* ira_error_string(int32_t code);
@@ -627,6 +627,26 @@ int32_t ira_edc_truncated(const float* x_dev, const int64_t* base_off_dev, const
                           const int32_t* nblk_dev, const int64_t* blk_off_dev, int32_t nseg, int32_t max_chunks,
                           const double* rec_dev, const int64_t* len_dev, const double* suffix_dev, double eps,
                           double floor_db, float* edc_dev, const int64_t* edc_off_dev, void* stream);
+
+/* ---- IEC 60268-16 speech transmission index: modulation transfer sums of the squared response -----------------------
+ * Nothing in the reference computes a modulation transfer function or an STI; both entry points replace nothing in the
+ * reference.  Host side, with the definitions pinned: audio_analysis_amd/analyse/sti.py (`python -m analyse.sti`).
+ * ira_mtf_sums: row j is len_dev[j] samples at x_dev + off_dev[j]; with e[n] = float64(x[n])^2 and the row's nf
+ *   (1..IRA_MTF_MAX_FREQS) modulation frequencies w_dev[j * nf + i] in turns per sample, 0 <= w <= 0.5 (per row: rows
+ *   of different sample rates share a launch), out_dev[j * (2 nf + 1) + ...] holds
+ *     E = sum e[n], then per frequency A_i = sum e[n] cos(2 pi frac(w_i n)), B_i = sum e[n] sin(2 pi frac(w_i n)),
+ *   n counted from the row's first sample.  w n is reduced to a fraction of a turn (its low part recovered by an FMA)
+ *   before any trigonometric evaluation, and every sample's phasor is the product of three directly evaluated unit
+ *   phasors: no recurrence grows with the row.  Float64 sums in an order that depends on the row's length alone
+ *   (bit-identical whatever the batch, the row's place in it or its alignment), one record per chunk of IRA_MTF_CHUNK
+ *   samples folded in a fixed order; no atomics.  max_len >= every len (<= 2^31); nseg <= 65535; scratch_dev holds as
+ *   many doubles as the size call returns (IRA_E_SIZE, negative, for arguments out of range; the size call is host
+ *   only).  Argument errors are reported before anything is launched. */
+#define IRA_MTF_MAX_FREQS 16
+#define IRA_MTF_CHUNK 16384
+int64_t ira_mtf_scratch_doubles(int32_t nseg, int64_t max_len, int32_t nf);
+int32_t ira_mtf_sums(const float* x_dev, const int64_t* off_dev, const int64_t* len_dev, const double* w_dev, int32_t nseg,
+                     int64_t max_len, int32_t nf, double* scratch_dev, double* out_dev, void* stream);
 
 #ifdef __cplusplus
 }
