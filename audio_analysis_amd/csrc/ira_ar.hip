@@ -1258,6 +1258,7 @@ __global__ __launch_bounds__(SV_THREADS) void ar_minnorm_kernel(const double* __
 // ------------------------------------------------------------------------------------------------------------
 constexpr int RT_MAX_DEG = 1024;
 constexpr int RT_MAX_ITERS = 200;
+constexpr double RT_ZERO_TOL = 2.0 * 1.1102230246251565e-16;   // 2 u, u = 2^-53
 
 struct cdbl { double re, im; };
 __device__ __forceinline__ cdbl c_mul(cdbl a, cdbl b) { return {a.re * b.re - a.im * b.im, a.re * b.im + a.im * b.re}; }
@@ -1326,21 +1327,47 @@ __global__ void poly_roots_kernel(const double* __restrict__ coeffs, int stride,
         const bool live = k0 < n;
         const int k = live ? k0 : n - 1;
         const cdbl zk = z[cur][k];
-        // Horner for p and p'
-        cdbl pv = {1.0, 0.0}, dv = {0.0, 0.0};
+        // Newton ratio p / p' and "p(zk) != 0".  The lanes of a group share zk: every branch here is uniform across them.
+        // p counts as zero, and the iterate stays where it is, once |p| is within RT_ZERO_TOL (two units roundoff) of
+        // sv = sum_k |c_k| |zk|^(n-k): Horner's own rounding error is of that size, a correction computed from such a p is noise.
+        // At an m-fold root every sweep is noise once the iterates are within u^(1/m) of it; this test is what ends them there.
+        // Outside the unit circle |zk|^n overflows long before the iterate is unreasonable (|zk| > 2 at n = 1024), and one NaN
+        // iterate enters every other root's pair sum.  There, with y = 1 / zk and q(y) = 1 + c_1 y + ... + c_n y^n,
+        // p(z) = z^n q(y) and p / p' = 1 / (y (n - y q'(y) / q(y))), every power at most 1 in modulus: the same Horner
+        // recurrence on the coefficients in reverse order at y (one loop for both, so that a wave with iterates on both
+        // sides of the circle does not run two).
+        const bool outside = zk.re * zk.re + zk.im * zk.im > 1.0;
+        const cdbl x = outside ? c_div(cdbl{1.0, 0.0}, zk) : zk;
+        const double ax = sqrt(x.re * x.re + x.im * x.im);
+        const int step = outside ? -1 : 1;
+        int idx = outside ? n : 0;
+        cdbl pv = {c[idx], 0.0}, dv = {0.0, 0.0};           // p and p' at zk, or q and q' at y
+        double sv = fabs(c[idx]);
         for (int m = 1; m <= n; ++m) {
-          dv = c_mul(dv, zk); dv.re += pv.re; dv.im += pv.im;
-          pv = c_mul(pv, zk); pv.re += c[m];
+          idx += step;
+          const double cm = c[idx];
+          dv = c_mul(dv, x); dv.re += pv.re; dv.im += pv.im;
+          pv = c_mul(pv, x); pv.re += cm;
+          sv = sv * ax + fabs(cm);
+        }
+        const bool nonzero = fabs(pv.re) + fabs(pv.im) > RT_ZERO_TOL * sv;
+        cdbl ratio;
+        if (outside) {
+          const cdbl t = c_mul(x, c_div(dv, pv));
+          ratio = c_div(cdbl{1.0, 0.0}, c_mul(x, cdbl{(double)n - t.re, -t.im}));
+        } else {
+          ratio = c_div(pv, dv);
         }
         cdbl w = {0.0, 0.0};
-        if (pv.re != 0.0 || pv.im != 0.0) {
-          const cdbl ratio = c_div(pv, dv);
+        if (nonzero) {
           cdbl sum = {0.0, 0.0};
           for (int j = part; j < n; j += LPR) {
             if (j == k) continue;
             const cdbl zj = z[cur][j];
             const double dr = zk.re - zj.re, di = zk.im - zj.im;
-            const double inv = 1.0 / (dr * dr + di * di);   // 1/(zk - zj) = conj(d)/|d|^2
+            const double d2 = dr * dr + di * di;
+            // 1/(zk - zj) = conj(d)/|d|^2; coincident iterates (a multiple root) add nothing instead of 0 * inf
+            const double inv = d2 != 0.0 ? 1.0 / d2 : 0.0;
             sum.re += dr * inv; sum.im -= di * inv;
           }
           if (LPR > 1) {
