@@ -30,20 +30,18 @@ Command line (no plots): python -m analyse.energy --input A.wav [B.wav ...] | --
 from __future__ import annotations
 
 import argparse
-import json
 import math
-import sys
 from dataclasses import dataclass, field
 from pathlib import Path
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from ..engine import get_engine
-from ._common import wav_channels
-from .frequency_response import rfft_bin_step
+from . import _measure as M
+from ._common import band_row_offsets
+from ._measure import BAND_MODES, MAX_BATCH_CHANNELS  # noqa: F401  (both are part of this module's surface)
 from .io import DEFAULT_EXPECTED_SAMPLE_RATE_HZ
-from .rt60bands import BandDefinition, Rt60BandsAnalysisSettings, _build_band_definitions, band_mask_record
+from .rt60bands import BandDefinition, Rt60BandsAnalysisSettings, band_signals_device
 
 STATUS_SILENT = 1
 STATUS_TOO_SHORT = 2
@@ -51,8 +49,6 @@ STATUS_NON_FINITE = 4
 _STATUS_WORDS = ((STATUS_SILENT, "silent"), (STATUS_TOO_SHORT, "too short"), (STATUS_NON_FINITE, "non-finite"))
 
 MAX_LIMITS = 4
-MAX_BATCH_CHANNELS = 256          # channels per device batch (the CLI's chunk)
-BAND_MODES = ("three", "octave", "third")
 
 
 @dataclass(frozen=True)
@@ -132,50 +128,12 @@ def window_samples(early_limits_ms: Sequence[float], sample_rate_hz: float) -> L
 
 
 def status_text(status: int) -> str:
-    if status == 0:
-        return "ok"
-    return f"{status} (" + ", ".join(w for bit, w in _STATUS_WORDS if status & bit) + ")"
+    return M.status_text(status, _STATUS_WORDS)
 
 
 # ---------------------------------------------------------------------------------------------------
 # device
 # ---------------------------------------------------------------------------------------------------
-
-
-def band_signals_device(eng, batch, sample_rate_hz: int, band_settings: Rt60BandsAnalysisSettings):
-    """The rt60bands filter bank for a device batch, by the engine calls of rt60_bands_device: one forward float64 rFFT of
-    every full file, masked inverse transforms per band.  Returns (bands, y float32 device, y_off (nch, nbands) int64):
-    band b of channel c is batch.length[c] samples at y_off[c, b]."""
-    t = eng.torch
-    nch = batch.count
-    n64 = batch.length.astype(np.int64)
-    if np.any(n64 < 8):
-        raise ValueError("Not enough samples for band analysis.")
-    bands = _build_band_definitions(band_settings, sample_rate_hz)
-    nb = len(bands)
-    if nb == 0:
-        return bands, None, np.zeros((nch, 0), dtype=np.int64)
-    nyq = 0.5 * float(sample_rate_hz)
-    records = np.stack([band_mask_record(b, band_settings.transition_width_octaves, nyq) for b in bands])
-    spec, spec_off = eng.rfft_any(batch.x, batch.off, n64, use_hann=False)
-    per_entry = np.repeat(n64, nb)
-    y_off = (np.cumsum(per_entry) - per_entry).reshape(nch, nb)
-    y = eng.empty(int(per_entry.sum()), t.float32)
-    fv_of = {int(v): rfft_bin_step(int(v), sample_rate_hz) for v in np.unique(n64)}
-    fv = np.array([fv_of[int(v)] for v in n64], dtype=np.float64)
-    eng.band_irfft(spec, np.repeat(np.asarray(spec_off, dtype=np.int64), nb), per_entry.astype(np.int32),
-                   np.tile(records, (nch, 1)), np.repeat(fv, nb), y, y_off.reshape(-1))
-    return bands, y, y_off
-
-
-def _common_base(tensors):
-    """One base pointer for float32 device buffers that one launch reads: the lowest of them, and every buffer's offset
-    from it in elements (the kernels address segments as base + offset in the device's flat address space)."""
-    ptrs = [int(x.data_ptr()) for x in tensors]
-    lo = int(np.argmin(ptrs))
-    if any((p - ptrs[lo]) % 4 for p in ptrs):
-        raise ValueError("float32 buffers of one launch must be 4-byte aligned to each other")
-    return tensors[lo], [(p - ptrs[lo]) // 4 for p in ptrs]
 
 
 def energy_parameters_device(eng, batch, sample_rate_hz: int, settings: Optional[EnergyParameterSettings] = None,
@@ -186,22 +144,16 @@ def energy_parameters_device(eng, batch, sample_rate_hz: int, settings: Optional
     built the band signals skip the filter bank; otherwise settings.bands decides which are built (None: broadband only).
     """
     settings = settings or EnergyParameterSettings()
-    t = eng.torch
     nch = batch.count
     limits = np.asarray(window_samples(settings.early_limits_ms, sample_rate_hz), dtype=np.int64)
     nlim = int(limits.size)
     onset_dev, _, peak_abs_dev = eng.onset_index(batch, settings.rel_energy)
     if band_signals is None and settings.bands is not None:
         band_signals = band_signals_device(eng, batch, sample_rate_hz, settings.bands)
-    bands, y, y_off = band_signals if band_signals is not None else ([], None, np.zeros((nch, 0), dtype=np.int64))
+    bands = band_signals[0] if band_signals is not None else []
     nb = len(bands)
-    y_off = np.asarray(y_off, dtype=np.int64).reshape(nch, nb)
     # segment rows: channel c's broadband signal, then its bands (row c * (1 + nb) + b)
-    if nb:
-        base, (dx, dy) = _common_base([batch.x, y])
-        seg_off = np.concatenate([(batch.off + dx)[:, None], y_off + dy], axis=1).reshape(-1)
-    else:
-        base, seg_off = batch.x, batch.off.copy()
+    base, seg_off = band_row_offsets(batch, band_signals)
     seg_len = np.repeat(batch.length.astype(np.int64), 1 + nb)
     chan = np.repeat(np.arange(nch, dtype=np.int32), 1 + nb)
     if nch:
@@ -280,6 +232,11 @@ def energy_parameters_results(res: EnergySums, sample_rate_hz: int, channel_name
 # ---------------------------------------------------------------------------------------------------
 
 
+def _results_of_batch(eng, batch, sample_rate_hz, names, settings) -> List[EnergyParametersChannelResult]:
+    res = energy_parameters_device(eng, batch, sample_rate_hz, settings)
+    return energy_parameters_results(res, sample_rate_hz, names, settings)
+
+
 def analyse_energy_parameters_batch(
     channels: Sequence[np.ndarray],
     sample_rate_hz: int,
@@ -287,21 +244,8 @@ def analyse_energy_parameters_batch(
     settings: Optional[EnergyParameterSettings] = None,
 ) -> List[EnergyParametersChannelResult]:
     """Every channel through the device in batches of at most MAX_BATCH_CHANNELS channels."""
-    settings = settings or EnergyParameterSettings()
-    if len(channels) != len(channel_names):
-        raise ValueError("one name per channel")
-    eng = get_engine()
-    out: List[EnergyParametersChannelResult] = []
-    for a in range(0, len(channels), MAX_BATCH_CHANNELS):
-        chans = [np.asarray(c, dtype=np.float32).reshape(-1) for c in channels[a : a + MAX_BATCH_CHANNELS]]
-        batch = eng.upload(chans)
-        out += _results_of_batch(eng, batch, sample_rate_hz, channel_names[a : a + MAX_BATCH_CHANNELS], settings)
-    return out
-
-
-def _results_of_batch(eng, batch, sample_rate_hz, names, settings) -> List[EnergyParametersChannelResult]:
-    res = energy_parameters_device(eng, batch, sample_rate_hz, settings)
-    return energy_parameters_results(res, sample_rate_hz, names, settings)
+    return M.analyse_channel_batches(channels, sample_rate_hz, channel_names, settings or EnergyParameterSettings(),
+                                     _results_of_batch)
 
 
 def analyse_energy_parameters_from_wav_file(
@@ -311,10 +255,8 @@ def analyse_energy_parameters_from_wav_file(
 ) -> List[EnergyParametersChannelResult]:
     """One WAV file (mono or stereo, rate checked against expected_sample_rate_hz); channels named as by
     get_analysis_channels ("mono", "left", "right")."""
-    settings = settings or EnergyParameterSettings()
-    loaded, chans = wav_channels(input_wav_file_path, settings.use_mono_downmix_for_stereo,
-                                 expected_sample_rate_hz=expected_sample_rate_hz)
-    return analyse_energy_parameters_batch([c for _, c in chans], loaded.sample_rate_hz, [n for n, _ in chans], settings)
+    return M.analyse_wav_file_channels(input_wav_file_path, settings or EnergyParameterSettings(), expected_sample_rate_hz,
+                                       analyse_energy_parameters_batch)
 
 
 def analyse_energy_parameters_files(
@@ -324,14 +266,8 @@ def analyse_energy_parameters_files(
 ) -> List[EnergyParametersChannelResult]:
     """Every channel of every file in one device batch per MAX_BATCH_CHANNELS channels; channels named
     "<file name>:<channel>"."""
-    settings = settings or EnergyParameterSettings()
-    chans, names = [], []
-    for p in paths:
-        _, cs = wav_channels(p, settings.use_mono_downmix_for_stereo, expected_sample_rate_hz=expected_sample_rate_hz)
-        for n, c in cs:
-            chans.append(c)
-            names.append(f"{Path(p).name}:{n}")
-    return analyse_energy_parameters_batch(chans, int(expected_sample_rate_hz), names, settings)
+    return M.analyse_file_channels(paths, settings or EnergyParameterSettings(), expected_sample_rate_hz,
+                                   analyse_energy_parameters_batch)
 
 
 def analyse_energy_parameters_bundle(
@@ -341,21 +277,8 @@ def analyse_energy_parameters_bundle(
 ) -> List[EnergyParametersChannelResult]:
     """The taps a bundle's meta.json lists (taps/<name>.wav), read by the native ingest (ingest.TapSet) a group at a
     time (at most MAX_BATCH_CHANNELS channels per group); channels named "<tap>:<channel>"."""
-    from ..ingest import TapSet
-
-    settings = settings or EnergyParameterSettings()
-    root = Path(bundle_root)
-    taps: List[str] = list(json.loads((root / "meta.json").read_text()).get("taps", []))
-    eng = get_engine()
-    out: List[EnergyParametersChannelResult] = []
-    step = MAX_BATCH_CHANNELS // 2                        # a tap has one or two channels
-    for a in range(0, len(taps), step):
-        group = taps[a : a + step]
-        ts = TapSet(eng, [root / "taps" / f"{t}.wav" for t in group], expected_sample_rate_hz)
-        batch, labels = ts.view(settings.use_mono_downmix_for_stereo)
-        names = [f"{group[i]}:{ch}" for i, ch in labels]
-        out += _results_of_batch(eng, batch, int(expected_sample_rate_hz), names, settings)
-    return out
+    return M.analyse_bundle_channels(bundle_root, settings or EnergyParameterSettings(), expected_sample_rate_hz,
+                                     _results_of_batch)
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -363,24 +286,16 @@ def analyse_energy_parameters_bundle(
 # ---------------------------------------------------------------------------------------------------
 
 
-def _fmt(v: float, digits: int) -> str:
-    if math.isnan(v):
-        return "NA"
-    if math.isinf(v):
-        return "+inf" if v > 0 else "-inf"
-    return f"{v:.{digits}f}"
-
-
 def _columns(r: EnergyParametersChannelResult) -> List[str]:
     return [f"C{v:g}_dB" for v in r.early_limits_ms] + [f"D{r.definition_limit_ms:g}", "Ts_ms"]
 
 
 def _cells(p: EnergyParameters) -> List[str]:
-    return [_fmt(v, 2) for v in p.clarity_db] + [_fmt(p.definition, 3), _fmt(1000.0 * p.centre_time_seconds, 2)]
+    return [M.fmt(v, 2) for v in p.clarity_db] + [M.fmt(p.definition, 3), M.fmt(1000.0 * p.centre_time_seconds, 2)]
 
 
-def _rows(r: EnergyParametersChannelResult) -> List[Tuple[str, EnergyParameters]]:
-    return [("Broadband", r.broadband)] + [(b.name, r.band_parameters_by_name[b.name]) for b in r.band_definitions]
+def _rows(r: EnergyParametersChannelResult) -> List[List[str]]:
+    return [[name] + _cells(p) for name, p in M.band_rows(r, r.band_parameters_by_name)]
 
 
 def summarise_energy_parameters_text(channel_results: List[EnergyParametersChannelResult]) -> str:
@@ -393,55 +308,28 @@ def summarise_energy_parameters_text(channel_results: List[EnergyParametersChann
         <band name>  ...                       (one row per band, ascending)
     Cells are separated by two spaces; NaN is "NA", an infinite clarity "+inf" / "-inf".
     """
-    lines: List[str] = []
-    for r in channel_results:
-        lines.append(f"[{r.channel_name}]")
-        lines.append(f"Onset: {r.onset_samples} samples ({1000.0 * r.onset_seconds:.3f} ms)  Status: {status_text(r.status)}")
-        lines.append("  ".join(["Band"] + _columns(r)))
-        for name, p in _rows(r):
-            lines.append("  ".join([name] + _cells(p)))
-        lines.append("")
-    return "\n".join(lines) + ("\n" if lines else "")
+    return M.join_blocks(M.text_block(
+        r.channel_name, f"Onset: {r.onset_samples} samples ({1000.0 * r.onset_seconds:.3f} ms)  Status: {status_text(r.status)}",
+        _columns(r), _rows(r)) for r in channel_results)
 
 
 def summarise_energy_parameters_markdown(channel_results: List[EnergyParametersChannelResult]) -> str:
     """The same values as a Markdown section per channel: a '### <channel name>' heading, an onset / status line and a
     table with a column per parameter (C in dB, D, Ts in ms), rows Broadband then the bands."""
-    lines: List[str] = []
-    for r in channel_results:
-        cols = [f"C{v:g} (dB)" for v in r.early_limits_ms] + [f"D{r.definition_limit_ms:g}", "Ts (ms)"]
-        lines.append(f"### {r.channel_name}")
-        lines.append("")
-        lines.append(f"Onset: {r.onset_samples} samples ({1000.0 * r.onset_seconds:.3f} ms). Status: {status_text(r.status)}.")
-        lines.append("")
-        lines.append("| Band | " + " | ".join(cols) + " |")
-        lines.append("|---|" + "---:|" * len(cols))
-        for name, p in _rows(r):
-            lines.append("| " + " | ".join([name] + _cells(p)) + " |")
-        lines.append("")
-    return "\n".join(lines) + ("\n" if lines else "")
-
-
-def _json_num(v: float):
-    if math.isnan(v):
-        return None
-    if math.isinf(v):
-        return "+inf" if v > 0 else "-inf"
-    return float(v)
-
-
-def _num_json(v) -> float:
-    return float("nan") if v is None else float(v)          # float("+inf") parses the infinite clarity
+    return M.join_blocks(M.markdown_block(
+        r.channel_name, f"Onset: {r.onset_samples} samples ({1000.0 * r.onset_seconds:.3f} ms). Status: {status_text(r.status)}.",
+        [f"C{v:g} (dB)" for v in r.early_limits_ms] + [f"D{r.definition_limit_ms:g}", "Ts (ms)"], _rows(r))
+        for r in channel_results)
 
 
 def _params_json(p: EnergyParameters) -> Dict:
-    return {"clarity_db": [_json_num(v) for v in p.clarity_db], "definition": _json_num(p.definition),
-            "centre_time_seconds": _json_num(p.centre_time_seconds)}
+    return {"clarity_db": [M.json_num(v) for v in p.clarity_db], "definition": M.json_num(p.definition),
+            "centre_time_seconds": M.json_num(p.centre_time_seconds)}
 
 
 def _params_from_json(d: Dict) -> EnergyParameters:
-    return EnergyParameters(tuple(_num_json(v) for v in d["clarity_db"]), _num_json(d["definition"]),
-                            _num_json(d["centre_time_seconds"]))
+    return EnergyParameters(tuple(M.num_json(v) for v in d["clarity_db"]), M.num_json(d["definition"]),
+                            M.num_json(d["centre_time_seconds"]))
 
 
 def energy_results_to_json(channel_results: List[EnergyParametersChannelResult]) -> Dict:
@@ -452,9 +340,7 @@ def energy_results_to_json(channel_results: List[EnergyParametersChannelResult])
             "channel_name": r.channel_name, "sample_rate_hz": r.sample_rate_hz, "early_limits_ms": list(r.early_limits_ms),
             "definition_limit_ms": r.definition_limit_ms, "onset_samples": r.onset_samples,
             "onset_seconds": r.onset_seconds, "status": r.status, "broadband": _params_json(r.broadband),
-            "bands": [dict(name=b.name, centre_hz=b.centre_hz, kind=b.kind, low_edge_hz=b.low_edge_hz,
-                           high_edge_hz=b.high_edge_hz, **_params_json(r.band_parameters_by_name[b.name]))
-                      for b in r.band_definitions],
+            "bands": [M.band_to_json(b, _params_json(r.band_parameters_by_name[b.name])) for b in r.band_definitions],
         })
     return {"energy_parameters": rows}
 
@@ -462,14 +348,13 @@ def energy_results_to_json(channel_results: List[EnergyParametersChannelResult])
 def energy_results_from_json(doc: Dict) -> List[EnergyParametersChannelResult]:
     out = []
     for d in doc["energy_parameters"]:
-        bands = [BandDefinition(b["name"], b["centre_hz"], b["kind"], b["low_edge_hz"], b["high_edge_hz"])
-                 for b in d["bands"]]
         out.append(EnergyParametersChannelResult(
             channel_name=d["channel_name"], sample_rate_hz=int(d["sample_rate_hz"]),
             early_limits_ms=tuple(float(v) for v in d["early_limits_ms"]),
             definition_limit_ms=float(d["definition_limit_ms"]), onset_samples=int(d["onset_samples"]),
             onset_seconds=float(d["onset_seconds"]), status=int(d["status"]), broadband=_params_from_json(d["broadband"]),
-            band_definitions=bands, band_parameters_by_name={b["name"]: _params_from_json(b) for b in d["bands"]}))
+            band_definitions=M.bands_from_json(d["bands"]),
+            band_parameters_by_name={b["name"]: _params_from_json(b) for b in d["bands"]}))
     return out
 
 
@@ -482,18 +367,13 @@ def build_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(
         prog="python -m analyse.energy",
         description="ISO 3382-1 clarity (C), definition (D) and centre time (Ts) per channel and band.")
-    src = p.add_mutually_exclusive_group(required=True)
-    src.add_argument("--input", nargs="+", type=Path, help="WAV files (every channel of every file is analysed)")
-    src.add_argument("--bundle", type=Path, help="bundle directory: meta.json + taps/<name>.wav")
-    p.add_argument("--mono", action="store_true", help="analyse stereo files as their mono downmix 0.5 * (L + R)")
-    p.add_argument("--bands", choices=["none", *BAND_MODES], default="octave", help="filter bank (default: octave)")
+    M.add_source_arguments(p)
+    M.add_bands_argument(p)
     p.add_argument("--onset-db", type=float, default=-20.0,
                    help="onset: first sample within this level of the peak (default: -20 dB, ISO 3382-1)")
     p.add_argument("--limits-ms", nargs="+", type=float, default=[50.0, 80.0],
                    help="early/late limits in ms, 1 to 4, ascending (default: 50 80)")
-    p.add_argument("--expected-sample-rate", type=int, default=DEFAULT_EXPECTED_SAMPLE_RATE_HZ,
-                   help="every file must have this sample rate (default: 48000)")
-    p.add_argument("--json", type=Path, default=None, help="also write the results as JSON to this file")
+    M.add_output_arguments(p)
     return p
 
 
@@ -504,20 +384,8 @@ def settings_from_args(args) -> EnergyParameterSettings:
 
 
 def main(argv: Optional[Sequence[str]] = None) -> None:
-    parser = build_parser()
-    args = parser.parse_args(argv)
-    try:
-        settings = settings_from_args(args)
-    except ValueError as e:
-        parser.error(str(e))
-    if args.input:
-        results = analyse_energy_parameters_files(args.input, settings, args.expected_sample_rate)
-    else:
-        results = analyse_energy_parameters_bundle(args.bundle, settings, args.expected_sample_rate)
-    sys.stdout.write(summarise_energy_parameters_text(results))
-    sys.stdout.flush()
-    if args.json is not None:
-        args.json.write_text(json.dumps(energy_results_to_json(results), indent=2) + "\n")
+    M.run_cli(build_parser(), argv, settings_from_args, analyse_energy_parameters_files, analyse_energy_parameters_bundle,
+              summarise_energy_parameters_text, energy_results_to_json)
 
 
 if __name__ == "__main__":

@@ -24,7 +24,7 @@ product and sum is float64 on the exact float32 samples.
            flag is set.
   IACC_E3  the mean of the early IACC at the first limit over the 500 Hz, 1000 Hz and 2000 Hz bands; reported only when the
            bank is the octave bank, otherwise NaN.
-  bands    the rt60bands filter bank through energy.band_signals_device: none, three, octave (default) or third.  Each
+  bands    the rt60bands filter bank (rt60bands.band_signals_device): none, three, octave (default) or third.  Each
            channel of the pair is filtered separately, with the same zero-phase circular filter as everywhere else.
 
 Per-pair status (bit flags; when any is set every output is NaN, the batch carries on):
@@ -38,9 +38,7 @@ Command line (no plots): python -m analyse.iacc --input A.wav [B.wav ...] | --bu
 from __future__ import annotations
 
 import argparse
-import json
 import math
-import sys
 from dataclasses import dataclass, field
 from pathlib import Path
 from typing import Dict, List, Optional, Sequence, Tuple
@@ -48,10 +46,12 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 from ..engine import get_engine
-from ._common import wav_channels
-from .energy import BAND_MODES, MAX_BATCH_CHANNELS, MAX_LIMITS, _common_base, band_signals_device, window_samples
+from . import _measure as M
+from ._common import band_row_offsets
+from ._measure import BAND_MODES
+from .energy import MAX_LIMITS, window_samples
 from .io import DEFAULT_EXPECTED_SAMPLE_RATE_HZ
-from .rt60bands import BandDefinition, Rt60BandsAnalysisSettings, _build_band_definitions
+from .rt60bands import BandDefinition, Rt60BandsAnalysisSettings, _build_band_definitions, band_signals_device
 
 STATUS_SILENT = 1
 STATUS_TOO_SHORT = 2
@@ -153,9 +153,7 @@ def max_lag_samples(max_lag_ms: float, sample_rate_hz: float) -> int:
 
 
 def status_text(status: int) -> str:
-    if status == 0:
-        return "ok"
-    return f"{status} (" + ", ".join(w for bit, w in _STATUS_WORDS if status & bit) + ")"
+    return M.status_text(status, _STATUS_WORDS)
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -168,7 +166,7 @@ def iacc_device(eng, batch, pairs: Sequence[Tuple[int, int]], sample_rate_hz: in
     """
     Onsets and partitioned lag sums of every (left, right) pair of channel indices of a device batch, broadband and per
     band, in ONE ira_xcorr_windows launch.  band_signals = (bands, y device, y_off (nch, nbands)) as
-    energy.band_signals_device returns them lets a caller that already built the band signals skip the filter bank;
+    band_signals_device returns them lets a caller that already built the band signals skip the filter bank;
     otherwise settings.bands decides which are built (None: broadband only).
     """
     settings = settings or IaccSettings()
@@ -190,16 +188,11 @@ def iacc_device(eng, batch, pairs: Sequence[Tuple[int, int]], sample_rate_hz: in
     onset_dev, _, peak_abs_dev = eng.onset_index(batch, settings.rel_energy)
     if band_signals is None and settings.bands is not None:
         band_signals = band_signals_device(eng, batch, sample_rate_hz, settings.bands)
-    bands, y, y_off = band_signals if band_signals is not None else ([], None, np.zeros((nch, 0), dtype=np.int64))
+    bands = band_signals[0] if band_signals is not None else []
     nb = len(bands)
-    y_off = np.asarray(y_off, dtype=np.int64).reshape(nch, nb)
     # segment rows: pair p's broadband signals, then its bands (row p * (1 + nb) + b)
-    if nb:
-        base, (dx, dy) = _common_base([batch.x, y])
-        l_off = np.concatenate([(batch.off[left] + dx)[:, None], y_off[left] + dy], axis=1).reshape(-1)
-        r_off = np.concatenate([(batch.off[right] + dx)[:, None], y_off[right] + dy], axis=1).reshape(-1)
-    else:
-        base, l_off, r_off = batch.x, batch.off[left].copy(), batch.off[right].copy()
+    base, l_off = band_row_offsets(batch, band_signals, channels=left)
+    _, r_off = band_row_offsets(batch, band_signals, channels=right)
     if npairs:
         out = eng.xcorr_windows(base, l_off, r_off, np.repeat(n64[left], 1 + nb), np.repeat(left.astype(np.int32), 1 + nb),
                                 np.repeat(right.astype(np.int32), 1 + nb), onset_dev, np.tile(limits, (l_off.size, 1)), tmax)
@@ -324,28 +317,26 @@ def iacc_results(res: IaccSums, sample_rate_hz: int, pair_names: Sequence[str], 
 # ---------------------------------------------------------------------------------------------------
 
 
+def _results_of_pairs(eng, batch, pairs, sample_rate_hz, names, settings) -> List[IaccPairResult]:
+    res = iacc_device(eng, batch, pairs, sample_rate_hz, settings)
+    return iacc_results(res, sample_rate_hz, names, settings)
+
+
+def _results_of_batch(eng, batch, sample_rate_hz, names, settings) -> List[IaccPairResult]:
+    """A batch of interleaved pairs (channels 2 i and 2 i + 1), every channel named by its pair."""
+    pairs = [(2 * i, 2 * i + 1) for i in range(batch.count // 2)]
+    return _results_of_pairs(eng, batch, pairs, sample_rate_hz, names[::2], settings)
+
+
 def analyse_iacc_pairs_batch(lefts: Sequence[np.ndarray], rights: Sequence[np.ndarray], sample_rate_hz: int,
                              names: Sequence[str], settings: Optional[IaccSettings] = None) -> List[IaccPairResult]:
     """Every (left, right) pair through the device in batches of at most MAX_BATCH_CHANNELS channels."""
-    settings = settings or IaccSettings()
     if not len(lefts) == len(rights) == len(names):
         raise ValueError("one right channel and one name per left channel")
-    eng = get_engine()
-    out: List[IaccPairResult] = []
-    step = MAX_BATCH_CHANNELS // 2
-    for a in range(0, len(lefts), step):
-        chans = []
-        for l, r in zip(lefts[a : a + step], rights[a : a + step]):
-            chans += [np.asarray(l, dtype=np.float32).reshape(-1), np.asarray(r, dtype=np.float32).reshape(-1)]
-        batch = eng.upload(chans)
-        pairs = [(2 * i, 2 * i + 1) for i in range(len(chans) // 2)]
-        out += _results_of_batch(eng, batch, pairs, sample_rate_hz, names[a : a + step], settings)
-    return out
-
-
-def _results_of_batch(eng, batch, pairs, sample_rate_hz, names, settings) -> List[IaccPairResult]:
-    res = iacc_device(eng, batch, pairs, sample_rate_hz, settings)
-    return iacc_results(res, sample_rate_hz, names, settings)
+    # left, right, left, ...: MAX_BATCH_CHANNELS is even, so a batch never splits a pair
+    chans = [c for pair in zip(lefts, rights) for c in pair]
+    return M.analyse_channel_batches(chans, sample_rate_hz, [n for n in names for _ in range(2)], settings or IaccSettings(),
+                                     _results_of_batch)
 
 
 def _merge(names: Sequence[str], stereo: Sequence[bool], pair_results: List[IaccPairResult], sample_rate_hz: int,
@@ -369,12 +360,12 @@ def analyse_iacc_files(paths: Sequence[str | Path], settings: Optional[IaccSetti
     settings = settings or IaccSettings()
     names, stereo, lefts, rights = [], [], [], []
     for p in paths:
-        _, cs = wav_channels(p, False, expected_sample_rate_hz=expected_sample_rate_hz)
+        cs = [c for _, c in M.file_channels([p], False, expected_sample_rate_hz)]
         names.append(Path(p).name)
         stereo.append(len(cs) == 2)
         if len(cs) == 2:
-            lefts.append(cs[0][1])
-            rights.append(cs[1][1])
+            lefts.append(cs[0])
+            rights.append(cs[1])
     fs = int(expected_sample_rate_hz)
     res = analyse_iacc_pairs_batch(lefts, rights, fs, [n for n, s in zip(names, stereo) if s], settings)
     return _merge(names, stereo, res, fs, settings)
@@ -384,25 +375,17 @@ def analyse_iacc_bundle(bundle_root: str | Path, settings: Optional[IaccSettings
                         expected_sample_rate_hz: int = DEFAULT_EXPECTED_SAMPLE_RATE_HZ) -> List[IaccPairResult]:
     """The taps a bundle's meta.json lists (taps/<name>.wav), read by the native ingest (ingest.TapSet) a group at a time
     (at most MAX_BATCH_CHANNELS channels per group); one result per tap, named by the tap; a mono tap gets status 8."""
-    from ..ingest import TapSet
-
     settings = settings or IaccSettings()
-    root = Path(bundle_root)
-    taps: List[str] = list(json.loads((root / "meta.json").read_text()).get("taps", []))
     fs = int(expected_sample_rate_hz)
-    eng = get_engine()
     out: List[IaccPairResult] = []
-    step = MAX_BATCH_CHANNELS // 2                        # a tap has one or two channels
-    for a in range(0, len(taps), step):
-        group = taps[a : a + step]
-        ts = TapSet(eng, [root / "taps" / f"{t}.wav" for t in group], expected_sample_rate_hz)
-        batch, labels = ts.view(False)
+    for group, batch, labels in M.bundle_groups(bundle_root, False, expected_sample_rate_hz):
         where: Dict[int, Dict[str, int]] = {}
         for k, (i, ch) in enumerate(labels):
             where.setdefault(i, {})[ch] = k
         stereo = [("left" in where.get(i, {}) and "right" in where.get(i, {})) for i in range(len(group))]
         pairs = [(where[i]["left"], where[i]["right"]) for i in range(len(group)) if stereo[i]]
-        res = _results_of_batch(eng, batch, pairs, fs, [g for g, s in zip(group, stereo) if s], settings) if pairs else []
+        names = [g for g, s in zip(group, stereo) if s]
+        res = _results_of_pairs(get_engine(), batch, pairs, fs, names, settings) if pairs else []
         out += _merge(group, stereo, res, fs, settings)
     return out
 
@@ -410,10 +393,6 @@ def analyse_iacc_bundle(bundle_root: str | Path, settings: Optional[IaccSettings
 # ---------------------------------------------------------------------------------------------------
 # text, Markdown, JSON
 # ---------------------------------------------------------------------------------------------------
-
-
-def _fmt(v: float, digits: int = 3) -> str:
-    return "NA" if math.isnan(v) else f"{v:.{digits}f}"
 
 
 def _columns(r: IaccPairResult, markdown: bool = False) -> List[str]:
@@ -429,12 +408,12 @@ def _cells(v: IaccValues) -> List[str]:
     cells: List[str] = []
     for coeff, tau in ((v.early, v.tau_early_seconds), (v.late, v.tau_late_seconds)):
         for c, t in zip(coeff, tau):
-            cells += [_fmt(c), _fmt(1000.0 * t)]
-    return cells + [_fmt(v.whole), _fmt(1000.0 * v.tau_whole_seconds)]
+            cells += [M.fmt(c), M.fmt(1000.0 * t)]
+    return cells + [M.fmt(v.whole), M.fmt(1000.0 * v.tau_whole_seconds)]
 
 
-def _rows(r: IaccPairResult) -> List[Tuple[str, IaccValues]]:
-    return [("Broadband", r.broadband)] + [(b.name, r.band_values_by_name[b.name]) for b in r.band_definitions]
+def _rows(r: IaccPairResult) -> List[List[str]]:
+    return [[name] + _cells(v) for name, v in M.band_rows(r, r.band_values_by_name)]
 
 
 def summarise_iacc_text(pair_results: List[IaccPairResult]) -> str:
@@ -449,59 +428,32 @@ def summarise_iacc_text(pair_results: List[IaccPairResult]) -> str:
     The early columns of every limit come first, then the late ones, then the whole response.  Cells are separated by two
     spaces; NaN is "NA".
     """
-    lines: List[str] = []
-    for r in pair_results:
-        lines.append(f"[{r.pair_name}]")
-        lines.append(f"Onset: {r.onset_samples} samples ({1000.0 * r.onset_seconds:.3f} ms)  "
-                     f"Max lag: {r.max_lag_samples} samples  Status: {status_text(r.status)}")
-        lines.append("  ".join(["Band"] + _columns(r)))
-        for name, v in _rows(r):
-            lines.append("  ".join([name] + _cells(v)))
-        lines.append(f"IACC_E3: {_fmt(r.iacc_e3)}")
-        lines.append("")
-    return "\n".join(lines) + ("\n" if lines else "")
+    return M.join_blocks(M.text_block(
+        r.pair_name, f"Onset: {r.onset_samples} samples ({1000.0 * r.onset_seconds:.3f} ms)  "
+                     f"Max lag: {r.max_lag_samples} samples  Status: {status_text(r.status)}",
+        _columns(r), _rows(r), tail=[f"IACC_E3: {M.fmt(r.iacc_e3)}"]) for r in pair_results)
 
 
 def summarise_iacc_markdown(pair_results: List[IaccPairResult]) -> str:
     """The same values as a Markdown section per pair: a '### <pair name>' heading, an onset / lag / status line, a table
     with two columns per coefficient (IACC, tau in ms), rows Broadband then the bands, and an IACC_E3 line."""
-    lines: List[str] = []
-    for r in pair_results:
-        cols = _columns(r, markdown=True)
-        lines.append(f"### {r.pair_name}")
-        lines.append("")
-        lines.append(f"Onset: {r.onset_samples} samples ({1000.0 * r.onset_seconds:.3f} ms). "
-                     f"Max lag: {r.max_lag_samples} samples. Status: {status_text(r.status)}.")
-        lines.append("")
-        lines.append("| Band | " + " | ".join(cols) + " |")
-        lines.append("|---|" + "---:|" * len(cols))
-        for name, v in _rows(r):
-            lines.append("| " + " | ".join([name] + _cells(v)) + " |")
-        lines.append("")
-        lines.append(f"IACC_E3: {_fmt(r.iacc_e3)}")
-        lines.append("")
-    return "\n".join(lines) + ("\n" if lines else "")
-
-
-def _json_num(v: float):
-    return None if math.isnan(v) else float(v)
-
-
-def _num_json(v) -> float:
-    return float("nan") if v is None else float(v)
+    return M.join_blocks(M.markdown_block(
+        r.pair_name, f"Onset: {r.onset_samples} samples ({1000.0 * r.onset_seconds:.3f} ms). "
+                     f"Max lag: {r.max_lag_samples} samples. Status: {status_text(r.status)}.",
+        _columns(r, markdown=True), _rows(r), tail=[f"IACC_E3: {M.fmt(r.iacc_e3)}"]) for r in pair_results)
 
 
 def _values_json(v: IaccValues) -> Dict:
-    return {"early": [_json_num(x) for x in v.early], "late": [_json_num(x) for x in v.late], "whole": _json_num(v.whole),
-            "tau_early_seconds": [_json_num(x) for x in v.tau_early_seconds],
-            "tau_late_seconds": [_json_num(x) for x in v.tau_late_seconds],
-            "tau_whole_seconds": _json_num(v.tau_whole_seconds)}
+    return {"early": [M.json_num(x) for x in v.early], "late": [M.json_num(x) for x in v.late], "whole": M.json_num(v.whole),
+            "tau_early_seconds": [M.json_num(x) for x in v.tau_early_seconds],
+            "tau_late_seconds": [M.json_num(x) for x in v.tau_late_seconds],
+            "tau_whole_seconds": M.json_num(v.tau_whole_seconds)}
 
 
 def _values_from_json(d: Dict) -> IaccValues:
-    return IaccValues(tuple(_num_json(x) for x in d["early"]), tuple(_num_json(x) for x in d["late"]), _num_json(d["whole"]),
-                      tuple(_num_json(x) for x in d["tau_early_seconds"]), tuple(_num_json(x) for x in d["tau_late_seconds"]),
-                      _num_json(d["tau_whole_seconds"]))
+    return IaccValues(tuple(M.num_json(x) for x in d["early"]), tuple(M.num_json(x) for x in d["late"]), M.num_json(d["whole"]),
+                      tuple(M.num_json(x) for x in d["tau_early_seconds"]), tuple(M.num_json(x) for x in d["tau_late_seconds"]),
+                      M.num_json(d["tau_whole_seconds"]))
 
 
 def iacc_results_to_json(pair_results: List[IaccPairResult]) -> Dict:
@@ -511,10 +463,8 @@ def iacc_results_to_json(pair_results: List[IaccPairResult]) -> Dict:
         rows.append({
             "pair_name": r.pair_name, "sample_rate_hz": r.sample_rate_hz, "early_limits_ms": list(r.early_limits_ms),
             "max_lag_samples": r.max_lag_samples, "onset_samples": r.onset_samples, "onset_seconds": r.onset_seconds,
-            "status": r.status, "iacc_e3": _json_num(r.iacc_e3), "broadband": _values_json(r.broadband),
-            "bands": [dict(name=b.name, centre_hz=b.centre_hz, kind=b.kind, low_edge_hz=b.low_edge_hz,
-                           high_edge_hz=b.high_edge_hz, **_values_json(r.band_values_by_name[b.name]))
-                      for b in r.band_definitions],
+            "status": r.status, "iacc_e3": M.json_num(r.iacc_e3), "broadband": _values_json(r.broadband),
+            "bands": [M.band_to_json(b, _values_json(r.band_values_by_name[b.name])) for b in r.band_definitions],
         })
     return {"iacc": rows}
 
@@ -522,14 +472,12 @@ def iacc_results_to_json(pair_results: List[IaccPairResult]) -> Dict:
 def iacc_results_from_json(doc: Dict) -> List[IaccPairResult]:
     out = []
     for d in doc["iacc"]:
-        bands = [BandDefinition(b["name"], b["centre_hz"], b["kind"], b["low_edge_hz"], b["high_edge_hz"])
-                 for b in d["bands"]]
         out.append(IaccPairResult(
             pair_name=d["pair_name"], sample_rate_hz=int(d["sample_rate_hz"]),
             early_limits_ms=tuple(float(v) for v in d["early_limits_ms"]), max_lag_samples=int(d["max_lag_samples"]),
             onset_samples=int(d["onset_samples"]), onset_seconds=float(d["onset_seconds"]), status=int(d["status"]),
-            broadband=_values_from_json(d["broadband"]), band_definitions=bands,
-            band_values_by_name={b["name"]: _values_from_json(b) for b in d["bands"]}, iacc_e3=_num_json(d["iacc_e3"])))
+            broadband=_values_from_json(d["broadband"]), band_definitions=M.bands_from_json(d["bands"]),
+            band_values_by_name={b["name"]: _values_from_json(b) for b in d["bands"]}, iacc_e3=M.num_json(d["iacc_e3"])))
     return out
 
 
@@ -543,18 +491,14 @@ def build_parser() -> argparse.ArgumentParser:
         prog="python -m analyse.iacc",
         description="ISO 3382-1 inter-channel cross-correlation coefficients (IACC early, late, whole) per stereo pair "
                     "and band.")
-    src = p.add_mutually_exclusive_group(required=True)
-    src.add_argument("--input", nargs="+", type=Path, help="stereo WAV files (one pair per file)")
-    src.add_argument("--bundle", type=Path, help="bundle directory: meta.json + taps/<name>.wav")
-    p.add_argument("--bands", choices=["none", *BAND_MODES], default="octave", help="filter bank (default: octave)")
+    M.add_source_arguments(p, "stereo WAV files (one pair per file)", mono=False)
+    M.add_bands_argument(p)
     p.add_argument("--onset-db", type=float, default=-20.0,
                    help="onset: first sample within this level of the peak (default: -20 dB, ISO 3382-1)")
     p.add_argument("--limits-ms", nargs="+", type=float, default=[80.0],
                    help="early/late limits in ms, 1 to 4, ascending (default: 80)")
     p.add_argument("--max-lag-ms", type=float, default=1.0, help="largest lag |tau| in ms (default: 1.0, ISO 3382-1)")
-    p.add_argument("--expected-sample-rate", type=int, default=DEFAULT_EXPECTED_SAMPLE_RATE_HZ,
-                   help="every file must have this sample rate (default: 48000)")
-    p.add_argument("--json", type=Path, default=None, help="also write the results as JSON to this file")
+    M.add_output_arguments(p)
     return p
 
 
@@ -564,25 +508,19 @@ def settings_from_args(args) -> IaccSettings:
                         bands=bands)
 
 
+def _checked_settings_from_args(args) -> IaccSettings:
+    """settings_from_args, and the lag limit checked at the expected sample rate: a usage error, not a failure later on."""
+    settings = settings_from_args(args)
+    tmax = max_lag_samples(settings.max_lag_ms, args.expected_sample_rate)
+    if not 1 <= tmax <= MAX_LAG_SAMPLES:
+        raise ValueError(f"--max-lag-ms {settings.max_lag_ms:g} is {tmax} samples at {args.expected_sample_rate} Hz; "
+                         f"1 to {MAX_LAG_SAMPLES} samples are supported")
+    return settings
+
+
 def main(argv: Optional[Sequence[str]] = None) -> None:
-    parser = build_parser()
-    args = parser.parse_args(argv)
-    try:
-        settings = settings_from_args(args)
-        tmax = max_lag_samples(settings.max_lag_ms, args.expected_sample_rate)
-        if not 1 <= tmax <= MAX_LAG_SAMPLES:
-            raise ValueError(f"--max-lag-ms {settings.max_lag_ms:g} is {tmax} samples at {args.expected_sample_rate} Hz; "
-                             f"1 to {MAX_LAG_SAMPLES} samples are supported")
-    except ValueError as e:
-        parser.error(str(e))
-    if args.input:
-        results = analyse_iacc_files(args.input, settings, args.expected_sample_rate)
-    else:
-        results = analyse_iacc_bundle(args.bundle, settings, args.expected_sample_rate)
-    sys.stdout.write(summarise_iacc_text(results))
-    sys.stdout.flush()
-    if args.json is not None:
-        args.json.write_text(json.dumps(iacc_results_to_json(results), indent=2) + "\n")
+    M.run_cli(build_parser(), argv, _checked_settings_from_args, analyse_iacc_files, analyse_iacc_bundle, summarise_iacc_text,
+              iacc_results_to_json)
 
 
 if __name__ == "__main__":

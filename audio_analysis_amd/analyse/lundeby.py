@@ -9,7 +9,7 @@ on the truncated, compensated Schroeder curve.  This text is the specification; 
 
 Rows.  Row 0 of a channel is its broadband signal from its start index s on, s = the first maximum of |x| (ira_peak_index,
 as trim_to_peak of the decay block); the band rows are the rt60bands filter bank's full-file zero-phase band signals
-(energy.band_signals_device) from the same s.  y = the row from s on, L its length, e[n] = float64(y[n])**2.  Times below
+(rt60bands.band_signals_device) from the same s.  y = the row from s on, L its length, e[n] = float64(y[n])**2.  Times below
 are in samples, levels in dB, slopes in dB per sample.
 
 1 Base blocks.  B = max(ceil(fs / 1000), ceil(L / 4096)), nb = L // B full blocks; a partial tail block takes no part in
@@ -60,21 +60,20 @@ Command line (no plots): python -m analyse.lundeby --input A.wav [B.wav ...] | -
 from __future__ import annotations
 
 import argparse
-import json
 import math
-import sys
 from dataclasses import dataclass, field
 from pathlib import Path
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from ..engine import LUNDEBY_DOUBLES, LUNDEBY_MAX_LEN, get_engine
-from ._common import wav_channels
+from ..engine import LUNDEBY_DOUBLES, LUNDEBY_MAX_LEN
+from . import _measure as M
+from ._common import band_row_offsets
+from ._measure import BAND_MODES
 from .decay import DecayAnalysisSettings, decay_fit_specs
-from .energy import BAND_MODES, MAX_BATCH_CHANNELS, _common_base, band_signals_device
 from .io import DEFAULT_EXPECTED_SAMPLE_RATE_HZ
-from .rt60bands import BandDefinition, Rt60BandsAnalysisSettings
+from .rt60bands import BandDefinition, Rt60BandsAnalysisSettings, band_signals_device
 
 STATUS_SILENT = 1
 STATUS_TOO_SHORT = 2
@@ -217,9 +216,7 @@ def validity(noise_db: float) -> Tuple[bool, bool, bool]:
 
 
 def status_text(status: int) -> str:
-    if status == 0:
-        return "ok"
-    return f"{status} (" + ", ".join(w for bit, w in _STATUS_WORDS if status & bit) + ")"
+    return M.status_text(status, _STATUS_WORDS)
 
 
 def values_from_records(rec: np.ndarray, fits: np.ndarray, sample_rate_hz: float) -> LundebyValues:
@@ -257,23 +254,15 @@ def lundeby_device(eng, batch, sample_rate_hz: int, settings: Optional[LundebySe
     start_dev = start_dev[:nch]
     if band_signals is None and settings.bands is not None:
         band_signals = band_signals_device(eng, batch, sample_rate_hz, settings.bands)
-    bands, y, y_off = band_signals if band_signals is not None else ([], None, np.zeros((nch, 0), dtype=np.int64))
+    bands = band_signals[0] if band_signals is not None else []
     nbands = len(bands)
-    y_off = np.asarray(y_off, dtype=np.int64).reshape(nch, nbands)
     start = start_dev.cpu().numpy().astype(np.int64) if nch else np.zeros(0, np.int64)
     lens64 = batch.length.astype(np.int64)
     row_len, b, nb, m0 = row_tables(lens64, start, sample_rate_hz, nbands)
     bb_off = np.cumsum(row_len) - row_len                              # broadband curves: a buffer of their own
     bb = eng.empty(int(row_len.sum()), t.float32)
-    if nbands:
-        owners = (batch.x, y, bb)
-        base, (dx, dy, db) = _common_base(list(owners))
-        seg_off = np.concatenate([(batch.off + dx)[:, None], y_off + dy], axis=1).reshape(-1)
-        edc_off = np.concatenate([(bb_off + db)[:, None], y_off + dy + start[:, None]], axis=1).reshape(-1)
-    else:
-        owners = (batch.x, bb)
-        base, (dx, db) = _common_base(list(owners))
-        seg_off, edc_off = batch.off + dx, bb_off + db
+    owners = (batch.x, band_signals[1], bb) if nbands else (batch.x, bb)
+    base, seg_off, edc_off = band_row_offsets(batch, band_signals, curves=(bb, bb_off, start))
     rep = 1 + nbands
     rows = eng.lundeby_rows(seg_off, np.repeat(lens64, rep), np.repeat(np.arange(nch, dtype=np.int32), rep), b, nb, m0)
     blk = eng.block_energy(base, rows, start_dev)
@@ -315,59 +304,27 @@ def _results_of_batch(eng, batch, sample_rate_hz, names, settings) -> List[Lunde
 def analyse_lundeby_batch(channels: Sequence[np.ndarray], sample_rate_hz: int, channel_names: Sequence[str],
                           settings: Optional[LundebySettings] = None) -> List[LundebyChannelResult]:
     """Every channel through the device in batches of at most MAX_BATCH_CHANNELS channels."""
-    settings = settings or LundebySettings()
-    if len(channels) != len(channel_names):
-        raise ValueError("one name per channel")
-    eng = get_engine()
-    out: List[LundebyChannelResult] = []
-    for a in range(0, len(channels), MAX_BATCH_CHANNELS):
-        chans = [np.asarray(c, dtype=np.float32).reshape(-1) for c in channels[a : a + MAX_BATCH_CHANNELS]]
-        batch = eng.upload(chans)
-        out += _results_of_batch(eng, batch, sample_rate_hz, channel_names[a : a + MAX_BATCH_CHANNELS], settings)
-    return out
+    return M.analyse_channel_batches(channels, sample_rate_hz, channel_names, settings or LundebySettings(), _results_of_batch)
 
 
 def analyse_lundeby_from_wav_file(input_wav_file_path: str | Path, settings: Optional[LundebySettings] = None,
                                   expected_sample_rate_hz: int = DEFAULT_EXPECTED_SAMPLE_RATE_HZ) -> List[LundebyChannelResult]:
     """One WAV file (mono or stereo, rate checked against expected_sample_rate_hz); channels named "mono", "left", "right"."""
-    settings = settings or LundebySettings()
-    loaded, chans = wav_channels(input_wav_file_path, settings.use_mono_downmix_for_stereo,
-                                 expected_sample_rate_hz=expected_sample_rate_hz)
-    return analyse_lundeby_batch([c for _, c in chans], loaded.sample_rate_hz, [n for n, _ in chans], settings)
+    return M.analyse_wav_file_channels(input_wav_file_path, settings or LundebySettings(), expected_sample_rate_hz,
+                                       analyse_lundeby_batch)
 
 
 def analyse_lundeby_files(paths: Sequence[str | Path], settings: Optional[LundebySettings] = None,
                           expected_sample_rate_hz: int = DEFAULT_EXPECTED_SAMPLE_RATE_HZ) -> List[LundebyChannelResult]:
     """Every channel of every file, MAX_BATCH_CHANNELS channels per device batch; channels named "<file name>:<channel>"."""
-    settings = settings or LundebySettings()
-    chans, names = [], []
-    for p in paths:
-        _, cs = wav_channels(p, settings.use_mono_downmix_for_stereo, expected_sample_rate_hz=expected_sample_rate_hz)
-        for n, c in cs:
-            chans.append(c)
-            names.append(f"{Path(p).name}:{n}")
-    return analyse_lundeby_batch(chans, int(expected_sample_rate_hz), names, settings)
+    return M.analyse_file_channels(paths, settings or LundebySettings(), expected_sample_rate_hz, analyse_lundeby_batch)
 
 
 def analyse_lundeby_bundle(bundle_root: str | Path, settings: Optional[LundebySettings] = None,
                            expected_sample_rate_hz: int = DEFAULT_EXPECTED_SAMPLE_RATE_HZ) -> List[LundebyChannelResult]:
     """The taps a bundle's meta.json lists (taps/<name>.wav), read by the native ingest (ingest.TapSet) a group at a time
     (at most MAX_BATCH_CHANNELS channels per group); channels named "<tap>:<channel>"."""
-    from ..ingest import TapSet
-
-    settings = settings or LundebySettings()
-    root = Path(bundle_root)
-    taps: List[str] = list(json.loads((root / "meta.json").read_text()).get("taps", []))
-    eng = get_engine()
-    out: List[LundebyChannelResult] = []
-    step = MAX_BATCH_CHANNELS // 2                        # a tap has one or two channels
-    for a in range(0, len(taps), step):
-        group = taps[a : a + step]
-        ts = TapSet(eng, [root / "taps" / f"{t}.wav" for t in group], expected_sample_rate_hz)
-        batch, labels = ts.view(settings.use_mono_downmix_for_stereo)
-        names = [f"{group[i]}:{ch}" for i, ch in labels]
-        out += _results_of_batch(eng, batch, int(expected_sample_rate_hz), names, settings)
-    return out
+    return M.analyse_bundle_channels(bundle_root, settings or LundebySettings(), expected_sample_rate_hz, _results_of_batch)
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -377,10 +334,6 @@ def analyse_lundeby_bundle(bundle_root: str | Path, settings: Optional[LundebySe
 _COLUMNS = ("Noise_dB", "Cross_ms", "Range_dB", "Slope_dB_s", "C", "EDT_s", "T20_s", "T30_s", "Valid", "Status")
 
 
-def _fmt(v: float, digits: int) -> str:
-    return "NA" if math.isnan(v) else f"{v:.{digits}f}"
-
-
 def _valid_text(v: LundebyValues) -> str:
     names = [n for n, ok in (("EDT", v.edt_valid), ("T20", v.t20_valid), ("T30", v.t30_valid)) if ok]
     return "+".join(names) if names else "none"
@@ -388,13 +341,13 @@ def _valid_text(v: LundebyValues) -> str:
 
 def _cells(v: LundebyValues) -> List[str]:
     c = "NA" if math.isnan(v.compensation_energy) else f"{v.compensation_energy:.4e}"
-    return [_fmt(v.noise_db, 2), _fmt(1000.0 * v.cross_point_seconds, 1), _fmt(v.dynamic_range_db, 2),
-            _fmt(v.late_slope_db_per_second, 2), c, _fmt(v.edt_seconds, 3), _fmt(v.t20_seconds, 3), _fmt(v.t30_seconds, 3),
+    return [M.fmt(v.noise_db, 2), M.fmt(1000.0 * v.cross_point_seconds, 1), M.fmt(v.dynamic_range_db, 2),
+            M.fmt(v.late_slope_db_per_second, 2), c, M.fmt(v.edt_seconds, 3), M.fmt(v.t20_seconds, 3), M.fmt(v.t30_seconds, 3),
             _valid_text(v), status_text(v.status)]
 
 
-def _rows(r: LundebyChannelResult) -> List[Tuple[str, LundebyValues]]:
-    return [("Broadband", r.broadband)] + [(b.name, r.band_values_by_name[b.name]) for b in r.band_definitions]
+def _rows(r: LundebyChannelResult) -> List[List[str]]:
+    return [[name] + _cells(v) for name, v in M.band_rows(r, r.band_values_by_name)]
 
 
 def summarise_lundeby_text(channel_results: List[LundebyChannelResult]) -> str:
@@ -408,15 +361,10 @@ def summarise_lundeby_text(channel_results: List[LundebyChannelResult]) -> str:
         <band name>  ...                       (one row per band, ascending)
     Cells are separated by two spaces; NaN is "NA".
     """
-    lines: List[str] = []
-    for r in channel_results:
-        lines.append(f"[{r.channel_name}]")
-        lines.append(f"Start: {r.start_samples} samples ({1000.0 * r.start_samples / r.sample_rate_hz:.3f} ms)  Mode: {r.mode}")
-        lines.append("  ".join(("Band",) + _COLUMNS))
-        for name, v in _rows(r):
-            lines.append("  ".join([name] + _cells(v)))
-        lines.append("")
-    return "\n".join(lines) + ("\n" if lines else "")
+    return M.join_blocks(M.text_block(
+        r.channel_name,
+        f"Start: {r.start_samples} samples ({1000.0 * r.start_samples / r.sample_rate_hz:.3f} ms)  Mode: {r.mode}",
+        _COLUMNS, _rows(r)) for r in channel_results)
 
 
 def summarise_lundeby_markdown(channel_results: List[LundebyChannelResult]) -> str:
@@ -424,18 +372,10 @@ def summarise_lundeby_markdown(channel_results: List[LundebyChannelResult]) -> s
     with the columns of the text format, rows Broadband then the bands."""
     cols = ("Noise (dB)", "Cross-point (ms)", "Range (dB)", "Late slope (dB/s)", "C", "EDT (s)", "T20 (s)", "T30 (s)", "Valid",
             "Status")
-    lines: List[str] = []
-    for r in channel_results:
-        lines.append(f"### {r.channel_name}")
-        lines.append("")
-        lines.append(f"Start: {r.start_samples} samples ({1000.0 * r.start_samples / r.sample_rate_hz:.3f} ms). Mode: {r.mode}.")
-        lines.append("")
-        lines.append("| Band | " + " | ".join(cols) + " |")
-        lines.append("|---|" + "---:|" * len(cols))
-        for name, v in _rows(r):
-            lines.append("| " + " | ".join([name] + _cells(v)) + " |")
-        lines.append("")
-    return "\n".join(lines) + ("\n" if lines else "")
+    return M.join_blocks(M.markdown_block(
+        r.channel_name,
+        f"Start: {r.start_samples} samples ({1000.0 * r.start_samples / r.sample_rate_hz:.3f} ms). Mode: {r.mode}.",
+        cols, _rows(r)) for r in channel_results)
 
 
 _FLOAT_FIELDS = ("noise_db", "cross_point_seconds", "dynamic_range_db", "late_slope_db_per_second", "compensation_energy",
@@ -446,8 +386,7 @@ _BOOL_FIELDS = ("edt_valid", "t20_valid", "t30_valid")
 def _values_json(v: LundebyValues) -> Dict:
     d: Dict = {"status": v.status}
     for k in _FLOAT_FIELDS:
-        x = getattr(v, k)
-        d[k] = None if math.isnan(x) else float(x)
+        d[k] = M.json_num(getattr(v, k))
     for k in _BOOL_FIELDS:
         d[k] = bool(getattr(v, k))
     return d
@@ -455,7 +394,7 @@ def _values_json(v: LundebyValues) -> Dict:
 
 def _values_from_json(d: Dict) -> LundebyValues:
     return LundebyValues(status=int(d["status"]),
-                         **{k: (float("nan") if d[k] is None else float(d[k])) for k in _FLOAT_FIELDS},
+                         **{k: M.num_json(d[k]) for k in _FLOAT_FIELDS},
                          **{k: bool(d[k]) for k in _BOOL_FIELDS})
 
 
@@ -466,9 +405,7 @@ def lundeby_results_to_json(channel_results: List[LundebyChannelResult]) -> Dict
         rows.append({
             "channel_name": r.channel_name, "sample_rate_hz": r.sample_rate_hz, "mode": r.mode,
             "start_samples": r.start_samples, "broadband": _values_json(r.broadband),
-            "bands": [dict(name=b.name, centre_hz=b.centre_hz, kind=b.kind, low_edge_hz=b.low_edge_hz,
-                           high_edge_hz=b.high_edge_hz, **_values_json(r.band_values_by_name[b.name]))
-                      for b in r.band_definitions],
+            "bands": [M.band_to_json(b, _values_json(r.band_values_by_name[b.name])) for b in r.band_definitions],
         })
     return {"lundeby": rows}
 
@@ -476,10 +413,10 @@ def lundeby_results_to_json(channel_results: List[LundebyChannelResult]) -> Dict
 def lundeby_results_from_json(doc: Dict) -> List[LundebyChannelResult]:
     out = []
     for d in doc["lundeby"]:
-        bands = [BandDefinition(b["name"], b["centre_hz"], b["kind"], b["low_edge_hz"], b["high_edge_hz"]) for b in d["bands"]]
         out.append(LundebyChannelResult(
             channel_name=d["channel_name"], sample_rate_hz=int(d["sample_rate_hz"]), mode=str(d["mode"]),
-            start_samples=int(d["start_samples"]), broadband=_values_from_json(d["broadband"]), band_definitions=bands,
+            start_samples=int(d["start_samples"]), broadband=_values_from_json(d["broadband"]),
+            band_definitions=M.bands_from_json(d["bands"]),
             band_values_by_name={b["name"]: _values_from_json(b) for b in d["bands"]}))
     return out
 
@@ -495,17 +432,12 @@ def build_parser() -> argparse.ArgumentParser:
         description="Noise level, cross-point and EDT / T20 / T30 on the truncated, compensated Schroeder curve "
                     "(Lundeby's method, ISO 3382-1) per channel and band.  A channel holds at most "
                     f"{MAX_CHANNEL_SAMPLES} samples (174.7 s at 48 kHz); a longer file is refused.")
-    src = p.add_mutually_exclusive_group(required=True)
-    src.add_argument("--input", nargs="+", type=Path, help="WAV files (every channel of every file is analysed)")
-    src.add_argument("--bundle", type=Path, help="bundle directory: meta.json + taps/<name>.wav")
-    p.add_argument("--mono", action="store_true", help="analyse stereo files as their mono downmix 0.5 * (L + R)")
-    p.add_argument("--bands", choices=["none", *BAND_MODES], default="octave", help="filter bank (default: octave)")
+    M.add_source_arguments(p)
+    M.add_bands_argument(p)
     p.add_argument("--mode", choices=list(MODES), default="compensate",
                    help="compensate: add the energy the decay would have had after the cross-point (default); "
                         "truncate: stop the integration there")
-    p.add_argument("--expected-sample-rate", type=int, default=DEFAULT_EXPECTED_SAMPLE_RATE_HZ,
-                   help="every file must have this sample rate (default: 48000)")
-    p.add_argument("--json", type=Path, default=None, help="also write the results as JSON to this file")
+    M.add_output_arguments(p)
     return p
 
 
@@ -515,20 +447,8 @@ def settings_from_args(args) -> LundebySettings:
 
 
 def main(argv: Optional[Sequence[str]] = None) -> None:
-    parser = build_parser()
-    args = parser.parse_args(argv)
-    try:
-        settings = settings_from_args(args)
-    except ValueError as e:
-        parser.error(str(e))
-    if args.input:
-        results = analyse_lundeby_files(args.input, settings, args.expected_sample_rate)
-    else:
-        results = analyse_lundeby_bundle(args.bundle, settings, args.expected_sample_rate)
-    sys.stdout.write(summarise_lundeby_text(results))
-    sys.stdout.flush()
-    if args.json is not None:
-        args.json.write_text(json.dumps(lundeby_results_to_json(results), indent=2) + "\n")
+    M.run_cli(build_parser(), argv, settings_from_args, analyse_lundeby_files, analyse_lundeby_bundle, summarise_lundeby_text,
+              lundeby_results_to_json)
 
 
 if __name__ == "__main__":

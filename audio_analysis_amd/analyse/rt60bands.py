@@ -196,6 +196,36 @@ def rt60_bands_results(bands, values, have, sample_rate_hz: int, channel_names) 
     return out
 
 
+def band_signals_device(eng, batch, sample_rate_hz: int, band_settings: Rt60BandsAnalysisSettings, want_tiles: bool = False):
+    """The filter bank for a device batch: one forward float64 rFFT of every full file, masked inverse transforms per band.
+    Returns (bands, y float32 device, y_off (nch, nbands) int64): band b of channel c is batch.length[c] samples at
+    y_off[c, b] of y, channel after channel, band after band.  want_tiles: a fourth element, what
+    Engine.band_irfft(want_tiles=True) returns (the partial energies of the band signals' EDC tiles, or None)."""
+    t = eng.torch
+    nch = batch.count
+    n64 = batch.length.astype(np.int64)
+    if np.any(n64 < 8):
+        raise ValueError("Not enough samples for band analysis.")
+    bands = _build_band_definitions(band_settings, sample_rate_hz)
+    nb = len(bands)
+    if nb == 0:
+        return (bands, None, np.zeros((nch, 0), dtype=np.int64)) + ((None,) if want_tiles else ())
+    nyq = 0.5 * float(sample_rate_hz)
+    records = np.stack([band_mask_record(b, band_settings.transition_width_octaves, nyq) for b in bands])
+    spec, spec_off = eng.rfft_any(batch.x, batch.off, n64, use_hann=False)
+    # (array arithmetic instead of nested Python loops over 256 channels x bands: the loops were ~2 ms of the host's ~6 ms
+    # per report step, which is what bounds the bundle configuration -- its kernels take less time than its host code)
+    per_entry = np.repeat(n64, nb)
+    y_off = (np.cumsum(per_entry) - per_entry).reshape(nch, nb)
+    y = eng.empty(int(per_entry.sum()), t.float32)
+    fv_of = {int(v): rfft_bin_step(int(v), sample_rate_hz) for v in np.unique(n64)}
+    fv = np.array([fv_of[int(v)] for v in n64], dtype=np.float64)
+    # one entry per (channel, band); the engine pairs entries of equal length two per inverse transform
+    tiles = eng.band_irfft(spec, np.repeat(np.asarray(spec_off, dtype=np.int64), nb), per_entry.astype(np.int32),
+                           np.tile(records, (nch, 1)), np.repeat(fv, nb), y, y_off.reshape(-1), want_tiles=want_tiles)
+    return (bands, y, y_off) + ((tiles,) if want_tiles else ())
+
+
 def rt60_bands_device(eng, batch, sample_rate_hz: int, settings: Rt60BandsAnalysisSettings, defer: bool = False):
     """
     Filter bank + per-band decay fits for a device-resident batch.
@@ -203,7 +233,6 @@ def rt60_bands_device(eng, batch, sample_rate_hz: int, settings: Rt60BandsAnalys
     With defer=True the device->host copy of the fit records is postponed: the second element is then a
     zero-argument callable producing `values` (lets a pipeline enqueue more work before synchronising).
     """
-    t = eng.torch
     dec = settings.decay_settings
     smooth = int(dec.edc_smoothing_window_samples or 0)
     nch = batch.count
@@ -217,12 +246,6 @@ def rt60_bands_device(eng, batch, sample_rate_hz: int, settings: Rt60BandsAnalys
         skip = np.clip(raw, 0, n_all)
     start = np.minimum(n_all, peaks + skip)
 
-    bands = _build_band_definitions(settings, sample_rate_hz)
-    nyq = 0.5 * float(sample_rate_hz)
-    records = np.stack([band_mask_record(b, settings.transition_width_octaves, nyq) for b in bands]) \
-        if bands else np.zeros((0, 8))
-    nb = len(bands)
-
     fits_spec = [("t30", dec.t30_range_db)]
     if settings.include_t20:
         fits_spec.append(("t20", dec.t20_range_db))
@@ -235,28 +258,14 @@ def rt60_bands_device(eng, batch, sample_rate_hz: int, settings: Rt60BandsAnalys
             raise ValueError("range_db should be (higher_db, lower_db), e.g. (-5, -25).")
         ranges.append((hi, max(lo, float(dec.fit_lower_limit_db))))
 
-    # forward spectra of the full files
-    spec, spec_off = eng.rfft_any(batch.x, batch.off, n_all, use_hann=False)
-
-    # band signals: y[c][b] has n_c float32 samples, channel after channel, band after band
-    # (array arithmetic instead of nested Python loops over 256 channels x bands: the loops were ~2 ms of the host's ~6 ms
-    # per report step, which is what bounds the bundle configuration -- its kernels take less time than its host code)
+    # (the inverses also leave the energies of every band signal's EDC tiles: the fused fits below then read a band
+    # signal once less -- not for the smoothed-curve path, which materialises the curve through ira_edc_db)
+    bands, y, y_off, *tiles = band_signals_device(eng, batch, sample_rate_hz, settings, want_tiles=smooth <= 1)
+    band_tiles = tiles[0] if tiles else None
+    nb = len(bands)
     n64 = n_all.astype(np.int64)
-    per_entry = np.repeat(n64, nb)
-    y_off = (np.cumsum(per_entry) - per_entry).reshape(nch, nb) if nb else np.zeros((nch, 1), dtype=np.int64)
-    pos = int(per_entry.sum())
-    y = eng.empty(pos, t.float32)
-    if nb:
-        # one entry per (channel, band); the engine pairs entries of equal length two per inverse transform
-        fv_of = {int(v): rfft_bin_step(int(v), sample_rate_hz) for v in np.unique(n64)}
-        fv = np.array([fv_of[int(v)] for v in n64], dtype=np.float64)
-        # (the inverses also leave the energies of every band signal's EDC tiles: the fused fits below then read a band
-        # signal once less -- not for the smoothed-curve path, which materialises the curve through ira_edc_db)
-        band_tiles = eng.band_irfft(spec, np.repeat(np.asarray(spec_off, dtype=np.int64), nb),
-                                    np.repeat(n64, nb).astype(np.int32), np.tile(records, (nch, 1)), np.repeat(fv, nb), y,
-                                    y_off.reshape(-1), want_tiles=smooth <= 1)
-    else:
-        band_tiles = None
+    if not nb:
+        y_off = np.zeros((nch, 1), dtype=np.int64)
 
     # Schroeder EDC + fits on every (channel, band) tail with at least 8 samples
     tail_c = n64 - start.astype(np.int64)

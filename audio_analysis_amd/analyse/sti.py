@@ -52,20 +52,17 @@ Command line (no plots): python -m analyse.sti --input A.wav [B.wav ...] | --bun
 from __future__ import annotations
 
 import argparse
-import json
 import math
-import sys
 from dataclasses import dataclass
 from pathlib import Path
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from ..engine import get_engine
-from ._common import wav_channels
-from .energy import band_signals_device
+from . import _measure as M
+from ._measure import MAX_BATCH_CHANNELS  # noqa: F401  (part of this module's surface)
 from .io import DEFAULT_EXPECTED_SAMPLE_RATE_HZ
-from .rt60bands import Rt60BandsAnalysisSettings
+from .rt60bands import Rt60BandsAnalysisSettings, band_signals_device
 
 STATUS_SILENT = 1
 STATUS_NON_FINITE = 2
@@ -81,7 +78,6 @@ ALPHA = (0.085, 0.127, 0.230, 0.233, 0.309, 0.224, 0.173)
 BETA = (0.085, 0.078, 0.065, 0.011, 0.047, 0.095)
 RECEPTION_THRESHOLD_DB = (46.0, 27.0, 12.0, 6.5, 7.5, 8.0, 12.0)
 RATINGS = ((0.30, "bad"), (0.45, "poor"), (0.60, "fair"), (0.75, "good"))
-MAX_BATCH_CHANNELS = 256          # channels per device batch (the CLI's chunk)
 
 
 def sti_band_settings() -> Rt60BandsAnalysisSettings:
@@ -156,9 +152,7 @@ class StiSums:
 
 
 def status_text(status: int) -> str:
-    if status == 0:
-        return "ok"
-    return f"{status} (" + ", ".join(w for bit, w in _STATUS_WORDS if status & bit) + ")"
+    return M.status_text(status, _STATUS_WORDS)
 
 
 def rating_word(sti: float) -> str:
@@ -303,68 +297,36 @@ def sti_results(res: StiSums, sample_rate_hz: int, channel_names: Sequence[str],
 # ---------------------------------------------------------------------------------------------------
 
 
+def _results_of_batch(eng, batch, sample_rate_hz, names, settings) -> List[StiChannelResult]:
+    return sti_results(sti_device(eng, batch, sample_rate_hz, settings), sample_rate_hz, names, settings)
+
+
 def analyse_sti_batch(channels: Sequence[np.ndarray], sample_rate_hz: int, channel_names: Sequence[str],
                       settings: Optional[StiSettings] = None) -> List[StiChannelResult]:
     """Every channel through the device in batches of at most MAX_BATCH_CHANNELS channels."""
-    settings = settings or StiSettings()
-    if len(channels) != len(channel_names):
-        raise ValueError("one name per channel")
-    eng = get_engine()
-    out: List[StiChannelResult] = []
-    for a in range(0, len(channels), MAX_BATCH_CHANNELS):
-        chans = [np.asarray(c, dtype=np.float32).reshape(-1) for c in channels[a : a + MAX_BATCH_CHANNELS]]
-        batch = eng.upload(chans)
-        out += _results_of_batch(eng, batch, sample_rate_hz, channel_names[a : a + MAX_BATCH_CHANNELS], settings)
-    return out
-
-
-def _results_of_batch(eng, batch, sample_rate_hz, names, settings) -> List[StiChannelResult]:
-    return sti_results(sti_device(eng, batch, sample_rate_hz, settings), sample_rate_hz, names, settings)
+    return M.analyse_channel_batches(channels, sample_rate_hz, channel_names, settings or StiSettings(), _results_of_batch)
 
 
 def analyse_sti_from_wav_file(input_wav_file_path: str | Path, settings: Optional[StiSettings] = None,
                               expected_sample_rate_hz: int = DEFAULT_EXPECTED_SAMPLE_RATE_HZ) -> List[StiChannelResult]:
     """One WAV file (mono or stereo, rate checked against expected_sample_rate_hz); channels named as by
     get_analysis_channels ("mono", "left", "right")."""
-    settings = settings or StiSettings()
-    loaded, chans = wav_channels(input_wav_file_path, settings.use_mono_downmix_for_stereo,
-                                 expected_sample_rate_hz=expected_sample_rate_hz)
-    return analyse_sti_batch([c for _, c in chans], loaded.sample_rate_hz, [n for n, _ in chans], settings)
+    return M.analyse_wav_file_channels(input_wav_file_path, settings or StiSettings(), expected_sample_rate_hz,
+                                       analyse_sti_batch)
 
 
 def analyse_sti_files(paths: Sequence[str | Path], settings: Optional[StiSettings] = None,
                       expected_sample_rate_hz: int = DEFAULT_EXPECTED_SAMPLE_RATE_HZ) -> List[StiChannelResult]:
     """Every channel of every file in one device batch per MAX_BATCH_CHANNELS channels; channels named
     "<file name>:<channel>"."""
-    settings = settings or StiSettings()
-    chans, names = [], []
-    for p in paths:
-        _, cs = wav_channels(p, settings.use_mono_downmix_for_stereo, expected_sample_rate_hz=expected_sample_rate_hz)
-        for n, c in cs:
-            chans.append(c)
-            names.append(f"{Path(p).name}:{n}")
-    return analyse_sti_batch(chans, int(expected_sample_rate_hz), names, settings)
+    return M.analyse_file_channels(paths, settings or StiSettings(), expected_sample_rate_hz, analyse_sti_batch)
 
 
 def analyse_sti_bundle(bundle_root: str | Path, settings: Optional[StiSettings] = None,
                        expected_sample_rate_hz: int = DEFAULT_EXPECTED_SAMPLE_RATE_HZ) -> List[StiChannelResult]:
     """The taps a bundle's meta.json lists (taps/<name>.wav), read by the native ingest (ingest.TapSet) a group at a
     time (at most MAX_BATCH_CHANNELS channels per group); channels named "<tap>:<channel>"."""
-    from ..ingest import TapSet
-
-    settings = settings or StiSettings()
-    root = Path(bundle_root)
-    taps: List[str] = list(json.loads((root / "meta.json").read_text()).get("taps", []))
-    eng = get_engine()
-    out: List[StiChannelResult] = []
-    step = MAX_BATCH_CHANNELS // 2                        # a tap has one or two channels
-    for a in range(0, len(taps), step):
-        group = taps[a : a + step]
-        ts = TapSet(eng, [root / "taps" / f"{t}.wav" for t in group], expected_sample_rate_hz)
-        batch, labels = ts.view(settings.use_mono_downmix_for_stereo)
-        names = [f"{group[i]}:{ch}" for i, ch in labels]
-        out += _results_of_batch(eng, batch, int(expected_sample_rate_hz), names, settings)
-    return out
+    return M.analyse_bundle_channels(bundle_root, settings or StiSettings(), expected_sample_rate_hz, _results_of_batch)
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -372,12 +334,12 @@ def analyse_sti_bundle(bundle_root: str | Path, settings: Optional[StiSettings] 
 # ---------------------------------------------------------------------------------------------------
 
 
-def _fmt(v: float, digits: int = 3) -> str:
-    return "NA" if math.isnan(v) else f"{v:.{digits}f}"
-
-
 def _columns(r: StiChannelResult) -> List[str]:
     return ["MTI"] + [f"{f:g}Hz" for f in r.modulation_frequencies_hz]
+
+
+def _rows(r: StiChannelResult) -> List[List[str]]:
+    return [[name, M.fmt(mti)] + [M.fmt(v) for v in row] for name, mti, row in zip(r.band_names, r.mti, r.mtf)]
 
 
 def summarise_sti_text(channel_results: List[StiChannelResult]) -> str:
@@ -389,41 +351,17 @@ def summarise_sti_text(channel_results: List[StiChannelResult]) -> str:
         <band name>  <MTI, 3 decimals>  <m, 3 decimals>  ...      (one row per band, ascending)
     Cells are separated by two spaces; NaN is "NA".
     """
-    lines: List[str] = []
-    for r in channel_results:
-        lines.append(f"[{r.channel_name}]")
-        lines.append(f"STI: {_fmt(r.sti)} ({r.rating})  Status: {status_text(r.status)}")
-        lines.append("  ".join(["Band"] + _columns(r)))
-        for name, mti, row in zip(r.band_names, r.mti, r.mtf):
-            lines.append("  ".join([name, _fmt(mti)] + [_fmt(v) for v in row]))
-        lines.append("")
-    return "\n".join(lines) + ("\n" if lines else "")
+    return M.join_blocks(M.text_block(
+        r.channel_name, f"STI: {M.fmt(r.sti)} ({r.rating})  Status: {status_text(r.status)}", _columns(r), _rows(r))
+        for r in channel_results)
 
 
 def summarise_sti_markdown(channel_results: List[StiChannelResult]) -> str:
     """The same values as a Markdown section per channel: a '### <channel name>' heading, an STI / status line and the
     modulation transfer matrix as a table (rows: bands; columns: MTI, then m per modulation frequency)."""
-    lines: List[str] = []
-    for r in channel_results:
-        cols = _columns(r)
-        lines.append(f"### {r.channel_name}")
-        lines.append("")
-        lines.append(f"STI: {_fmt(r.sti)} ({r.rating}). Status: {status_text(r.status)}.")
-        lines.append("")
-        lines.append("| Band | " + " | ".join(cols) + " |")
-        lines.append("|---|" + "---:|" * len(cols))
-        for name, mti, row in zip(r.band_names, r.mti, r.mtf):
-            lines.append("| " + " | ".join([name, _fmt(mti)] + [_fmt(v) for v in row]) + " |")
-        lines.append("")
-    return "\n".join(lines) + ("\n" if lines else "")
-
-
-def _json_num(v: float):
-    return None if math.isnan(v) else float(v)
-
-
-def _num_json(v) -> float:
-    return float("nan") if v is None else float(v)
+    return M.join_blocks(M.markdown_block(
+        r.channel_name, f"STI: {M.fmt(r.sti)} ({r.rating}). Status: {status_text(r.status)}.", _columns(r), _rows(r))
+        for r in channel_results)
 
 
 def sti_results_to_json(channel_results: List[StiChannelResult]) -> Dict:
@@ -432,9 +370,9 @@ def sti_results_to_json(channel_results: List[StiChannelResult]) -> Dict:
     for r in channel_results:
         rows.append({
             "channel_name": r.channel_name, "sample_rate_hz": r.sample_rate_hz, "status": r.status,
-            "sti": _json_num(r.sti), "rating": r.rating,
+            "sti": M.json_num(r.sti), "rating": r.rating,
             "modulation_frequencies_hz": list(r.modulation_frequencies_hz),
-            "bands": [dict(name=n, mti=_json_num(v), mtf=[_json_num(x) for x in row])
+            "bands": [dict(name=n, mti=M.json_num(v), mtf=[M.json_num(x) for x in row])
                       for n, v, row in zip(r.band_names, r.mti, r.mtf)],
         })
     return {"sti": rows}
@@ -445,10 +383,10 @@ def sti_results_from_json(doc: Dict) -> List[StiChannelResult]:
     for d in doc["sti"]:
         out.append(StiChannelResult(
             channel_name=d["channel_name"], sample_rate_hz=int(d["sample_rate_hz"]), status=int(d["status"]),
-            sti=_num_json(d["sti"]), rating=str(d["rating"]), band_names=tuple(b["name"] for b in d["bands"]),
+            sti=M.num_json(d["sti"]), rating=str(d["rating"]), band_names=tuple(b["name"] for b in d["bands"]),
             modulation_frequencies_hz=tuple(float(v) for v in d["modulation_frequencies_hz"]),
-            mti=tuple(_num_json(b["mti"]) for b in d["bands"]),
-            mtf=tuple(tuple(_num_json(x) for x in b["mtf"]) for b in d["bands"])))
+            mti=tuple(M.num_json(b["mti"]) for b in d["bands"]),
+            mtf=tuple(tuple(M.num_json(x) for x in b["mtf"]) for b in d["bands"])))
     return out
 
 
@@ -461,17 +399,12 @@ def build_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(
         prog="python -m analyse.sti",
         description="Speech transmission index (IEC 60268-16, male) and the modulation transfer matrix per channel.")
-    src = p.add_mutually_exclusive_group(required=True)
-    src.add_argument("--input", nargs="+", type=Path, help="WAV files (every channel of every file is analysed)")
-    src.add_argument("--bundle", type=Path, help="bundle directory: meta.json + taps/<name>.wav")
-    p.add_argument("--mono", action="store_true", help="analyse stereo files as their mono downmix 0.5 * (L + R)")
+    M.add_source_arguments(p)
     p.add_argument("--snr-db", nargs="+", type=float, default=None,
                    help="signal-to-noise ratio in dB: one value for every band, or 7 (125 Hz .. 8 kHz)")
     p.add_argument("--levels-db", nargs=NUM_BANDS, type=float, default=None,
                    help="band levels in dB SPL (signal plus noise), 7 values: switches on masking and the reception threshold")
-    p.add_argument("--expected-sample-rate", type=int, default=DEFAULT_EXPECTED_SAMPLE_RATE_HZ,
-                   help="every file must have this sample rate (default: 48000)")
-    p.add_argument("--json", type=Path, default=None, help="also write the results as JSON to this file")
+    M.add_output_arguments(p)
     return p
 
 
@@ -482,20 +415,8 @@ def settings_from_args(args) -> StiSettings:
 
 
 def main(argv: Optional[Sequence[str]] = None) -> None:
-    parser = build_parser()
-    args = parser.parse_args(argv)
-    try:
-        settings = settings_from_args(args)
-    except ValueError as e:
-        parser.error(str(e))
-    if args.input:
-        results = analyse_sti_files(args.input, settings, args.expected_sample_rate)
-    else:
-        results = analyse_sti_bundle(args.bundle, settings, args.expected_sample_rate)
-    sys.stdout.write(summarise_sti_text(results))
-    sys.stdout.flush()
-    if args.json is not None:
-        args.json.write_text(json.dumps(sti_results_to_json(results), indent=2) + "\n")
+    M.run_cli(build_parser(), argv, settings_from_args, analyse_sti_files, analyse_sti_bundle, summarise_sti_text,
+              sti_results_to_json)
 
 
 if __name__ == "__main__":

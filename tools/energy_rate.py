@@ -13,7 +13,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 
 from audio_analysis_amd.analyse import energy as E
-from audio_analysis_amd.analyse.rt60bands import Rt60BandsAnalysisSettings
+from audio_analysis_amd.analyse.rt60bands import Rt60BandsAnalysisSettings, band_signals_device
 from audio_analysis_amd.engine import Engine
 from audio_analysis_amd.synth import synth_ir
 
@@ -24,7 +24,7 @@ batch = eng.upload(host)
 rows = []
 for mode in ("octave", "third"):
     st = E.EnergyParameterSettings(bands=Rt60BandsAnalysisSettings(band_mode=mode))
-    sig = E.band_signals_device(eng, batch, SR, st.bands)
+    sig = band_signals_device(eng, batch, SR, st.bands)
     for _ in range(2):
         E.energy_parameters_device(eng, batch, SR, st, band_signals=sig)
     eng.sync()

@@ -12,8 +12,8 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 
-from audio_analysis_amd.analyse import energy as E
 from audio_analysis_amd.analyse import iacc as I
+from audio_analysis_amd.analyse.rt60bands import band_signals_device
 from audio_analysis_amd.engine import Engine
 from audio_analysis_amd.synth import synth_ir
 
@@ -23,7 +23,7 @@ host = [synth_ir(i, c, N, SR) for i in range(PAIRS) for c in (0, 1)]
 batch = eng.upload(host)
 pairs = [(2 * i, 2 * i + 1) for i in range(PAIRS)]
 st = I.IaccSettings()
-sig = E.band_signals_device(eng, batch, SR, st.bands)
+sig = band_signals_device(eng, batch, SR, st.bands)
 for _ in range(2):
     res = I.iacc_device(eng, batch, pairs, SR, st, band_signals=sig)
 eng.sync()

@@ -12,9 +12,10 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 
-from audio_analysis_amd.analyse import energy as E
 from audio_analysis_amd.analyse import lundeby as L
+from audio_analysis_amd.analyse._common import band_row_offsets
 from audio_analysis_amd.analyse.decay import decay_fit_specs
+from audio_analysis_amd.analyse.rt60bands import band_signals_device
 from audio_analysis_amd.engine import Engine
 from audio_analysis_amd.synth import synth_ir
 
@@ -28,7 +29,7 @@ for i in range(CH):
     host.append((x + rng.standard_normal(N).astype(np.float32) * np.float32(np.max(np.abs(x)) * 10.0 ** (-55.0 / 20.0))))
 batch = eng.upload(host)
 st = L.LundebySettings()
-bands, y, y_off = E.band_signals_device(eng, batch, SR, st.bands)
+bands, y, y_off = band_signals_device(eng, batch, SR, st.bands)
 y0 = y.clone()
 NAMES = ("ira_block_energy", "ira_lundeby_estimate", "ira_edc_truncated", "ira_curve_fits")
 runs = {n: [] for n in NAMES}
@@ -49,8 +50,8 @@ curve_len = dev.lens_dev.cpu().numpy().astype(np.int64)
 status = dev.records.cpu().numpy()[:, 0].astype(np.int64)
 # the yardstick: the fused plain EDC + fits on the same rows
 y.copy_(y0)
-base, (dx, dy) = E._common_base([batch.x, y])
-seg_off = np.concatenate([(batch.off + dx + start)[:, None], y_off + dy + start[:, None]], axis=1).reshape(-1)
+base, seg_off = band_row_offsets(batch, (bands, y, y_off))
+seg_off = seg_off + np.repeat(start, rows)
 _, ranges = decay_fit_specs(st.decay)
 fused = []
 for rep in range(WARM + REPS):

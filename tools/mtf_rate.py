@@ -13,7 +13,8 @@ import numpy as np
 
 from audio_analysis_amd.analyse import energy as E
 from audio_analysis_amd.analyse import sti as S
-from audio_analysis_amd.analyse.rt60bands import Rt60BandsAnalysisSettings
+from audio_analysis_amd.analyse._common import band_row_offsets
+from audio_analysis_amd.analyse.rt60bands import Rt60BandsAnalysisSettings, band_signals_device
 from audio_analysis_amd.engine import Engine
 from audio_analysis_amd.synth import synth_ir
 
@@ -21,10 +22,9 @@ CH, N, SR, REPS, WARM = 256, 480_000, 48_000, 7, 2
 FP64_PEAK_TFLOPS, HBM_COPY_TB_S = 78.6, 6.29      # MI355X: specified vector float64 peak, measured float4 copy
 eng = Engine("cuda:0")
 batch = eng.upload([synth_ir(i, 0, N, SR) for i in range(CH)])
-bands, y, y_off = E.band_signals_device(eng, batch, SR, Rt60BandsAnalysisSettings(band_mode="octave"))
+bands, y, y_off = band_signals_device(eng, batch, SR, Rt60BandsAnalysisSettings(band_mode="octave"))
 rows = 1 + len(bands)
-base, (dx, dy) = E._common_base([batch.x, y])
-seg_off = np.concatenate([(batch.off + dx)[:, None], y_off + dy], axis=1).reshape(-1)
+base, seg_off = band_row_offsets(batch, (bands, y, y_off))
 seg_len = np.repeat(batch.length.astype(np.int64), rows)
 w = np.tile(S.modulation_turns(S.MODULATION_FREQUENCIES_HZ, SR), (seg_off.size, 1))
 nf = int(w.shape[1])
