@@ -1,4 +1,4 @@
-"""What the per-channel measure modules (energy, iacc, lundeby, sti) share beyond their arithmetic: the batch, file and
+"""What the per-channel measure modules (energy, iacc, lundeby, sti, harmonics) share beyond their arithmetic: the batch, file and
 bundle drivers, the cells, band rows and blocks of their text / Markdown / JSON output, and the command-line skeleton.
 A measure module holds its settings, its device function, its host arithmetic and thin entry points built from these."""
 from __future__ import annotations
@@ -140,17 +140,17 @@ def band_rows(r, values_by_name: Dict) -> List[Tuple[str, object]]:
 
 
 def text_block(name: str, head: str, columns: Sequence[str], rows: Iterable[Sequence[str]],
-               tail: Sequence[str] = ()) -> List[str]:
+               tail: Sequence[str] = (), first: str = "Band") -> List[str]:
     """The lines of one block of a text summary: [name], the head line, the column row, a row of cells per row (cells
-    separated by two spaces), the tail lines and an empty line."""
-    return [f"[{name}]", head, "  ".join(["Band", *columns])] + ["  ".join(cells) for cells in rows] + [*tail, ""]
+    separated by two spaces), the tail lines and an empty line.  first: the heading of the rows' first cell."""
+    return [f"[{name}]", head, "  ".join([first, *columns])] + ["  ".join(cells) for cells in rows] + [*tail, ""]
 
 
 def markdown_block(name: str, head: str, columns: Sequence[str], rows: Iterable[Sequence[str]],
-                   tail: Sequence[str] = ()) -> List[str]:
+                   tail: Sequence[str] = (), first: str = "Band") -> List[str]:
     """The lines of one section of a Markdown summary: '### name', the head line, a table with a right-aligned column per
-    entry of columns, and the tail lines, each part followed by an empty line."""
-    table = ["| Band | " + " | ".join(columns) + " |", "|---|" + "---:|" * len(columns)]
+    entry of columns, and the tail lines, each part followed by an empty line.  first: the heading of the rows' first cell."""
+    table = [f"| {first} | " + " | ".join(columns) + " |", "|---|" + "---:|" * len(columns)]
     table += ["| " + " | ".join(cells) + " |" for cells in rows]
     return [f"### {name}", "", head, "", *table, ""] + [line for t in tail for line in (t, "")]
 

@@ -48,6 +48,8 @@ SOURCES = {
     "ira_lundeby.hip": ["-ffp-contract=off"],
     # modulation transfer sums: compared only with themselves and to 1e-10 with a long-double restatement; FMAs wanted
     "ira_mtf.hip": [],
+    # a harmonic segment sample is one float64 product rounded once to float32, bit for bit NumPy's
+    "ira_harmonics.hip": ["-ffp-contract=off"],
 }
 COMMON = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function"]
 

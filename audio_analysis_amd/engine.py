@@ -690,6 +690,68 @@ class Engine:
                                     _ptr(out), self.stream), "ira_mtf_sums")
         return out[: nseg * nrec].view(nseg, nrec)
 
+    # ------------------------------------------------------------------ harmonic distortion from a deconvolved sweep
+    def harmonic_peaks(self, h_dev, h_off: np.ndarray, n_search: np.ndarray):
+        """The linear peak of circular responses: the first maximum of |h| over the first n_search[c] samples of channel c
+        (ira_peak_index on a view of h; nothing returns to the host).  Returns (peak int64 device, |h[peak]| float32
+        device), one entry per channel."""
+        h_off = np.ascontiguousarray(h_off, dtype=np.int64)
+        n_search = np.ascontiguousarray(n_search, dtype=np.int64)
+        n = int(h_off.size)
+        if n_search.shape != (n,) or (n and n_search.min() < 1):
+            raise ValueError("n_search must hold one length >= 1 per channel")
+        d_off, d_len = self.job_tables(h_off, n_search)
+        pk, pa = self._peak_pick(h_dev, d_off, d_len, n, int(n_search.max()) if n else 0)
+        return pk[:n], pa[:n]
+
+    def harmonic_windows(self, h_dev, h_off: np.ndarray, n_fft: np.ndarray, peak_dev, lags: np.ndarray, guard: int,
+                         window: np.ndarray):
+        """Windowed harmonic segments (ira_harmonic_windows).  Channel c: the circular response of n_fft[c] samples at
+        h_off[c] of h_dev, peak_dev[c] its linear peak on the device; lags (K,) int64 samples; window (seg,) float64.
+        Returns (nch * K, seg) float32 device, row c * K + k:
+        float32(float64(h_c[(peak - lags[k] - guard + i) mod n_fft[c]]) * window[i])."""
+        t = self.torch
+        h_off = np.ascontiguousarray(h_off, dtype=np.int64)
+        n_fft = np.ascontiguousarray(n_fft, dtype=np.int32)
+        lags = np.ascontiguousarray(lags, dtype=np.int64).reshape(-1)
+        window = np.ascontiguousarray(window, dtype=np.float64).reshape(-1)
+        nch, k, seg, guard = int(h_off.size), int(lags.size), int(window.size), int(guard)
+        if n_fft.shape != (nch,) or (nch and n_fft.min() < 1):
+            raise ValueError("n_fft must hold one length >= 1 per channel")
+        if not (1 <= guard < seg):
+            raise ValueError("guard must be at least 1 sample and the window longer than it")
+        out = self.empty(nch * k * seg, t.float32)
+        if nch:
+            d_off, d_n, d_lag, d_win = self.job_tables(h_off, n_fft, lags, window)
+            check(self.lib.ira_harmonic_windows(_ptr(h_dev), _ptr(d_off), _ptr(d_n), _ptr(peak_dev), _ptr(d_lag),
+                                                _ptr(d_win), nch, k, guard, seg, _ptr(out), self.stream),
+                  "ira_harmonic_windows")
+        return out[: nch * k * seg].view(nch * k, seg)
+
+    def harmonic_band_powers(self, spec_dev, spec_off: np.ndarray, lo: np.ndarray, cnt: np.ndarray, nbins: int):
+        """Mean band powers of half spectra (ira_harmonic_band_powers).  Row r: nbins complex float64 values at spec_off[r]
+        (in complex values, as rfft_any returns them) of spec_dev; lo / cnt (K, J) int32, shared by every channel; row r
+        belongs to harmonic r % K.  Returns (nrow // K, K, J) float64 device: the mean of re^2 + im^2 over the bins
+        lo .. lo + cnt - 1, 0 where cnt = 0."""
+        t = self.torch
+        spec_off = np.ascontiguousarray(spec_off, dtype=np.int64)
+        lo = np.ascontiguousarray(lo, dtype=np.int32)
+        cnt = np.ascontiguousarray(cnt, dtype=np.int32)
+        nrow, nbins = int(spec_off.size), int(nbins)
+        if lo.ndim != 2 or lo.shape != cnt.shape or lo.size == 0:
+            raise ValueError("lo and cnt must be (K, J)")
+        k, j = lo.shape
+        if nrow % k:
+            raise ValueError("one spectrum per channel and harmonic: nrow must be a multiple of K")
+        if cnt.min() < 0 or lo.min() < 0 or int((lo.astype(np.int64) + cnt).max()) > nbins:
+            raise ValueError("every band must lie inside the half spectrum")
+        out = self.empty(nrow * j, t.float64)
+        if nrow:
+            d_so, d_lo, d_cnt = self.job_tables(spec_off, lo.reshape(-1), cnt.reshape(-1))
+            check(self.lib.ira_harmonic_band_powers(_ptr(spec_dev), _ptr(d_so), _ptr(d_lo), _ptr(d_cnt), nrow, k, j, nbins,
+                                                    _ptr(out), self.stream), "ira_harmonic_band_powers")
+        return out[: nrow * j].view(nrow // k, k, j)
+
     # ------------------------------------------------------------------ ISO 3382-1 noise handling (Lundeby)
     def lundeby_rows(self, base_off: np.ndarray, base_len: np.ndarray, chan_of_seg: np.ndarray, blk_size: np.ndarray,
                      nblk: np.ndarray, first_m: np.ndarray) -> Dict[str, object]:

@@ -33,7 +33,7 @@ extern "C" {
 #define IRA_E_FORMAT (-5)     /* a file is not RIFF/WAVE (host-side ingest entry points only) */
 #define IRA_E_HIP_BASE (-1000)
 
-#define IRA_ABI_VERSION 12  /* bumped whenever an exported signature or a scratch-size constant changes */
+#define IRA_ABI_VERSION 13  /* bumped whenever an exported signature or a scratch-size constant changes */
 
 int32_t ira_abi_version(void);
 const char* ira_error_string(int32_t code);
@@ -647,6 +647,32 @@ int32_t ira_edc_truncated(const float* x_dev, const int64_t* base_off_dev, const
 int64_t ira_mtf_scratch_doubles(int32_t nseg, int64_t max_len, int32_t nf);
 int32_t ira_mtf_sums(const float* x_dev, const int64_t* off_dev, const int64_t* len_dev, const double* w_dev, int32_t nseg,
                      int64_t max_len, int32_t nf, double* scratch_dev, double* out_dev, void* stream);
+
+/* ---- Harmonic distortion from a deconvolved logarithmic sweep: harmonic windows and their band powers -----------------
+ * Nothing in the reference reads the harmonic impulses its sweep deconvolution produces; both entry points replace nothing
+ * in the reference.  Host side, with the definitions pinned: audio_analysis_amd/analyse/harmonics.py
+ * (`python -m analyse.harmonics`).
+ * ira_harmonic_windows: channel c is the circular response of nfft_dev[c] float32 samples at h_dev + h_off_dev[c], p =
+ *   peak_dev[c] its linear peak as ira_peak_index wrote it (read on the device, no host round trip).  With the nharm
+ *   (1..IRA_HARMONIC_MAX) lags lag_dev[k] in samples and the float64 window window_dev[0 .. seg), row r = c * nharm + k is
+ *     out_dev[r * seg + i] = float32(float64(h_c[(p - lag[k] - guard + i) mod nfft_c]) * window[i]),  i < seg:
+ *   one float64 product, one rounding (bit-identical with NumPy).  Every index is reduced into the channel's buffer before
+ *   it is used, whatever the tables hold; a channel with nfft <= 0 gives rows of zeros.  1 <= guard < seg <= 2^21;
+ *   nch * nharm <= 65535.
+ * ira_harmonic_band_powers: row r is a half spectrum of nbins complex float64 values at spec_dev + 2 * spec_off_dev[r]
+ *   (offsets in complex values, as ira_rfft_any leaves them), k = r % nharm its harmonic.  With the tables lo_dev / cnt_dev
+ *   (nharm x nband, int32, shared by every channel), out_dev[r * nband + j] = the mean of re^2 + im^2 over the bins
+ *   lo[k][j] .. lo[k][j] + cnt[k][j] - 1; exactly 0 where cnt <= 0; NaN, without reading, where the bins leave [0, nbins).
+ *   One wave per band, float64 sums in an order that depends on the band's cnt alone (bit-identical whatever the batch or
+ *   the row's place in it); no atomics.  nrow a multiple of nharm, <= 65535; nband 1..4096; nbins 1..2^20 + 1.
+ * Neither needs scratch.  Argument errors are reported before anything is launched. */
+#define IRA_HARMONIC_MAX 10
+int32_t ira_harmonic_windows(const float* h_dev, const int64_t* h_off_dev, const int32_t* nfft_dev, const int64_t* peak_dev,
+                             const int64_t* lag_dev, const double* window_dev, int32_t nch, int32_t nharm, int32_t guard,
+                             int32_t seg, float* out_dev, void* stream);
+int32_t ira_harmonic_band_powers(const double* spec_dev, const int64_t* spec_off_dev, const int32_t* lo_dev,
+                                 const int32_t* cnt_dev, int32_t nrow, int32_t nharm, int32_t nband, int32_t nbins,
+                                 double* out_dev, void* stream);
 
 #ifdef __cplusplus
 }
