@@ -196,17 +196,19 @@ def rt60_bands_results(bands, values, have, sample_rate_hz: int, channel_names) 
     return out
 
 
-def band_signals_device(eng, batch, sample_rate_hz: int, band_settings: Rt60BandsAnalysisSettings, want_tiles: bool = False):
+def band_signals_device(eng, batch, sample_rate_hz: int, band_settings: Rt60BandsAnalysisSettings, want_tiles: bool = False,
+                        bands: Optional[Sequence[BandDefinition]] = None):
     """The filter bank for a device batch: one forward float64 rFFT of every full file, masked inverse transforms per band.
     Returns (bands, y float32 device, y_off (nch, nbands) int64): band b of channel c is batch.length[c] samples at
     y_off[c, b] of y, channel after channel, band after band.  want_tiles: a fourth element, what
-    Engine.band_irfft(want_tiles=True) returns (the partial energies of the band signals' EDC tiles, or None)."""
+    Engine.band_irfft(want_tiles=True) returns (the partial energies of the band signals' EDC tiles, or None).
+    bands: an explicit band list instead of the one band_settings.band_mode names (its transition width still applies)."""
     t = eng.torch
     nch = batch.count
     n64 = batch.length.astype(np.int64)
     if np.any(n64 < 8):
         raise ValueError("Not enough samples for band analysis.")
-    bands = _build_band_definitions(band_settings, sample_rate_hz)
+    bands = _build_band_definitions(band_settings, sample_rate_hz) if bands is None else list(bands)
     nb = len(bands)
     if nb == 0:
         return (bands, None, np.zeros((nch, 0), dtype=np.int64)) + ((None,) if want_tiles else ())

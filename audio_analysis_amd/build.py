@@ -50,6 +50,8 @@ SOURCES = {
     "ira_mtf.hip": [],
     # a harmonic segment sample is one float64 product rounded once to float32, bit for bit NumPy's
     "ira_harmonics.hip": ["-ffp-contract=off"],
+    # float64 running sums of |p|^n and their ratios round one operation at a time, like NumPy's
+    "ira_echo.hip": ["-ffp-contract=off"],
 }
 COMMON = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function"]
 

@@ -41,6 +41,11 @@ LUNDEBY_DOUBLES = 16          # IRA_LUNDEBY_DOUBLES
 LUNDEBY_MAX_BLOCKS = 4096     # IRA_LUNDEBY_MAX_BLOCKS
 LUNDEBY_STAGE = 4096          # samples a workgroup of the two sample passes stages; the largest block size
 LUNDEBY_MAX_LEN = 2047 * 4096
+ECHO_DOUBLES = 8              # IRA_ECHO_DOUBLES
+ECHO_CHUNK = 4096             # IRA_ECHO_CHUNK: samples per workgroup of the two sample passes, counted from the onset
+ECHO_MAX_LAG = 2048           # IRA_ECHO_MAX_LAG: the largest D (the halo the emit pass keeps of the chunk in front)
+ECHO_MAX_PARAMS = 16          # IRA_ECHO_MAX_PARAMS
+ECHO_PARAM_DOUBLES = 8        # IRA_ECHO_PARAM_DOUBLES
 
 
 def lundeby_layout(base_off, base_len, chan_of_seg, blk_size, nblk, first_m) -> Dict[str, object]:
@@ -105,7 +110,7 @@ class _TimedLib:
     time can be read back after a synchronise (bench.py's roofline uses this).
     """
     _PLAIN = {"ira_error_string", "ira_abi_version", "ira_ar_partial_doubles", "ira_ar_exact_doubles",
-              "ira_energy_scratch_doubles", "ira_xcorr_scratch_doubles"}
+              "ira_energy_scratch_doubles", "ira_xcorr_scratch_doubles", "ira_echo_scratch_doubles"}
 
     def __init__(self, lib, eng):
         self._lib, self._eng, self._cache = lib, eng, {}
@@ -630,6 +635,54 @@ class Engine:
                                           max_len, _ptr(d_lim), nlim, _ptr(scratch), _ptr(out), self.stream),
               "ira_energy_windows")
         return out[: nseg * (nlim + 2)].view(nseg, nlim + 2)
+
+    # ------------------------------------------------------------------ Dietsch-Kraak echo criterion
+    # A/B: True lets the first sample pass of ira_echo_criterion leave s = |y|^n behind as float64 for the second pass to
+    # read back (8 bytes written and 16 read per sample) instead of forming it again (both times); the
+    # results are the same to the bit.
+    echo_stash = False
+
+    def echo_criterion(self, x_dev, base_off: np.ndarray, base_len: np.ndarray, chan_of_seg: np.ndarray, onset_dev,
+                       params: np.ndarray, param_of_seg: np.ndarray):
+        """Echo criterion records and curves (ira_echo_criterion).  Segment j: the samples from base_off[j] + o of x_dev,
+        o = onset_dev[chan_of_seg[j]], L = base_len[j] - o; its parameters are row param_of_seg[j] of params (nparam, 8)
+        float64: exponent n, D, G, Mmax, S (samples per curve step, 0 = none), threshold_10, threshold_50, fs.
+        Returns (records (nseg, 8) float64 device: EK_max, its first index, the first indices at or above the two
+        thresholds (-1 = none), ts[M-1], W[M-1], M, V[M-1]; curve (nseg, ncurve) float32 device: the maximum of EK per
+        step, NaN past a segment's range, ncurve = 0 when no row asks for a curve)."""
+        t = self.torch
+        base_off = np.ascontiguousarray(base_off, dtype=np.int64)
+        base_len = np.ascontiguousarray(base_len, dtype=np.int64)
+        param_of_seg = np.ascontiguousarray(param_of_seg, dtype=np.int32)
+        params = np.ascontiguousarray(params, dtype=np.float64)
+        nseg = int(base_off.size)
+        if params.ndim != 2 or params.shape[1] != ECHO_PARAM_DOUBLES or not 1 <= params.shape[0] <= ECHO_MAX_PARAMS:
+            raise ValueError(f"params must be (1..{ECHO_MAX_PARAMS}, {ECHO_PARAM_DOUBLES})")
+        if base_len.size != nseg or param_of_seg.size != nseg or len(chan_of_seg) != nseg:
+            raise ValueError("base_off, base_len, chan_of_seg and param_of_seg must be (nseg,)")
+        if nseg and (param_of_seg.min() < 0 or param_of_seg.max() >= params.shape[0]):
+            raise ValueError("param_of_seg must index params")
+        # M <= min(base_len - G, Mmax) whatever the onset: this bound sizes the grid, the scratch and the curve
+        with np.errstate(invalid="ignore"):
+            m_up = np.clip(np.minimum(base_len - params[param_of_seg, 2], params[param_of_seg, 3]), 0, None) if nseg else np.zeros(0)
+            step = params[param_of_seg, 4] if nseg else np.zeros(0)
+            steps = np.where(step > 0, np.ceil(m_up / np.where(step > 0, step, 1.0)), 0.0)
+        max_len = int(np.nan_to_num(m_up).max()) if nseg else 0
+        ncurve = int(np.nan_to_num(steps).max()) if nseg else 0
+        nsc = int(self.lib.ira_echo_scratch_doubles(nseg, max_len))
+        check(min(nsc, 0), "ira_echo_scratch_doubles")
+        scratch = self.empty(nsc, t.float64)
+        stash = self.empty(nseg * (-(-max_len // ECHO_CHUNK)) * ECHO_CHUNK, t.float64) if self.echo_stash else None
+        rec = self.empty(nseg * ECHO_DOUBLES, t.float64)
+        curve = self.empty(nseg * ncurve, t.float32)
+        d_off, d_len, d_ch, d_par = self.job_tables(base_off, base_len, np.ascontiguousarray(chan_of_seg, np.int32),
+                                                    param_of_seg)
+        with self.tagged("[stash]" if self.echo_stash else self.event_tag):
+            check(self.lib.ira_echo_criterion(_ptr(x_dev), _ptr(d_off), _ptr(d_len), _ptr(d_ch), _ptr(d_par),
+                                              _ptr(onset_dev), nseg, max_len, _lib.dbl_array(params.reshape(-1)),
+                                              int(params.shape[0]), ncurve, _ptr(scratch),
+                                              _ptr(stash), _ptr(rec), _ptr(curve), self.stream), "ira_echo_criterion")
+        return rec[: nseg * ECHO_DOUBLES].view(nseg, ECHO_DOUBLES), curve[: nseg * ncurve].view(nseg, ncurve)
 
     # ------------------------------------------------------------------ ISO 3382-1 inter-channel cross-correlation
     def xcorr_windows(self, x_dev, l_off: np.ndarray, r_off: np.ndarray, seg_len: np.ndarray, lchan_of_seg: np.ndarray,

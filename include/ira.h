@@ -33,7 +33,7 @@ extern "C" {
 #define IRA_E_FORMAT (-5)     /* a file is not RIFF/WAVE (host-side ingest entry points only) */
 #define IRA_E_HIP_BASE (-1000)
 
-#define IRA_ABI_VERSION 13  /* bumped whenever an exported signature or a scratch-size constant changes */
+#define IRA_ABI_VERSION 14  /* bumped whenever an exported signature or a scratch-size constant changes */
 
 int32_t ira_abi_version(void);
 const char* ira_error_string(int32_t code);
@@ -673,6 +673,45 @@ int32_t ira_harmonic_windows(const float* h_dev, const int64_t* h_off_dev, const
 int32_t ira_harmonic_band_powers(const double* spec_dev, const int64_t* spec_off_dev, const int32_t* lo_dev,
                                  const int32_t* cnt_dev, int32_t nrow, int32_t nharm, int32_t nband, int32_t nbins,
                                  double* out_dev, void* stream);
+
+/* ---- Dietsch-Kraak echo criterion EK: running centre time of |p|^n, lagged difference, maximum, crossings, curve -------
+ * Nothing in the reference computes an echo criterion; both entry points replace no reference function.  Host side, with
+ * the definition pinned: audio_analysis_amd/analyse/echo.py (`python -m analyse.echo`).
+ * ira_echo_criterion: segment j is one (channel, criterion) row: the float32 samples at x_dev + base_off_dev[j] + o, o =
+ *   onset_dev[chan_of_seg_dev[j]] read on the device (band rows of a channel share its broadband onset; no host round
+ *   trip), L = base_len_dev[j] - o, m counted from o.  Its parameter set is row p = param_of_seg_dev[j] of the HOST array
+ *   params (nparam rows, 1..IRA_ECHO_MAX_PARAMS, of IRA_ECHO_PARAM_DOUBLES doubles; a host array so that its values are
+ *   checked before anything is launched; rows of different sample rates are different sets):
+ *     [0] exponent n (finite, > 0)  [1] D samples (1..IRA_ECHO_MAX_LAG)  [2] G samples (>= 0)  [3] Mmax (0..2^31)
+ *     [4] S, samples per curve step (0: no curve for these rows)  [5] threshold_10  [6] threshold_50 (finite)
+ *     [7] fs in Hz (finite, > 0).  [1]..[4] are whole numbers.
+ *   With s[m] = float64(|y[m]|)^n (fabs for n = 1, a product for 2, sqrt for 0.5, pow otherwise; 0 for a zero sample),
+ *   W[m] = s[0] + .. + s[m], V[m] = 0 s[0] + .. + m s[m], ts[m] = V[m] / (fs W[m]) (0 where W[m] = 0 and for m < 0),
+ *   EK[m] = (ts[m] - ts[m - D]) / (D / fs) for m < M = min(L - G, Mmax), formed on the device from the onset,
+ *   rec_dev[j * IRA_ECHO_DOUBLES + ..] = [0] max EK  [1] the first index of the maximum  [2] the first m with EK >=
+ *   threshold_10, -1 for none  [3] the same for threshold_50  [4] ts[M - 1]  [5] W[M - 1]  [6] M (as defined: it may be
+ *   <= 0)  [7] V[M - 1];  with M <= 0: [NaN, -1, -1, -1, NaN, 0, M, 0].
+ *   ncurve > 0: curve_dev[j * ncurve + k] = float32(max EK[k S .. min((k + 1) S, M) - 1]), NaN for k S >= M and in rows
+ *   with S = 0.  ncurve = 0: no curve, curve_dev may be NULL.
+ *   Nothing at or after sample M of a row is read.  Float64 sums in chunks of IRA_ECHO_CHUNK samples counted from the
+ *   onset, in an order that depends on the row's own onset, length and parameters alone; the only atomics are an
+ *   integer minimum (first crossings) and an integer maximum (curve), which do not depend on arrival order: a row's
+ *   record and curve are bit-identical whatever the batch, the row's place in it or its alignment.
+ *   max_len >= every row's M (it sizes the grid and the scratch; <= 2^31); nseg <= 65535; scratch_dev holds as many
+ *   doubles as the size call returns for (nseg, max_len) (IRA_E_SIZE, negative, for arguments out of range; host only).
+ *   stash_dev: NULL, and the second sample pass forms s again from the samples; or nseg * ceil(max_len /
+ *   IRA_ECHO_CHUNK) * IRA_ECHO_CHUNK doubles, and the first pass leaves s there for the second to read back (same
+ *   results to the bit; DESIGN.md 4.12 has both times).  Argument errors are reported before anything is launched. */
+#define IRA_ECHO_DOUBLES 8
+#define IRA_ECHO_CHUNK 4096
+#define IRA_ECHO_MAX_LAG 2048      /* halo capacity: 14 ms at 96 kHz is 1344 samples */
+#define IRA_ECHO_MAX_PARAMS 16
+#define IRA_ECHO_PARAM_DOUBLES 8
+int64_t ira_echo_scratch_doubles(int32_t nseg, int64_t max_len);
+int32_t ira_echo_criterion(const float* x_dev, const int64_t* base_off_dev, const int64_t* base_len_dev,
+                           const int32_t* chan_of_seg_dev, const int32_t* param_of_seg_dev, const int64_t* onset_dev,
+                           int32_t nseg, int64_t max_len, const double* params, int32_t nparam, int64_t ncurve,
+                           double* scratch_dev, double* stash_dev, double* rec_dev, float* curve_dev, void* stream);
 
 #ifdef __cplusplus
 }
