@@ -61,13 +61,41 @@ def _expected_gaussian_abs_exceedance(threshold_rms: float) -> float:
     return 2.0 * (1.0 - phi)
 
 
-def window_geometry(sample_rate_hz: int, settings: DiffusionAnalysisSettings) -> Tuple[int, int, int]:
-    """(win, hop, max_lag) in samples (reference diffusion.py:246-258)."""
+MAX_WINDOW_SAMPLES = 8192
+MAX_LAG_SAMPLES = 4096
+# What a workgroup of ira_diffusion.hip stages in LDS: per channel a float64 copy of the window behind a zero halo of
+# max_lag + 9 values, the lag partials (9 lags per thread, at least 256 threads' worth), and one float32 copy of the window.
+LDS_LIMIT_BYTES = 150 * 1024
+_LAGS_PER_THREAD = 9
+_THREADS = 256
+
+
+def diffusion_lds_bytes(win: int, max_lag: int, stereo: bool) -> int:
+    """Dynamic LDS of one workgroup of the mono (one staged channel) or the stereo kernel (two)."""
+    groups = -(-(2 * max_lag + 1) // _LAGS_PER_THREAD)
+    partials = _LAGS_PER_THREAD * max(_THREADS, groups)
+    return 8 * ((2 if stereo else 1) * (max_lag + _LAGS_PER_THREAD + win) + partials) + 4 * win
+
+
+def max_window_samples(max_lag: int, stereo: bool) -> int:
+    """Longest window the mono or the stereo kernel takes at this lag range (0: none)."""
+    room = LDS_LIMIT_BYTES - diffusion_lds_bytes(0, max_lag, stereo)
+    return max(0, min(MAX_WINDOW_SAMPLES, room // (20 if stereo else 12)))
+
+
+def window_geometry(sample_rate_hz: int, settings: DiffusionAnalysisSettings, stereo: bool = False
+                    ) -> Tuple[int, int, int]:
+    """(win, hop, max_lag) in samples (reference diffusion.py:246-258), checked against what the mono kernel -- with
+    stereo=True the stereo kernel -- can stage, before any device work."""
     win = max(16, int(round(settings.window_seconds * float(sample_rate_hz))))
     hop = max(1, int(round(settings.hop_seconds * float(sample_rate_hz))))
     max_lag = max(1, int(round((settings.max_lag_milliseconds / 1000.0) * float(sample_rate_hz))))
-    if win > 8192 or max_lag > 4096:
-        raise ValueError("diffusion windows are limited to 8192 samples and lags to 4096 samples on the GPU path.")
+    if max_lag > MAX_LAG_SAMPLES:
+        raise ValueError(f"diffusion lags are limited to {MAX_LAG_SAMPLES} samples on the GPU path ({max_lag} asked for).")
+    limit = max_window_samples(max_lag, stereo)
+    if win > limit:
+        raise ValueError(f"diffusion windows are limited to {limit} samples at a lag range of {max_lag} samples for "
+                         f"{'stereo pairs' if stereo else 'single channels'} on the GPU path ({win} asked for).")
     return win, hop, max_lag
 
 
@@ -130,8 +158,8 @@ def analyse_diffusion_for_channel(samples: np.ndarray, sample_rate_hz: int, chan
 def stereo_series(left: np.ndarray, right: np.ndarray, sample_rate_hz: int, settings: DiffusionAnalysisSettings
                   ) -> Tuple[np.ndarray, np.ndarray]:
     """corr0 and IACC max per window; both channels start at the peak of their float32 MEAN (diffusion.py:323-358)."""
+    win, hop, max_lag = window_geometry(sample_rate_hz, settings, stereo=True)
     eng = get_engine()
-    win, hop, max_lag = window_geometry(sample_rate_hz, settings)
     comb = ((left.astype(np.float64) + right.astype(np.float64)) * 0.5).astype(np.float32)
     peak = int(np.argmax(np.abs(comb.astype(np.float64)))) if settings.trim_to_peak else 0
     start = trim_start(int(comb.size), peak, sample_rate_hz, settings)
@@ -151,7 +179,7 @@ def stereo_series_device(eng, split_batch, left_index: Sequence[int], mix_peaks:
     right channel the next one; mix_peaks[j] = argmax|0.5*(L+R)| of that file (reference diffusion.py:326-335).  One
     launch for all files.
     """
-    win, hop, max_lag = window_geometry(sample_rate_hz, settings)
+    win, hop, max_lag = window_geometry(sample_rate_hz, settings, stereo=True)
     li = np.asarray(left_index, dtype=np.int64)
     n = split_batch.length[li]
     starts = np.array([trim_start(int(n[j]), int(mix_peaks[j]) if settings.trim_to_peak else 0, sample_rate_hz, settings)
@@ -175,8 +203,10 @@ def analyse_diffusion_from_wav_file(input_wav_file_path: str | Path,
                                     ) -> List[DiffusionChannelResult]:
     settings = settings or DiffusionAnalysisSettings()
     loaded, chans = wav_channels(input_wav_file_path, settings.use_mono_downmix_for_stereo)
+    stereo = (not settings.use_mono_downmix_for_stereo) and len(chans) == 2
+    window_geometry(loaded.sample_rate_hz, settings, stereo=stereo)         # a window the stereo pass cannot take: fail now
     results = analyse_diffusion_batch([c for _, c in chans], loaded.sample_rate_hz, [n for n, _ in chans], settings)
-    if (not settings.use_mono_downmix_for_stereo) and len(chans) == 2:
+    if stereo:
         corr0, iacc = stereo_series(chans[0][1], chans[1][1], loaded.sample_rate_hz, settings)
         results = [DiffusionChannelResult(
             channel_name=r.channel_name, sample_rate_hz=r.sample_rate_hz,

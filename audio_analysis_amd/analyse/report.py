@@ -352,6 +352,9 @@ def run_reports_batched(
         s = _apply_common_overrides(settings.diffusion_analysis_settings
                                     or DiffusionAnalysisSettings(hop_seconds=0.05, max_lag_milliseconds=5.0), settings)
         d_names, d_batch, d_labels = view(s.use_mono_downmix_for_stereo)
+        per_file = [sum(1 for i, _ in d_labels if i == f) for f in range(nf)]
+        if not s.use_mono_downmix_for_stereo and 2 in per_file:
+            _diff.window_geometry(sr, s, stereo=True)       # a window the stereo pass cannot take fails before the mono pass
         res = _diff.diffusion_results(_diff.diffusion_device(eng, d_batch, sr, s), sr, d_names)
         grouped = _group(res, d_labels, nf)
         if not s.use_mono_downmix_for_stereo:
