@@ -13,7 +13,7 @@ _LIB_PATH = Path(__file__).resolve().parent / "csrc" / "libira.so"
 _lib = None
 # must equal IRA_ABI_VERSION of include/ira.h: a stale .so called with this file's prototypes would read shifted
 # arguments or undersized scratch (memory corruption on the GPU instead of a clean error)
-ABI_VERSION = 14
+ABI_VERSION = 15
 
 c_f32p = C.c_void_p
 c_i64p = C.c_void_p
@@ -92,6 +92,8 @@ PROTOTYPES = {
     "ira_harmonic_band_powers": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]),
     "ira_echo_scratch_doubles": (C.c_int64, [i32, C.c_int64]),
     "ira_echo_criterion": (i32, [vp, vp, vp, vp, vp, vp, i32, C.c_int64, C.POINTER(f64), i32, C.c_int64, vp, vp, vp, vp, vp]),
+    "ira_xspec_accumulate": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp]),
+    "ira_xspec_finish": (i32, [vp, vp, i32, i32, i32, i32, vp, vp]),
 }
 
 

@@ -46,6 +46,15 @@ ECHO_CHUNK = 4096             # IRA_ECHO_CHUNK: samples per workgroup of the two
 ECHO_MAX_LAG = 2048           # IRA_ECHO_MAX_LAG: the largest D (the halo the emit pass keeps of the chunk in front)
 ECHO_MAX_PARAMS = 16          # IRA_ECHO_MAX_PARAMS
 ECHO_PARAM_DOUBLES = 8        # IRA_ECHO_PARAM_DOUBLES
+XSPEC_FRAMES = 16             # IRA_XSPEC_FRAMES: frames a workgroup of ira_xspec_accumulate sums before it writes
+XSPEC_ROWS = 11               # IRA_XSPEC_ROWS
+XSPEC_MIN_FFT, XSPEC_MAX_FFT = 256, 8192
+
+
+def xspec_frames(n, n_fft: int, hop: int) -> np.ndarray:
+    """K = 1 + (n - n_fft) // hop frames of n samples, 0 when n < n_fft (int64, elementwise)."""
+    n = np.asarray(n, dtype=np.int64)
+    return np.where(n >= n_fft, 1 + (n - n_fft) // hop, 0).astype(np.int64)
 
 
 def lundeby_layout(base_off, base_len, chan_of_seg, blk_size, nblk, first_m) -> Dict[str, object]:
@@ -683,6 +692,50 @@ class Engine:
                                               int(params.shape[0]), ncurve, _ptr(scratch),
                                               _ptr(stash), _ptr(rec), _ptr(curve), self.stream), "ira_echo_criterion")
         return rec[: nseg * ECHO_DOUBLES].view(nseg, ECHO_DOUBLES), curve[: nseg * ncurve].view(nseg, ncurve)
+
+    # ------------------------------------------------------------------ dual-channel spectral sums (Welch H1 / H2)
+    def cross_spectra(self, x_dev, x_off: np.ndarray, y_off: np.ndarray, n: np.ndarray, n_fft: int, hop: int,
+                      use_hann: bool):
+        """Auto- and cross-spectra of (reference, measurement) pairs summed over overlapping frames, and what follows from
+        them (ira_xspec_accumulate, ira_xspec_finish).  Pair p: reference n[p] samples at x_off[p] of x_dev, measurement
+        n[p] samples at y_off[p] (the pair's delay is in the offsets); K = 1 + (n[p] - n_fft) // hop frames, none when
+        n[p] < n_fft.  The window is window(n_fft, use_hann, 64).  Returns (npairs, XSPEC_ROWS, n_fft // 2 + 1) float64
+        device: Sxx, Syy, Re Sxy, Im Sxy, H1 (re, im), H2 (re, im), coherence, 20 log10 |H1|, phase."""
+        t = self.torch
+        x_off = np.ascontiguousarray(x_off, dtype=np.int64).reshape(-1)
+        y_off = np.ascontiguousarray(y_off, dtype=np.int64).reshape(-1)
+        n = np.ascontiguousarray(n, dtype=np.int64).reshape(-1)
+        n_fft, hop = int(n_fft), int(hop)
+        npairs = int(x_off.size)
+        if y_off.size != npairs or n.size != npairs:
+            raise ValueError("x_off, y_off and n must be (npairs,)")
+        if n_fft < XSPEC_MIN_FFT or n_fft > XSPEC_MAX_FFT or n_fft & (n_fft - 1):
+            raise ValueError(f"n_fft must be a power of two from {XSPEC_MIN_FFT} to {XSPEC_MAX_FFT}, got {n_fft}")
+        if not 1 <= hop <= n_fft:
+            raise ValueError(f"hop must be 1 .. n_fft, got {hop}")
+        if npairs > 65535:
+            raise ValueError("at most 65535 pairs per launch")
+        total = int(x_dev.numel())
+        if npairs and (n.min() < 0 or min(x_off.min(), y_off.min()) < 0 or max((x_off + n).max(), (y_off + n).max()) > total):
+            raise ValueError("a pair's rows must lie inside x_dev")
+        nbins = n_fft // 2 + 1
+        if npairs == 0:                                         # nothing to launch (zero-size tables have no address)
+            return self.empty(0, t.float64)[:0].view(0, XSPEC_ROWS, nbins)
+        max_frames = int(xspec_frames(n, n_fft, hop).max())
+        if max_frames >= 1 << 31:
+            raise ValueError("too many frames for one launch")
+        chunks = -(-max_frames // XSPEC_FRAMES)
+        partial = self.empty(npairs * chunks * 4 * nbins, t.float64)
+        out = self.empty(npairs * XSPEC_ROWS * nbins, t.float64)
+        win, tw = self.window(n_fft, use_hann, 64), self.twiddle(n_fft, 64)
+        d_xo, d_yo, d_n = self.job_tables(x_off, y_off, n)
+        with self.tagged(f"[{n_fft}]"):
+            check(self.lib.ira_xspec_accumulate(_ptr(x_dev), _ptr(d_xo), _ptr(d_yo), _ptr(d_n), npairs, max_frames, n_fft,
+                                                hop, _ptr(win), _ptr(tw), _ptr(partial), self.stream),
+                  "ira_xspec_accumulate")
+            check(self.lib.ira_xspec_finish(_ptr(partial), _ptr(d_n), npairs, max_frames, n_fft, hop, _ptr(out),
+                                            self.stream), "ira_xspec_finish")
+        return out[: npairs * XSPEC_ROWS * nbins].view(npairs, XSPEC_ROWS, nbins)
 
     # ------------------------------------------------------------------ ISO 3382-1 inter-channel cross-correlation
     def xcorr_windows(self, x_dev, l_off: np.ndarray, r_off: np.ndarray, seg_len: np.ndarray, lchan_of_seg: np.ndarray,
@@ -1528,9 +1581,11 @@ class Engine:
                                          int(n_out.max()) if n else 0, 1 if remove_dc else 0, 1 if normalise_peak else 0,
                                          float(target_peak), _ptr(mean), _ptr(peak), self.stream), "ira_deconv_finish")
 
-    def segment_peaks(self, x_dev, off: np.ndarray, lens: np.ndarray):
-        """max|x| (float32 values as float64) of arbitrary segments."""
+    def segment_peaks(self, x_dev, off: np.ndarray, lens: np.ndarray, with_index: bool = False):
+        """max|x| (float32 values as float64) of arbitrary segments; with_index: (values, argmax|x| int64, the first
+        maximum of a segment)."""
         n = int(off.size)
         d_o, d_l = self.job_tables(np.ascontiguousarray(off, np.int64), np.ascontiguousarray(lens, np.int64))
-        _, pa = self._peak_pick(x_dev, d_o, d_l, n, int(np.max(lens)) if n else 0)
-        return pa.cpu().numpy()[:n].astype(np.float64)
+        pk, pa = self._peak_pick(x_dev, d_o, d_l, n, int(np.max(lens)) if n else 0)
+        values = pa.cpu().numpy()[:n].astype(np.float64)
+        return (values, pk.cpu().numpy()[:n].astype(np.int64)) if with_index else values

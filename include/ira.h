@@ -33,7 +33,7 @@ extern "C" {
 #define IRA_E_FORMAT (-5)     /* a file is not RIFF/WAVE (host-side ingest entry points only) */
 #define IRA_E_HIP_BASE (-1000)
 
-#define IRA_ABI_VERSION 14  /* bumped whenever an exported signature or a scratch-size constant changes */
+#define IRA_ABI_VERSION 15  /* bumped whenever an exported signature or a scratch-size constant changes */
 
 int32_t ira_abi_version(void);
 const char* ira_error_string(int32_t code);
@@ -712,6 +712,37 @@ int32_t ira_echo_criterion(const float* x_dev, const int64_t* base_off_dev, cons
                            const int32_t* chan_of_seg_dev, const int32_t* param_of_seg_dev, const int64_t* onset_dev,
                            int32_t nseg, int64_t max_len, const double* params, int32_t nparam, int64_t ncurve,
                            double* scratch_dev, double* stash_dev, double* rec_dev, float* curve_dev, void* stream);
+
+/* ---- Dual-channel spectral sums (Welch): auto- and cross-spectra over overlapping frames, H1 / H2, coherence -----------
+ * Nothing in the reference computes a transfer function from two channels; both entry points replace no reference
+ * function.  Host side, with the definitions pinned: audio_analysis_amd/analyse/transfer.py (`python -m
+ * analyse.transfer`).
+ * Pair p: reference x' = x_dev + x_off_dev[p], measurement y' = x_dev + y_off_dev[p] (float32; the pair's delay is
+ *   already in the two offsets), n_dev[p] samples of each.  n_fft a power of two 256 .. 8192, 1 <= hop <= n_fft,
+ *   K = 1 + (n_dev[p] - n_fft) / hop frames (0 when n_dev[p] < n_fft), frame f at f * hop, no padding, no detrending.
+ *   window_dev: n_fft doubles; twiddle_dev: exp(-2 pi i k / n_fft), k < n_fft / 2, interleaved (re, im) doubles.
+ *   For bins k = 0 .. n_fft / 2, X_f = FFT(w x'_f), Y_f = FFT(w y'_f) in float64 (one complex transform carries both):
+ *     Sxx = sum_f |X_f|^2,  Syy = sum_f |Y_f|^2,  Sxy = sum_f conj(X_f) Y_f.
+ * ira_xspec_accumulate: grid (chunk of IRA_XSPEC_FRAMES frames, pair); a workgroup adds the frames of its chunk in
+ *   ascending order in registers and writes partial_dev[((p * chunks + c) * 4 + s) * nbins + k], s = Sxx, Syy, Re Sxy,
+ *   Im Sxy, nbins = n_fft / 2 + 1, chunks = ceil(max_frames / IRA_XSPEC_FRAMES), with plain stores (no atomics).  Chunks
+ *   at or past ceil(K / IRA_XSPEC_FRAMES) of a pair are not written, and nothing past a row's n_dev[p] samples is read.
+ *   The chunk size is a constant, so a pair's sums are the same bytes whatever else is in the batch.  A channel whose
+ *   windowed frame is all zeros contributes the spectrum 0 exactly (not the other channel's rounding error).
+ * ira_xspec_finish: one thread per (pair, bin) adds the pair's chunks in ascending order and writes out_dev[(p *
+ *   IRA_XSPEC_ROWS + r) * nbins + k], float64, r = 0 Sxx  1 Syy  2 Re Sxy  3 Im Sxy  4, 5 H1 = Sxy / Sxx (re, im)
+ *   6, 7 H2 = Syy / conj(Sxy) = Syy Sxy / |Sxy|^2 (re, im)  8 coherence = min(1, |Sxy|^2 / (Sxx Syy))
+ *   9 10 log10 |H1|^2 dB  10 atan2(Im Sxy, Re Sxy) radians.  A quotient whose denominator is 0 is NaN; each operation
+ *   rounds once (no contraction).  A pair without frames has zero sums.
+ * max_frames >= every pair's K (it sizes the grid and the partial array); npairs <= 65535.  NULL pointers: IRA_E_NULL;
+ * n_fft, hop or a count out of range: IRA_E_SIZE; both before anything is launched.  npairs = 0: IRA_OK, no launch. */
+#define IRA_XSPEC_FRAMES 16   /* frames per chunk: a constant, never sized from the batch or the device */
+#define IRA_XSPEC_ROWS 11
+int32_t ira_xspec_accumulate(const float* x_dev, const int64_t* x_off_dev, const int64_t* y_off_dev,
+                             const int64_t* n_dev, int32_t npairs, int32_t max_frames, int32_t n_fft, int32_t hop,
+                             const double* window_dev, const double* twiddle_dev, double* partial_dev, void* stream);
+int32_t ira_xspec_finish(const double* partial_dev, const int64_t* n_dev, int32_t npairs, int32_t max_frames,
+                         int32_t n_fft, int32_t hop, double* out_dev, void* stream);
 
 #ifdef __cplusplus
 }
