@@ -17,7 +17,9 @@ constexpr double kPi = 3.14159265358979323846;
 // hypot + log10; the float32 result is the same unless the float64 value lies within 1e-15 of a rounding tie), and the angle
 // through a 65-entry arctangent table: t = min / max of |re|, |im|, atan t = atan(k/64) + atan((t - k/64) / (1 + t k/64))
 // with the second term by its series to r^9 (|r| <= 1/128: next term < 1e-24), then the usual octant / sign fix-ups:
-// ~50 instructions instead of ~150, 1-2 ulp.  Zero, infinite and NaN operands take the library routines.  With both the
+// ~50 instructions instead of ~150; measured 2.05 ulp of the result at worst against a long-double atan2, the derived bound
+// (tests/spectrum_ref.py, phase_bound) is 5.3 half-ulps of its own roundings plus the library's error in the table entry.
+// Zero, tiny, huge, infinite and NaN operands take the library routines.  With both the
 // kernel is bound by its 28 bytes per bin instead of by the VALU (times: DESIGN.md section 4).
 constexpr int ATAN_TAB = 64;
 
@@ -28,7 +30,9 @@ __device__ __forceinline__ void build_atan_table(double* tab, int tid) {
 __device__ __forceinline__ double atan2_table(double y, double x, const double* tab) {
   const double ax = fabs(x), ay = fabs(y);
   const double mx = fmax(ax, ay), mn = fmin(ax, ay);
-  if (!(mx > 0.0 && mx < 1.0e300 && mn > 1.0e-300)) return atan2(y, x);        // zero / tiny / huge / infinite / NaN: library
+  // zero / tiny / huge / infinite / NaN: library.  Both parts are tested: fmax / fmin drop a NaN, so a bin with ONE NaN part
+  // used to pass as its other part twice and came out at +-pi/4 (its dB was NaN already)
+  if (!(ax > 1.0e-300 && ay > 1.0e-300 && ax < 1.0e300 && ay < 1.0e300)) return atan2(y, x);
   const double t = mn / mx;
   const int k = (int)(t * (double)ATAN_TAB + 0.5);
   const double t0 = (double)k * (1.0 / ATAN_TAB);
@@ -262,18 +266,19 @@ __global__ void gd_gradient_kernel(const double* __restrict__ phase, const int64
 // MSB-first radix select on the order-preserving uint64 image of the doubles, eight 8-bit digits, up to OS_MAX_RANKS
 // ranks per segment in one sweep: every pass histograms the next digit of the values that still match each rank's
 // prefix, then each rank descends into the bucket holding it.  One workgroup per segment; the data (<= a few MB)
-// stays in L2 across the eight passes.  -0.0 sorts before +0.0 and NaNs sort last (numpy would propagate NaN; group
-// delay has none).
+// stays in L2 across the eight passes.  -0.0 sorts before +0.0; every NaN, whatever its sign or payload, takes the top key
+// and so sorts last as numpy.sort has it, and a rank that lands on one returns the quiet NaN 0x7ff8000000000000.
 constexpr int OS_THREADS = 1024;
 constexpr int OS_MAX_RANKS = 8;
 
 __device__ __forceinline__ unsigned long long os_key(double v) {
   const unsigned long long u = (unsigned long long)__double_as_longlong(v);
+  if (v != v) return ~0ull;          // (the plain image put NaNs with the sign bit set, x86's default NaN among them, below -inf)
   return (u & 0x8000000000000000ull) ? ~u : (u | 0x8000000000000000ull);
 }
 __device__ __forceinline__ double os_unkey(unsigned long long k) {
   const unsigned long long u = (k & 0x8000000000000000ull) ? (k & 0x7fffffffffffffffull) : ~k;
-  return __longlong_as_double((long long)u);
+  return __longlong_as_double((long long)(k == ~0ull ? 0x7ff8000000000000ull : u));
 }
 
 // Round 4: once the buckets that hold the wanted ranks are small (after two digits as a rule: a few hundred values of
@@ -500,6 +505,7 @@ __global__ __launch_bounds__(ST_THREADS) void stats_kernel(const float* __restri
         const float db = dbv[u];
         uint32_t uu = __float_as_uint(db);
         uu = (uu & 0x80000000u) ? ~uu : (uu | 0x80000000u);  // monotone map float -> uint
+        if (db != db) uu = 0xFFFFFFFFu;                      // numpy.argmax: the first NaN wins, whatever its sign or payload
         const unsigned long long key = ((unsigned long long)uu << 32) | (unsigned long long)(0xFFFFFFFFu - (uint32_t)k);
         best = key > best ? key : best;
         // 10^(dB/20): table-driven (ira_log.h) for finite values in the table's range -- the float64 exp10 was 70 of this
