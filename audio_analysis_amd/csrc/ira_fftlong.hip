@@ -310,14 +310,15 @@ __device__ __forceinline__ cd value_input(const Jobs& J, const Ctx& c, unsigned 
     // Hermitian extension of X * (m1 + i m2); the inverse DFT is conj(DFT(conj(.)))/L, so feed conj(W) * chirp
     const bool upper = n > L / 2;
     const unsigned k = upper ? L - n : n;
-    const cd xk = {r.a, upper ? -r.b : r.b};
+    const bool self = k == 0u || 2u * k == L;          // bin 0 / Nyquist: imaginary parts ignored, like numpy.fft.irfft
+    const cd xk = {r.a, self ? 0.0 : (upper ? -r.b : r.b)};
     const double m1 = (double)ira::mask_cut(c.b1, c.k1, (int)k, c.fv);
     const double m2 = (double)ira::mask_cut(c.b2, c.k2, (int)k, c.fv);
     cd wk;
     if (!c.two) {
       wk = ira::cmul(xk, cd{m1, m2});
     } else {                                        // X1 m1 + i X2 m2: band 1 of one channel, band 2 of another
-      const cd x2 = {r.c, upper ? -r.d : r.d};
+      const cd x2 = {r.c, self ? 0.0 : (upper ? -r.d : r.d)};
       wk = {xk.re * m1 - x2.im * m2, xk.im * m1 + x2.re * m2};
     }
     const cd cw = {wk.re, -wk.im};

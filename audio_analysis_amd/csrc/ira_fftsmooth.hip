@@ -455,7 +455,9 @@ __device__ __forceinline__ cd smooth_value(const SmoothPlan& P, const SJobs& J, 
     //   y[2 m] + i y[2 m + 1] = IDFT_n(Z)[m]        (inverse = conj(DFT(conj .)) / n: feed conj(Z))
     const double ma = (double)ira::mask_cut(c.b1, c.k1, i, c.fv);
     const double mb = (double)ira::mask_cut(c.b1, c.k1, n - i, c.fv);
-    const cd xa = {r.a * ma, r.b * ma}, xb = {r.c * mb, -r.d * mb};            // Xm[i], conj Xm[n - i]
+    // (i = 0 pairs bin 0 with the Nyquist bin n: a real signal's inverse ignores both imaginary parts, like numpy.fft.irfft)
+    const double ia = i == 0 ? 0.0 : r.b, ib = i == 0 ? 0.0 : r.d;
+    const cd xa = {r.a * ma, ia * ma}, xb = {r.c * mb, -ib * mb};              // Xm[i], conj Xm[n - i]
     const cd e = {0.5 * (xa.re + xb.re), 0.5 * (xa.im + xb.im)};
     const cd d = {0.5 * (xa.re - xb.re), 0.5 * (xa.im - xb.im)};
     const cd o = {cs * d.re - sn * d.im, cs * d.im + sn * d.re};                // W_2n^(-i) d
@@ -465,14 +467,15 @@ __device__ __forceinline__ cd smooth_value(const SmoothPlan& P, const SJobs& J, 
     // conj of the Hermitian extension of X1 m1 + i X2 m2  (inverse = conj(DFT(conj .)) / n)
     const bool upper = i > n / 2;
     const int k = upper ? n - i : i;
-    cd x1 = {r.a, upper ? -r.b : r.b};
+    const bool self = k == 0 || 2 * k == n;             // bin 0 / Nyquist: imaginary parts ignored, like numpy.fft.irfft
+    cd x1 = {r.a, self ? 0.0 : (upper ? -r.b : r.b)};
     const double m1 = (double)ira::mask_cut(c.b1, c.k1, k, c.fv);
     const double m2 = (double)ira::mask_cut(c.b2, c.k2, k, c.fv);
     cd w;
     if (!c.two) {
       w = ira::cmul(x1, cd{m1, m2});
     } else {
-      const cd x2 = {r.c, upper ? -r.d : r.d};
+      const cd x2 = {r.c, self ? 0.0 : (upper ? -r.d : r.d)};
       w = {x1.re * m1 - x2.im * m2, x1.im * m1 + x2.re * m2};
     }
     return {w.re, -w.im};

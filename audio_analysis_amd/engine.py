@@ -1199,6 +1199,9 @@ class Engine:
         Half spectra (complex f64) of x[xoff[e] : xoff[e]+L[e]] (* hanning) for every element.
         data_len / win_len (optional, per element): numpy.fft.rfft(x[:d] * hanning(w)[:d], n=L) -- d samples are read
         (d < L zero-pads, d > L truncates) under the Hann window of length w (reference group_delay.py:95-109).
+        NumPy defines that product for w >= d (and w = 1) only, and no caller passes another w; for 1 < w < d the window's
+        cosine 0.5 + 0.5 cos(pi (2 i + 1 - w) / (w - 1)) simply continues past i = w - 1 (w = 3: 0, 1, 0, 1, ...) -- not a
+        zero-extended window.  That is what the kernels do and what tests/longfft_ref.py states; w < 1 is invalid.
         Returns (spec float64 device viewed as (total_bins, 2), spec_off int64 host in complex elements, packed) -- always
         three values; the public wrappers are rfft_any (two) and rfft_any_packed (three).
         packed_ok: the caller's consumer is spectrum_mag_phase(packed=...) -- even-length elements that ride a half-length
