@@ -46,6 +46,13 @@ ECHO_CHUNK = 4096             # IRA_ECHO_CHUNK: samples per workgroup of the two
 ECHO_MAX_LAG = 2048           # IRA_ECHO_MAX_LAG: the largest D (the halo the emit pass keeps of the chunk in front)
 ECHO_MAX_PARAMS = 16          # IRA_ECHO_MAX_PARAMS
 ECHO_PARAM_DOUBLES = 8        # IRA_ECHO_PARAM_DOUBLES
+NED_DOUBLES = 8               # IRA_NED_DOUBLES
+NED_TILE = 1024               # IRA_NED_TILE: positions a workgroup of ira_echo_density takes at a time when their span fits
+NED_MAX_DELTA = 2048          # IRA_NED_MAX_DELTA: the largest half window (W = 2 delta + 1 <= 4097)
+NED_MAX_THRESHOLDS = 3        # IRA_NED_MAX_THRESHOLDS
+NED_NAN_SILENT = 0x7fc00000   # IRA_NED_NAN_SILENT: the profile's NaN where the window holds digital silence (B == 0)
+NED_NAN_NONFINITE = 0x7fc00001  # IRA_NED_NAN_NONFINITE: the profile's NaN where B is not finite
+NED_SLOTS = 5120              # float64 squares a workgroup stages (NED_SLOTS of ira_echodensity.hip)
 XSPEC_FRAMES = 16             # IRA_XSPEC_FRAMES: frames a workgroup of ira_xspec_accumulate sums before it writes
 XSPEC_ROWS = 11               # IRA_XSPEC_ROWS
 XSPEC_MIN_FFT, XSPEC_MAX_FFT = 256, 8192
@@ -55,6 +62,27 @@ def xspec_frames(n, n_fft: int, hop: int) -> np.ndarray:
     """K = 1 + (n - n_fft) // hop frames of n samples, 0 when n < n_fft (int64, elementwise)."""
     n = np.asarray(n, dtype=np.int64)
     return np.where(n >= n_fft, 1 + (n - n_fft) // hop, 0).astype(np.int64)
+
+
+def ned_positions(length, onset, step: int, kmax: int) -> np.ndarray:
+    """K = 0 if L <= o else min((L - 1 - o) // S + 1, Kmax) positions of a profile (int64, elementwise)."""
+    length, onset = np.asarray(length, dtype=np.int64), np.asarray(onset, dtype=np.int64)
+    return np.where(length > onset, np.minimum((length - 1 - onset) // int(step) + 1, int(kmax)), 0).astype(np.int64)
+
+
+def ned_tile_positions(delta: int, step: int) -> int:
+    """Positions a workgroup of ira_echo_density takes at a time (ned_geometry of ira_echodensity.hip, restated): NED_TILE
+    when their span fits NED_SLOTS, fewer for large steps and windows.  No result depends on it; tests place K at its
+    multiples."""
+    w, s = 2 * int(delta) + 1, int(step)
+    if 1 < s <= NED_SLOTS:
+        wq = -(-w // s)
+        t = min(NED_TILE, NED_SLOTS // s - wq + 1)
+        while t >= 1 and s * ((t - 1 + wq) | 1) > NED_SLOTS:
+            t -= 1
+        if t >= 1:
+            return t
+    return min(NED_TILE, (NED_SLOTS - w) // s + 1)
 
 
 def lundeby_layout(base_off, base_len, chan_of_seg, blk_size, nblk, first_m) -> Dict[str, object]:
@@ -692,6 +720,45 @@ class Engine:
                                               int(params.shape[0]), ncurve, _ptr(scratch),
                                               _ptr(stash), _ptr(rec), _ptr(curve), self.stream), "ira_echo_criterion")
         return rec[: nseg * ECHO_DOUBLES].view(nseg, ECHO_DOUBLES), curve[: nseg * ncurve].view(nseg, ncurve)
+
+    # ------------------------------------------------------------------ normalized echo density (Abel & Huang)
+    def echo_density(self, x_dev, off: np.ndarray, length: np.ndarray, onset_dev, weights: np.ndarray, delta: int,
+                     step: int, kmax: int, thresholds: Sequence[float]):
+        """Normalized echo density profiles and their records (ira_echo_density).  Channel c: length[c] samples at off[c]
+        of x_dev, the profile starts at onset_dev[c] (int64 device, read on the device); weights: the 2 delta + 1 float64
+        window weights, step the distance of neighbouring positions in samples, kmax the most positions per channel,
+        thresholds 0..NED_MAX_THRESHOLDS levels.  Returns (prof float32 device, flat; prof_off int64 host (nch,): row c
+        starts at prof_off[c] and holds ned_positions(length[c], 0, step, kmax) values -- the onset is not known on the
+        host -- of which the first K are the profile and the rest NaN; rec (nch, NED_DOUBLES) float64 device: K, the
+        positions whose window is digital silence, those whose window sum is not finite, the maximum of the others, its
+        first index, the first index at or above each threshold (-1: none))."""
+        t = self.torch
+        off = np.ascontiguousarray(off, dtype=np.int64).reshape(-1)
+        length = np.ascontiguousarray(length, dtype=np.int64).reshape(-1)
+        weights = np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
+        delta, step, kmax = int(delta), int(step), int(kmax)
+        nch = int(off.size)
+        if length.size != nch:
+            raise ValueError("off and length must be (nch,)")
+        if not 1 <= delta <= NED_MAX_DELTA:
+            raise ValueError(f"delta must be 1..{NED_MAX_DELTA} samples, got {delta}")
+        if weights.size != 2 * delta + 1 or not (np.all(np.isfinite(weights)) and np.all(weights > 0.0)):
+            raise ValueError("weights must be 2 * delta + 1 finite values > 0")
+        if not (1 <= step < 1 << 31 and 0 <= kmax <= 1 << 31):
+            raise ValueError("step must be >= 1 and kmax 0..2^31")
+        thresholds = [float(v) for v in thresholds]
+        if len(thresholds) > NED_MAX_THRESHOLDS:
+            raise ValueError(f"at most {NED_MAX_THRESHOLDS} thresholds")
+        room = ned_positions(length, 0, step, kmax)
+        prof_off = exclusive_cumsum(room)
+        total = int(room.sum())
+        prof = self.empty(total, t.float32)
+        rec = self.empty(nch * NED_DOUBLES, t.float64)
+        d_off, d_len, d_poff, d_w = self.job_tables(off, length, prof_off, weights)
+        check(self.lib.ira_echo_density(_ptr(x_dev), _ptr(d_off), _ptr(d_len), _ptr(onset_dev), nch, _ptr(d_w), delta, step,
+                                        kmax, _lib.dbl_array(thresholds), len(thresholds), _ptr(prof), _ptr(d_poff),
+                                        _ptr(rec), self.stream), "ira_echo_density")
+        return prof[:total], prof_off, rec[: nch * NED_DOUBLES].view(nch, NED_DOUBLES)
 
     # ------------------------------------------------------------------ dual-channel spectral sums (Welch H1 / H2)
     def cross_spectra(self, x_dev, x_off: np.ndarray, y_off: np.ndarray, n: np.ndarray, n_fft: int, hop: int,

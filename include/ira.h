@@ -744,6 +744,38 @@ int32_t ira_xspec_accumulate(const float* x_dev, const int64_t* x_off_dev, const
 int32_t ira_xspec_finish(const double* partial_dev, const int64_t* n_dev, int32_t npairs, int32_t max_frames,
                          int32_t n_fft, int32_t hop, double* out_dev, void* stream);
 
+/* ---- Normalized echo density (Abel & Huang): sliding-window fraction of samples outside the window's own sigma ---------
+ * Nothing in the reference computes it (its "echo density proxy" is ira_diffusion's count over hard windows against a
+ * user threshold); the entry point replaces no reference function.  Host side, with the definition pinned:
+ * audio_analysis_amd/analyse/echodensity.py (`python -m analyse.echodensity`).
+ * ira_echo_density: channel c is len_dev[c] float32 samples at x_dev + off_dev[c]; o = max(onset_dev[c], 0) is read on the
+ *   device.  w_dev: W = 2 delta + 1 float64 weights (> 0), built on the host.  K = 0 if len <= o, else min((len - 1 - o) /
+ *   step + 1, kmax); position j < K has its centre at c = o + j step and the window i = c - delta .. c + delta clipped
+ *   to [0, len), k = i - (c - delta).  With h2[i] = float64(x[i])^2 and, over the clipped window with k ascending,
+ *   A = sum w[k], B = sum w[k] h2[i], C = sum of w[k] where h2[i] A > B (1 + 2^-32):
+ *     prof_dev[prof_off_dev[c] + j] = float32((C / A) / 0.31731050786291415), the NaN IRA_NED_NAN_SILENT where B == 0 and
+ *     the NaN IRA_NED_NAN_NONFINITE where B is not finite.  Row c must hold the K of onset 0 (min((len - 1) / step + 1,
+ *     kmax), 0 for len = 0) floats: the onset never returns to the host to size it; entries from K on are NaN.
+ *   rec_dev[c * IRA_NED_DOUBLES + ..], reduced from the float32 row as stored: [0] K  [1] positions with B == 0
+ *     [2] positions with B not finite  [3] the maximum of the other values (NaN for none)  [4] its first index (-1)
+ *     [5..7] the first j with prof[j] >= thresholds[t], t < nthr (-1 for none and for unused slots); NaN never crosses.
+ *   thresholds is a HOST array of nthr doubles (0..IRA_NED_MAX_THRESHOLDS, finite; NULL only with nthr = 0), checked
+ *   like delta (1..IRA_NED_MAX_DELTA), step (>= 1), kmax (0..2^31) and nch (0..65535) before anything is launched:
+ *   IRA_E_NULL / IRA_E_SIZE.  nch = 0: IRA_OK, no launch.  No scratch.
+ *   A workgroup stages float64 squares of IRA_NED_TILE positions' span (fewer for large steps and windows) and the
+ *   weights in LDS, one thread per position; a position's sums are a function of its own window in one fixed order, and
+ *   there are no atomics: a channel's row and record are bit-identical whatever the batch or the channel's place in it. */
+#define IRA_NED_DOUBLES 8
+#define IRA_NED_TILE 1024          /* positions a workgroup takes at a time when their span fits (always at step 1) */
+#define IRA_NED_MAX_DELTA 2048     /* W <= 4097: 20 ms at 192 kHz is 3841 */
+#define IRA_NED_MAX_THRESHOLDS 3
+#define IRA_NED_NAN_SILENT 0x7fc00000u
+#define IRA_NED_NAN_NONFINITE 0x7fc00001u
+int32_t ira_echo_density(const float* x_dev, const int64_t* off_dev, const int64_t* len_dev, const int64_t* onset_dev,
+                         int32_t nch, const double* w_dev, int32_t delta, int32_t step, int64_t kmax,
+                         const double* thresholds, int32_t nthr, float* prof_dev, const int64_t* prof_off_dev,
+                         double* rec_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
