@@ -555,7 +555,7 @@ __global__ __launch_bounds__(SV_THREADS) void ar_solve_kernel(const double* __re
                                                               const double* __restrict__ gpart, double cond_threshold) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   __shared__ double piv, trace_s, nrm_s;
-  __shared__ int fail;
+  __shared__ int fail, bad_s;
   const int e = blockIdx.x;
   const int tid = threadIdx.x;
   // refinement call (gpart != null): only flagged elements; rhs = gradient of the current residual, a += G^-1 rhs
@@ -637,6 +637,13 @@ __global__ __launch_bounds__(SV_THREADS) void ar_solve_kernel(const double* __re
     double tr = 0.0;
     for (int k = 0; k < p; ++k) tr += G[k * p + k];
     trace_s = tr;
+    // A NaN or infinite sample reaches every entry of diagonal 0 of the lag-sum form (Phi[0][0] holds s[p..N-1], the head
+    // corrections s[0..p-1]; inf - inf = NaN from then on), so the trace says "not finite" for the whole segment.  The dense
+    // Gram never squares s[N-1]: there the right-hand side is looked at as well.
+    int bad = !(tr - tr == 0.0);
+    if (!lag_mode)
+      for (int k = 0; k < p; ++k) { const double v = vec[k]; if (!(v - v == 0.0)) bad = 1; }
+    bad_s = bad;
   }
   double dmax = 0.0, dmin = INFINITY;
 
@@ -676,14 +683,21 @@ __global__ __launch_bounds__(SV_THREADS) void ar_solve_kernel(const double* __re
     if (tid == 0 && !fail) info[IRA_AR_INFO_DOUBLES * e + 0] = 2.0;  // refined
     return;
   }
+  // not finite (status 3): NaN coefficients, as ar_minnorm_kernel reports it -- but at every order, with a ridge and with the
+  // dense Gram, where that kernel does not run (the reference's lstsq raises LinAlgError there).  A finite fit is untouched.
+  const bool bad = bad_s != 0;                                  // written before the factorisation's barriers
+  const double qn = __longlong_as_double(0x7ff8000000000000ll);
   if (tid == 0) co[0] = 1.0;
-  for (int j = tid; j < p; j += SV_THREADS) co[j + 1] = vec[j];
+  for (int j = tid; j < p; j += SV_THREADS) co[j + 1] = bad ? qn : vec[j];
   if (info == nullptr) return;
   // cond(G) estimate: lambda_max <= trace(G); 1/lambda_min from two inverse iterations on the factor, started from the
-  // alternating vector (the weakest direction of a low-passed signal's Gram is the one at Nyquist).  Within a factor p
-  // above the true condition number -- it only decides whether ira_ar_refine has work to do.
+  // alternating vector (the weakest direction of a low-passed signal's Gram is the one at Nyquist).  At most p times the
+  // true condition number (trace <= p lambda_max, ||G^-1 v|| <= 1 / lambda_min).  NOT bounded from below: for even p the
+  // start vector is orthogonal to the constant vector, the weak direction of a HIGH-passed signal, and two iterations
+  // recover only part of it -- 0.25 cond(G) is the least the tests accept (tests/test_gpu_ar.py, tests/ar_ref.py
+  // estimate_f64).  It only decides whether ira_ar_refine / ira_ar_exact have work to do.
   double cond_est = INFINITY;
-  if (!fail) {
+  if (!fail && !bad) {
     __syncthreads();
     for (int j = tid; j < p; j += SV_THREADS) vec[j] = (j & 1) ? -1.0 : 1.0;
     __syncthreads();
@@ -706,7 +720,7 @@ __global__ __launch_bounds__(SV_THREADS) void ar_solve_kernel(const double* __re
     }
   }
   if (tid == 0) {
-    info[IRA_AR_INFO_DOUBLES * e + 0] = (double)fail;
+    info[IRA_AR_INFO_DOUBLES * e + 0] = bad ? 3.0 : (double)fail;
     info[IRA_AR_INFO_DOUBLES * e + 1] = dmax;   // largest / smallest Cholesky pivot
     info[IRA_AR_INFO_DOUBLES * e + 2] = dmin;
     info[IRA_AR_INFO_DOUBLES * e + 3] = cond_est;
@@ -828,11 +842,12 @@ __global__ __launch_bounds__(64) void ar_solve_wave_kernel(const double* __restr
     if (lane == 0 && !fail) info[IRA_AR_INFO_DOUBLES * e + 0] = 2.0;  // refined
     return;
   }
+  const bool bad = !(trace - trace == 0.0);                            // not finite (status 3), see ar_solve_kernel
   if (lane == 0) co[0] = 1.0;
-  if (lane < p) co[lane + 1] = vec;
+  if (lane < p) co[lane + 1] = bad ? __longlong_as_double(0x7ff8000000000000ll) : vec;
   if (info == nullptr) return;
   double cond_est = INFINITY;
-  if (!fail) {
+  if (!fail && !bad) {
     vec = lane < p ? ((lane & 1) ? -1.0 : 1.0) : 0.0;
     for (int it = 0; it < 2; ++it) {
       double q = 0.0;
@@ -846,7 +861,7 @@ __global__ __launch_bounds__(64) void ar_solve_wave_kernel(const double* __restr
     cond_est = trace * sqrt(q);
   }
   if (lane == 0) {
-    info[IRA_AR_INFO_DOUBLES * e + 0] = (double)fail;
+    info[IRA_AR_INFO_DOUBLES * e + 0] = bad ? 3.0 : (double)fail;
     info[IRA_AR_INFO_DOUBLES * e + 1] = dmax;
     info[IRA_AR_INFO_DOUBLES * e + 2] = dmin;
     info[IRA_AR_INFO_DOUBLES * e + 3] = cond_est;

@@ -312,11 +312,14 @@ int32_t ira_log_smooth_db(float* mag_dev, const int64_t* off_dev, const int32_t*
  * analyse/zplane.py:83-120 (which uses an SVD-based lstsq; results agree to ~cond(A)^2 * 1e-16).
  * partial_dev: nb * ira_ar_partial_doubles(order, max_len) doubles of scratch; gscratch_dev: nb*order*order
  * doubles, only needed when order > 128; info_dev (optional): IRA_AR_INFO_DOUBLES doubles per element
- * [0] status: 0 solved, 1 a Cholesky pivot was not positive, 2 solved and refined (ira_ar_refine), 3 not finite,
+ * [0] status: 0 solved, 1 a Cholesky pivot was not positive, 2 solved and refined (ira_ar_refine), 3 not finite (a NaN or
+ * infinite sample: coefficients 1, NaN ..; written by ira_ar_solve itself, at every order, with or without a ridge),
  * 4 rank-deficient: minimum-norm solution (ira_ar_minnorm, which then redefines [1..3]), 5 solved by the double-double
  * normal equations (ira_ar_exact), [1] largest,
- * [2] smallest pivot, [3] condition estimate trace(G) * ||G^-1|| (two inverse iterations on the factor; between
- * cond(G) and order * cond(G)).  1 <= order <= 1024 < len. */
+ * [2] smallest pivot, [3] condition estimate trace(G) * ||G^-1|| (two inverse iterations on the factor, started from the
+ * alternating vector): at most order * cond(G); no rigorous lower bound -- on high-passed signals of even order the
+ * start vector is orthogonal to the weak direction; the tests hold it above 0.25 cond(G), the smallest ratio measured
+ * is recorded in tests/test_gpu_ar.py).  1 <= order <= 1024 < len. */
 #define IRA_AR_INFO_DOUBLES 4
 #define IRA_AR_DENSE_GRAM 1   /* flags: form G = A^T A as a dense contraction on the FP64 matrix cores (v_mfma_f64_16x16x4_f64)
                                * instead of the O(order * len) lag-sum form: the cross-check of the default path.  gram, solve
