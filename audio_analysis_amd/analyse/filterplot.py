@@ -3,7 +3,8 @@ Filter response (magnitude + phase of the whole-segment spectrum) on the GPU.
 
 Host-side mirror of the reference's analyse/filterplot.py (dataclasses :43-104,
 analyse_filter_response_for_channel :112-203, summary :382-390).  Same float64 Bluestein rFFT as the
-frequency-response module; the phase unwrap (numpy.unwrap semantics) is a parallel scan (ira_phase_unwrap).
+frequency-response module; the phase unwrap (numpy.unwrap semantics) is a parallel scan, in the same pass as the dB
+values and the statistics (ira_spectrum_finish).
 """
 from __future__ import annotations
 

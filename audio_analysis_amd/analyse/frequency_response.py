@@ -125,15 +125,17 @@ def spectrum_device(eng, batch, sample_rate_hz: int, settings, what: str, want_p
     starts, lens = spectrum_segments(eng, batch, sample_rate_hz, settings, what)
     # nothing but the dB / phase kernel reads these spectra: even-length Bluestein elements stay packed (engine.rfft_any)
     spec, off, packed = eng.rfft_any_packed(batch.x, batch.off + starts, lens, bool(settings.use_hann_window))
-    mag, ph = eng.spectrum_mag_phase(spec, off, lens, float(settings.magnitude_floor_db), want_phase=want_phase,
-                                     packed=packed)
-    phase = eng.phase_unwrap(ph, off, lens, unwrap, degrees) if want_phase else None
     nyq = 0.5 * float(sample_rate_hz)
     f_lo = float(np.clip(settings.f_min_hz, 0.0, nyq))
     f_hi = float(np.clip(settings.f_max_hz, f_lo, nyq))
     steps = np.array([rfft_bin_step(int(n), sample_rate_hz) for n in lens], dtype=np.float64)
     smoothed = False
     bins_w = int(getattr(settings, "smoothing_log_bins", 0) or 0)
+    # dB, (unwrapped) phase and -- unless the curve is smoothed first -- the statistics in one pass over the spectra
+    done = eng.spectrum_finish(spec, off, lens, float(settings.magnitude_floor_db), packed=packed, want_phase=want_phase,
+                               unwrap=unwrap, degrees=degrees,
+                               stats=None if bins_w > 1 else (steps, f_lo, f_hi, 1000.0))
+    mag, phase, stats = done["mag"], done["phase"], done["stats"]
     if bins_w > 1:
         # optional, default-off: log-frequency smoothing of the dB curve on the device, in place (ira_log_smooth_db); the
         # statistics below then see the smoothed curve, exactly as the reference recomputes them (frequency_response.py:236-260)
@@ -146,7 +148,7 @@ def spectrum_device(eng, batch, sample_rate_hz: int, settings, what: str, want_p
         if np.all(nsel > 0):
             smoothed = eng.log_smooth(mag, off, np.ones(len(rng), np.int32), k_lo, nsel, steps, bins_w,
                                       int(getattr(settings, "log_bins_per_octave", 96)), through_float32=False)
-    stats = eng.spectrum_stats(mag, off, lens, steps, f_lo, f_hi, 1000.0)
+        stats = eng.spectrum_stats(mag, off, lens, steps, f_lo, f_hi, 1000.0)
     # with packed elements `spec` holds half-length transforms Z in some slots, not half spectra: nothing may read it as
     # "the spectra"  -- it travels as spec_packed, and `spec` is only there when every slot is a spectrum
     return dict(spec=spec if packed is None else None, spec_packed=spec if packed is not None else None, off=off, packed=packed, starts=starts, lens=lens, mag=mag, phase=phase, stats=stats, f_lo=f_lo,

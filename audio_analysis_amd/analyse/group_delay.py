@@ -4,8 +4,8 @@ Group delay vs frequency on the GPU.
 Host-side mirror of the reference's analyse/group_delay.py (dataclasses :39-73, _compute_group_delay_from_ir
 :89-137, the time selection of plot_group_delay_from_wav_file :159-171, summary :209-220).  Device work per
 channel: one zero-padded / truncated Hann-windowed rFFT of n_fft points (ira_rfft_any with data/window lengths;
-channels that share n_fft ride one complex transform in pairs), atan2 (ira_spectrum_mag_phase), numpy.unwrap in
-float64 (ira_phase_unwrap) and -numpy.gradient on the rad/sample axis (ira_group_delay).  The optional
+channels that share n_fft ride one complex transform in pairs), atan2 and numpy.unwrap in float64 (one pass,
+ira_spectrum_finish) and -numpy.gradient on the rad/sample axis (ira_group_delay).  The optional
 moving-average smoothing (default off) and the frequency mask are host-side NumPy on the device result.
 """
 from __future__ import annotations
@@ -100,8 +100,9 @@ def group_delay_device(eng, batch, sample_rate_hz: int, settings: GroupDelayAnal
     with eng.tagged("[gd]"):                               # per-call device times of this block (bench.py) under their own names
         spec, off = eng.rfft_any(batch.x, batch.off + starts, n_fft.astype(np.int32), bool(settings.use_hann_window),
                                  data_len=np.minimum(lens, n_fft).astype(np.int32), win_len=lens.astype(np.int32))
-        _, ph = eng.spectrum_mag_phase(spec, off, n_fft.astype(np.int32), -400.0, want_phase=True)
-        ph64 = eng.phase_unwrap(ph, off, n_fft.astype(np.int32), bool(settings.unwrap_phase), False, as_float64=True)
+        # the angle and its unwrap in one pass (no dB array, no wrapped phase through memory)
+        ph64 = eng.spectrum_finish(spec, off, n_fft.astype(np.int32), want_mag=False, want_phase=True,
+                                   unwrap=bool(settings.unwrap_phase), degrees=False, as_float64=True)["phase"]
         steps = np.array([rfft_bin_step(int(v), sample_rate_hz) for v in n_fft], dtype=np.float64)
         gd = eng.group_delay(ph64, off, n_fft, steps, float(sample_rate_hz))
     return dict(gd=gd, off=off, n_fft=n_fft, starts=starts, lens=lens)

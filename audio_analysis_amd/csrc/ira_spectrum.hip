@@ -23,6 +23,23 @@ constexpr double kPi = 3.14159265358979323846;
 // kernel is bound by its 28 bytes per bin instead of by the VALU (times: DESIGN.md section 4).
 constexpr int ATAN_TAB = 64;
 
+// The library routines behind the rare operands (and the twiddles' sincospi) stay OUT of line: inlined, each of them holds
+// more registers than the arithmetic around it, and spectrum_finish_kernel -- 1024 threads, 128 registers -- spilled to
+// scratch with them (mag_phase_kernel: 114 registers inlined, 53 so).  The calls sit on paths the everyday bin never takes.
+__device__ __attribute__((noinline)) double atan2_lib(double y, double x) { return atan2(y, x); }
+__device__ __attribute__((noinline)) double fmod_lib(double a, double b) { return fmod(a, b); }
+__device__ __attribute__((noinline)) double exp10_lib(double y) { return exp10(y); }
+__device__ __attribute__((noinline)) cd twiddle_lib(long long k, long long l) {
+  double sn, cs;
+  sincospi(-(double)(k % (2 * l)) / (double)l, &sn, &cs);
+  return {cs, sn};
+}
+__device__ __attribute__((noinline)) float db_lib(double re, double im, double floor_lin) {
+  const double a = hypot(re, im);
+  const double m = (a != a) ? a : fmax(a, floor_lin);
+  return (float)(20.0 * log10(m));
+}
+
 __device__ __forceinline__ void build_atan_table(double* tab, int tid) {
   if (tid <= ATAN_TAB) tab[tid] = atan((double)tid * (1.0 / ATAN_TAB));
 }
@@ -32,7 +49,7 @@ __device__ __forceinline__ double atan2_table(double y, double x, const double* 
   const double mx = fmax(ax, ay), mn = fmin(ax, ay);
   // zero / tiny / huge / infinite / NaN: library.  Both parts are tested: fmax / fmin drop a NaN, so a bin with ONE NaN part
   // used to pass as its other part twice and came out at +-pi/4 (its dB was NaN already)
-  if (!(ax > 1.0e-300 && ay > 1.0e-300 && ax < 1.0e300 && ay < 1.0e300)) return atan2(y, x);
+  if (!(ax > 1.0e-300 && ay > 1.0e-300 && ax < 1.0e300 && ay < 1.0e300)) return atan2_lib(y, x);
   const double t = mn / mx;
   const int k = (int)(t * (double)ATAN_TAB + 0.5);
   const double t0 = (double)k * (1.0 / ATAN_TAB);
@@ -62,7 +79,7 @@ __device__ __forceinline__ double unwrap_correction(double prev, double cur) {
   if (a >= 0.0 && a < period) md = a;
   else if (a >= period && a < 2.0 * period) md = a - period;
   else if (a < 0.0 && a > -period) md = a;
-  else md = fmod(a, period);
+  else md = fmod_lib(a, period);
   if (md != 0.0) {
     if (md < 0.0) md += period;
   } else {
@@ -73,6 +90,26 @@ __device__ __forceinline__ double unwrap_correction(double prev, double cur) {
   double corr = ddmod - dd;
   if (fabs(dd) < kPi) corr = 0.0;
   return corr;
+}
+
+// ---- the per-bin bodies shared by mag_phase_kernel and spectrum_finish_kernel ------------------------------------------
+// bin k of a packed element from Z[k], Z[l - k] and W_2l^k = cs + i sn (the formulas of ira::half_split_bin, ira_fft_reg.h);
+// edge: k == 0 or k == l, DC / Nyquist of a real signal
+__device__ __forceinline__ cd packed_bin(cd zk, cd zl, double cs, double sn, bool edge) {
+  const auto [ev, od] = ira::hermitian_parts(zk, zl);
+  cd v = {ev.re + (cs * od.re - sn * od.im), ev.im + (cs * od.im + sn * od.re)};
+  if (edge) v.im = 0.0;
+  return v;
+}
+
+__device__ __forceinline__ float bin_db(cd v, double floor_lin, double floor_p, float floor_db32,
+                                        const ira::LogTabEntry* ltab) {
+  const double p = v.re * v.re + v.im * v.im;
+  if (p > 1.0e-280 && p < 1.0e280 && floor_lin > 1.0e-140) {
+    // numpy.maximum(|X|, floor) in the squared domain; a value AT the floor gives the floor's own float32 dB value
+    return p > floor_p ? (float)(3.0102999566398120 * ira::log2_table(p, ltab)) : floor_db32;
+  }
+  return db_lib(v.re, v.im, floor_lin);
 }
 
 __global__ __launch_bounds__(256) void mag_phase_kernel(const cd* __restrict__ spec, const int64_t* __restrict__ spec_off,
@@ -107,27 +144,14 @@ __global__ __launch_bounds__(256) void mag_phase_kernel(const cd* __restrict__ s
   for (long long k = k_first; k < nb; k += k_step) {
     cd v;
     if (pk) {
-      const cd zk = s[k == l ? 0 : k], zl = s[(k == 0 || k == l) ? 0 : l - k];
-      const auto [ev, od] = ira::hermitian_parts(zk, zl);
-      v = {ev.re + (cs * od.re - sn * od.im), ev.im + (cs * od.im + sn * od.re)};
-      if (k == 0 || k == l) v.im = 0.0;                            // DC / Nyquist of a real signal
+      v = packed_bin(s[k == l ? 0 : k], s[(k == 0 || k == l) ? 0 : l - k], cs, sn, k == 0 || k == l);
       const double nc = cs * rc - sn * rs;
       sn = sn * rc + cs * rs;
       cs = nc;
     } else {
       v = s[k];
     }
-    const double p = v.re * v.re + v.im * v.im;
-    float db;
-    if (p > 1.0e-280 && p < 1.0e280 && floor_lin > 1.0e-140) {
-      // numpy.maximum(|X|, floor) in the squared domain; a value AT the floor gives the floor's own float32 dB value
-      db = p > floor_p ? (float)(3.0102999566398120 * ira::log2_table(p, ltab)) : floor_db32;
-    } else {
-      const double a = hypot(v.re, v.im);
-      const double m = (a != a) ? a : fmax(a, floor_lin);        // numpy.maximum keeps NaN (frequency_response.py:215-218)
-      db = (float)(20.0 * log10(m));
-    }
-    mo[k] = db;
+    mo[k] = bin_db(v, floor_lin, floor_p, floor_db32, ltab);
     if (po) po[k] = atan2_table(v.im, v.re, atab);
   }
 }
@@ -138,6 +162,26 @@ __global__ __launch_bounds__(256) void mag_phase_kernel(const cd* __restrict__ s
 constexpr int UW_THREADS = 1024;
 constexpr int UW_PER = 4;
 constexpr int UW_TILE = UW_THREADS * UW_PER;
+
+// A tile's corrections (c: the thread's UW_PER consecutive bins) -> their inclusive prefix within the thread (left in c) and
+// what the thread adds to it: the carry of the earlier tiles plus everything before the thread in this tile, across the wave
+// by a shuffle scan, then the wave totals in order.  ONE barrier inside: every thread of the workgroup calls it.
+__device__ __forceinline__ double unwrap_scan(double (&c)[UW_PER], double carry, double* wave_tot, int lane, int wave) {
+  c[1] += c[0]; c[2] += c[1]; c[3] += c[2];
+  double incl = c[3];
+#pragma unroll
+  for (int o2 = 1; o2 < 64; o2 <<= 1) {
+    const double dn = __shfl_up(incl, o2, 64);
+    if (lane >= o2) incl += dn;
+  }
+  double excl = __shfl_up(incl, 1, 64);
+  if (lane == 0) excl = 0.0;
+  if (lane == 63) wave_tot[wave] = incl;
+  __syncthreads();
+  double before = 0.0;
+  for (int w = 0; w < wave; ++w) before += wave_tot[w];
+  return carry + (before + excl);
+}
 
 __global__ __launch_bounds__(UW_THREADS) void unwrap_kernel(const double* __restrict__ phase,
                                                             const int64_t* __restrict__ phase_off,
@@ -181,21 +225,7 @@ __global__ __launch_bounds__(UW_THREADS) void unwrap_kernel(const double* __rest
       c[r] = (do_unwrap && i >= 1 && i < n) ? unwrap_correction(prev, v[r]) : 0.0;
       prev = v[r];
     }
-    // inclusive prefix within the thread, then across the wave, then across waves
-    c[1] += c[0]; c[2] += c[1]; c[3] += c[2];
-    double incl = c[3];
-#pragma unroll
-    for (int o2 = 1; o2 < 64; o2 <<= 1) {
-      const double dn = __shfl_up(incl, o2, 64);
-      if (lane >= o2) incl += dn;
-    }
-    double excl = __shfl_up(incl, 1, 64);
-    if (lane == 0) excl = 0.0;
-    if (lane == 63) wave_tot[wave] = incl;
-    __syncthreads();
-    double before = 0.0;
-    for (int w = 0; w < wave; ++w) before += wave_tot[w];
-    const double add = carry + (before + excl);
+    const double add = unwrap_scan(c, carry, wave_tot, lane, wave);
 #pragma unroll
     for (int r = 0; r < UW_PER; ++r) {
       const long long i = i0 + r;
@@ -462,28 +492,103 @@ __global__ __launch_bounds__(OS_THREADS) void order_stats_kernel(const double* _
 // [3] sum(f*lin) [4] sum(lin) [5] first in-range frequency [6] index nearest 1 kHz [7] magnitude_db there
 constexpr int ST_THREADS = 1024;
 
+// A thread's running statistics and the scratch of their reduction over the workgroup (stats_kernel and
+// spectrum_finish_kernel).
+struct StatsAcc {
+  double cnt = 0.0, sfl = 0.0, sl = 0.0;
+  unsigned long long best = 0ull;      // argmax of float32 dB with first-max-wins: order-preserving key of the float, then smallest index
+  unsigned long long near = ~0ull;     // argmin |f - probe| first-min-wins: key = (bits(|d|) << 32 | idx) minimised
+  long long first_in;
+  float near_db = 0.0f;                // the dB value of the bin `near` names
+};
+struct StatsScratch {
+  double red[3][ST_THREADS / IRA_WAVE];
+  unsigned long long kred[2][ST_THREADS / IRA_WAVE];
+  long long lred[ST_THREADS / IRA_WAVE];
+  float dred[ST_THREADS / IRA_WAVE];
+};
+
+// bin k with the float32 dB value db: a thread takes its bins in ascending order (the sums are added in that order)
+__device__ __forceinline__ void stats_bin(StatsAcc& a, long long k, float db, double val, float f_min, float f_max,
+                                          float probe_hz, const double* etab) {
+  const float f = (float)((double)k * val);
+  const float d = fabsf(f - probe_hz);
+  const unsigned long long nk = ((unsigned long long)__float_as_uint(d) << 32) | (unsigned long long)(uint32_t)k;
+  a.near_db = nk < a.near ? db : a.near_db;
+  a.near = nk < a.near ? nk : a.near;
+  if (f >= f_min && f <= f_max) {
+    uint32_t uu = __float_as_uint(db);
+    uu = (uu & 0x80000000u) ? ~uu : (uu | 0x80000000u);  // monotone map float -> uint
+    if (db != db) uu = 0xFFFFFFFFu;                      // numpy.argmax: the first NaN wins, whatever its sign or payload
+    const unsigned long long key = ((unsigned long long)uu << 32) | (unsigned long long)(0xFFFFFFFFu - (uint32_t)k);
+    a.best = key > a.best ? key : a.best;
+    // 10^(dB/20): table-driven (ira_log.h) for finite values in the table's range -- the float64 exp10 was 70 of this
+    // kernel's 100 instructions per bin, and the kernel is VALU-bound (one workgroup per spectrum); NaN / infinite / huge
+    // values take the library routine
+    const double y = (double)db * 0.05;
+    const double lin = fabs(y) < 15.0 ? ira::exp10_table(y, etab) : exp10_lib(y);
+    a.cnt += 1.0; a.sfl += (double)f * lin; a.sl += lin;
+    a.first_in = k < a.first_in ? k : a.first_in;
+  }
+}
+
+// The workgroup's record from its threads' statistics: ira::wave_sum and the key shuffles across each wave, then the serial
+// sum over the waves by thread 0, which writes the eight doubles.  ONE barrier inside: every thread calls it.
+__device__ __forceinline__ void stats_finish(StatsAcc a, StatsScratch& sc, long long n, double val, double* o) {
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  a.cnt = ira::wave_sum(a.cnt); a.sfl = ira::wave_sum(a.sfl); a.sl = ira::wave_sum(a.sl);
+#pragma unroll
+  for (int o2 = 32; o2 > 0; o2 >>= 1) {
+    const unsigned long long ob = __shfl_xor(a.best, o2, 64);
+    a.best = ob > a.best ? ob : a.best;
+    const unsigned long long on = __shfl_xor(a.near, o2, 64);
+    const float od = __shfl_xor(a.near_db, o2, 64);
+    a.near_db = on < a.near ? od : a.near_db;
+    a.near = on < a.near ? on : a.near;
+    const long long of = __shfl_xor(a.first_in, o2, 64);
+    a.first_in = of < a.first_in ? of : a.first_in;
+  }
+  if (lane == 0) {
+    sc.red[0][wave] = a.cnt; sc.red[1][wave] = a.sfl; sc.red[2][wave] = a.sl;
+    sc.kred[0][wave] = a.best; sc.kred[1][wave] = a.near; sc.lred[wave] = a.first_in; sc.dred[wave] = a.near_db;
+  }
+  __syncthreads();
+  if (t == 0) {
+    a.cnt = a.sfl = a.sl = 0.0;
+    for (int w = 0; w < ST_THREADS / IRA_WAVE; ++w) {
+      a.cnt += sc.red[0][w]; a.sfl += sc.red[1][w]; a.sl += sc.red[2][w];
+      a.best = sc.kred[0][w] > a.best ? sc.kred[0][w] : a.best;
+      a.near_db = sc.kred[1][w] < a.near ? sc.dred[w] : a.near_db;
+      a.near = sc.kred[1][w] < a.near ? sc.kred[1][w] : a.near;
+      a.first_in = sc.lred[w] < a.first_in ? sc.lred[w] : a.first_in;
+    }
+    const long long pk = (a.cnt > 0.0) ? (long long)(0xFFFFFFFFu - (uint32_t)(a.best & 0xFFFFFFFFull)) : 0;
+    o[0] = a.cnt;
+    o[1] = (double)pk;
+    o[2] = (double)(float)((double)pk * val);
+    o[3] = a.sfl; o[4] = a.sl;
+    o[5] = a.first_in < n ? (double)(float)((double)a.first_in * val) : 0.0;
+    o[6] = (double)(long long)(a.near & 0xFFFFFFFFull);
+    o[7] = (double)a.near_db;
+  }
+}
+
 __global__ __launch_bounds__(ST_THREADS) void stats_kernel(const float* __restrict__ mag_db,
                                                            const int64_t* __restrict__ mag_off,
                                                            const int32_t* __restrict__ L,
                                                            const double* __restrict__ freq_val, float f_min, float f_max,
                                                            float probe_hz, double* __restrict__ out) {
-  __shared__ double red[4][ST_THREADS / IRA_WAVE];
-  __shared__ unsigned long long kred[2][ST_THREADS / IRA_WAVE];
-  __shared__ long long lred[ST_THREADS / IRA_WAVE];
+  __shared__ StatsScratch sc;
   __shared__ double etab[ira::EXPTAB_N];
   const int e = blockIdx.x;
   const long long n = (long long)L[e] / 2 + 1;
   const float* m = mag_db + mag_off[e];
   const double val = freq_val[e];
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int t = threadIdx.x;
   ira::build_exp_table(etab, t);
   __syncthreads();
-  double cnt = 0.0, sfl = 0.0, sl = 0.0;
-  // argmax of float32 dB with first-max-wins: order-preserving key of the float, then smallest index
-  unsigned long long best = 0ull;
-  // argmin |f - probe| first-min-wins: key = (bits(|d|) << 32 | idx) minimised
-  unsigned long long near = ~0ull;
-  long long first_in = n;
+  StatsAcc acc;
+  acc.first_in = n;
   // ST_U loads per thread in flight before the first is used; the per-thread order of the additions is unchanged
   constexpr int ST_U = 16;          // (64 KB of loads in flight per CU: one workgroup per spectrum has only its own loads to hide memory latency with)
   for (long long k0 = t; k0 < n; k0 += (long long)ST_THREADS * ST_U) {
@@ -497,61 +602,168 @@ __global__ __launch_bounds__(ST_THREADS) void stats_kernel(const float* __restri
     for (int u = 0; u < ST_U; ++u) {
       const long long k = k0 + (long long)ST_THREADS * u;
       if (k >= n) continue;
-      const float f = (float)((double)k * val);
-      const float d = fabsf(f - probe_hz);
-      const unsigned long long nk = ((unsigned long long)__float_as_uint(d) << 32) | (unsigned long long)(uint32_t)k;
-      near = nk < near ? nk : near;
-      if (f >= f_min && f <= f_max) {
-        const float db = dbv[u];
-        uint32_t uu = __float_as_uint(db);
-        uu = (uu & 0x80000000u) ? ~uu : (uu | 0x80000000u);  // monotone map float -> uint
-        if (db != db) uu = 0xFFFFFFFFu;                      // numpy.argmax: the first NaN wins, whatever its sign or payload
-        const unsigned long long key = ((unsigned long long)uu << 32) | (unsigned long long)(0xFFFFFFFFu - (uint32_t)k);
-        best = key > best ? key : best;
-        // 10^(dB/20): table-driven (ira_log.h) for finite values in the table's range -- the float64 exp10 was 70 of this
-        // kernel's 100 instructions per bin, and the kernel is VALU-bound (one workgroup per spectrum); NaN / infinite / huge
-        // values take the library routine
-        const double y = (double)db * 0.05;
-        const double lin = fabs(y) < 15.0 ? ira::exp10_table(y, etab) : exp10(y);
-        cnt += 1.0; sfl += (double)f * lin; sl += lin;
-        first_in = k < first_in ? k : first_in;
+      stats_bin(acc, k, dbv[u], val, f_min, f_max, probe_hz, etab);
+    }
+  }
+  stats_finish(acc, sc, n, val, out + (int64_t)e * 8);
+}
+
+// ---- dB, (unwrapped) phase and statistics in ONE pass over a spectrum -------------------------------------------------------
+// What mag_phase_kernel, unwrap_kernel and stats_kernel do in three launches -- 44 bytes per bin, the wrapped float64 phase
+// written to memory only to be read back, the dB array read a second time -- as one workgroup per spectrum that walks it in
+// tiles of UW_TILE bins with the next loads in flight: 16 bytes in and 8 out per bin.  Per tile:
+//   * thread t takes bins t, t + 1024, t + 2048, t + 3072 of the tile: coalesced loads (a packed element's second stream,
+//     Z[l - k], runs backwards), dB and angle by the per-bin functions above, the dB stored from the register and fed to
+//     stats_bin -- the very bins, in the very order, stats_kernel gives the thread, so the sums are the same bits (the dB
+//     values need no staging in LDS for that: load, statistics and store share the mapping);
+//   * the angles go through LDS into unwrap_kernel's mapping (4 consecutive bins per thread) and through unwrap_scan.
+// Two barriers per tile, one after the angles are staged and the one inside unwrap_scan: ph_tile is rewritten only after the
+// scan's barrier (every read of it comes before), wave_tot only after the next tile's staging barrier, and tile_total /
+// prev_last are written after the scan's barrier and read after the next staging barrier.  The trip count depends on the
+// element's length alone, so every thread reaches every barrier.
+// Packed elements: W_2l^k for k = 1024 q + t is ONE complex product of W^(1024 q) (an LDS table of SF_TWQ entries, built per
+// element) and W^t (the thread's own, in registers), both from sincospi with exactly reduced arguments: three roundings
+// where mag_phase_kernel's rotation takes up to 16 steps.  The table covers SF_TWQ * 1024 bins (128 tiles) and is built
+// again, between two barriers of its own, when the walk gets past them.
+constexpr int SF_TWQ = 512;
+constexpr int SF_STAGE = 2;
+
+template <bool DB, bool PHASE>
+__global__ __launch_bounds__(UW_THREADS) void spectrum_finish_kernel(
+    const cd* __restrict__ spec, const int64_t* __restrict__ spec_off, const int32_t* __restrict__ L, double floor_lin,
+    const int32_t* __restrict__ packed, float* __restrict__ mag_db, const int64_t* __restrict__ out_off, int do_unwrap,
+    double out_scale, float* __restrict__ phase32, double* __restrict__ phase64, double* __restrict__ wrapped64,
+    const double* __restrict__ freq_val, float f_min, float f_max, float probe_hz, double* __restrict__ stats) {
+  static_assert(ST_THREADS == UW_THREADS, "the statistics' thread mapping is the tile's load mapping");
+  __shared__ ira::LogTabEntry ltab[ira::LOGTAB_N];
+  __shared__ double atab[ATAN_TAB + 1];
+  __shared__ double etab[ira::EXPTAB_N];
+  __shared__ StatsScratch sc;
+  __shared__ cd twq[SF_TWQ];
+  __shared__ double ph_tile[UW_TILE];
+  __shared__ double wave_tot[UW_THREADS / IRA_WAVE];
+  __shared__ double tile_total, prev_last;
+  const int e = blockIdx.x;
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const long long len = ira::uniform(L[e]);
+  const long long n = len / 2 + 1, l = len / 2;
+  const cd* s = spec + ira::uniform(spec_off[e]);
+  const long long oo = ira::uniform(out_off[e]);
+  const bool pk = packed != nullptr && ira::uniform(packed[e]) != 0 && l > 0;
+  const bool want_stats = DB && stats != nullptr;
+  const double val = want_stats ? ira::uniform(freq_val[e]) : 0.0;
+  const double floor_p = floor_lin * floor_lin;
+  const float floor_db32 = (float)(20.0 * log10(floor_lin));
+  if constexpr (DB) ira::build_log_table(ltab, t);
+  if constexpr (PHASE) build_atan_table(atab, t);
+  if (want_stats) ira::build_exp_table(etab, t);
+  double wt_c = 1.0, wt_s = 0.0;
+  // twq[i] = W^(1024 (q0 + i)) for the SF_TWQ * 1024 bins from 1024 q0 on
+  auto build_twq = [&](long long q0) {
+    const long long k = (q0 + t) * UW_THREADS;
+    if (t < SF_TWQ && k < n) twq[t] = twiddle_lib(k, l);
+  };
+  if (pk) {
+    const cd wt = twiddle_lib(t, l);
+    wt_c = wt.re;
+    wt_s = wt.im;
+    build_twq(0);
+  }
+  if (t == 0) { tile_total = 0.0; prev_last = 0.0; }
+  __syncthreads();
+  StatsAcc acc;
+  acc.first_in = n;
+  // The loads run one stage (SF_STAGE bins per thread, half a tile) ahead of the arithmetic: a whole tile ahead of it, a packed
+  // element's two streams alone would hold 64 registers, and the kernel has 128 for everything (1024 threads).  64 KB of
+  // loads in flight per workgroup, as in stats_kernel.
+  cd nza[SF_STAGE], nzb[SF_STAGE];
+  auto load_stage = [&](long long first) {
+#pragma unroll
+    for (int r = 0; r < SF_STAGE; ++r) {
+      const long long k = first + t + (long long)UW_THREADS * r;
+      nza[r] = {0.0, 0.0};
+      nzb[r] = {0.0, 0.0};
+      if (k < n) {
+        if (pk) {
+          nza[r] = s[k == l ? 0 : k];
+          nzb[r] = s[(k == 0 || k == l) ? 0 : l - k];
+        } else {
+          nza[r] = s[k];
+        }
       }
     }
-  }
-  cnt = ira::wave_sum(cnt); sfl = ira::wave_sum(sfl); sl = ira::wave_sum(sl);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const unsigned long long ob = __shfl_xor(best, o, 64);
-    best = ob > best ? ob : best;
-    const unsigned long long on = __shfl_xor(near, o, 64);
-    near = on < near ? on : near;
-    const long long of = __shfl_xor(first_in, o, 64);
-    first_in = of < first_in ? of : first_in;
-  }
-  if (lane == 0) {
-    red[0][wave] = cnt; red[1][wave] = sfl; red[2][wave] = sl;
-    kred[0][wave] = best; kred[1][wave] = near; lred[wave] = first_in;
-  }
-  __syncthreads();
-  if (t == 0) {
-    cnt = sfl = sl = 0.0;
-    for (int w = 0; w < ST_THREADS / IRA_WAVE; ++w) {
-      cnt += red[0][w]; sfl += red[1][w]; sl += red[2][w];
-      best = kred[0][w] > best ? kred[0][w] : best;
-      near = kred[1][w] < near ? kred[1][w] : near;
-      first_in = lred[w] < first_in ? lred[w] : first_in;
+  };
+  load_stage(0);
+  for (long long base = 0; base < n; base += UW_TILE) {
+    if (pk && base > 0 && base % ((long long)SF_TWQ * UW_THREADS) == 0) {
+      __syncthreads();                                       // every read of the table's earlier entries is behind us
+      build_twq(base / UW_THREADS);
+      __syncthreads();
     }
-    double* o = out + (int64_t)e * 8;
-    const long long pk = (cnt > 0.0) ? (long long)(0xFFFFFFFFu - (uint32_t)(best & 0xFFFFFFFFull)) : 0;
-    const long long i1k = (long long)(near & 0xFFFFFFFFull);
-    o[0] = cnt;
-    o[1] = (double)pk;
-    o[2] = (double)(float)((double)pk * val);
-    o[3] = sfl; o[4] = sl;
-    o[5] = first_in < n ? (double)(float)((double)first_in * val) : 0.0;
-    o[6] = (double)i1k;
-    o[7] = (double)m[i1k];
+    const long long qb = base / ((long long)SF_TWQ * UW_THREADS) * SF_TWQ;
+    // (not unrolled: the library fallbacks of the per-bin functions -- hypot, log10, atan2, exp10 -- are large, and four
+    // copies of them do not fit the registers)
+#pragma unroll 1
+    for (int h = 0; h < UW_PER / SF_STAGE; ++h) {
+      const long long first = base + (long long)h * SF_STAGE * UW_THREADS;
+      cd za[SF_STAGE], zb[SF_STAGE];
+#pragma unroll
+      for (int r = 0; r < SF_STAGE; ++r) { za[r] = nza[r]; zb[r] = nzb[r]; }
+      if (first + SF_STAGE * UW_THREADS < n) load_stage(first + SF_STAGE * UW_THREADS);
+#pragma unroll
+      for (int r = 0; r < SF_STAGE; ++r) {
+        const int j = t + UW_THREADS * (h * SF_STAGE + r);   // place in the tile
+        const long long k = base + j;
+        double ph = 0.0;
+        if (k < n) {
+          cd v = za[r];
+          if (pk) {
+            const cd w = twq[k / UW_THREADS - qb];           // k = 1024 q + t; q is uniform over the workgroup
+            const double cs = w.re * wt_c - w.im * wt_s;
+            const double sn = w.im * wt_c + w.re * wt_s;
+            v = packed_bin(za[r], zb[r], cs, sn, k == 0 || k == l);
+          }
+          if constexpr (DB) {
+            const float db = bin_db(v, floor_lin, floor_p, floor_db32, ltab);
+            mag_db[oo + k] = db;
+            if (want_stats) stats_bin(acc, k, db, val, f_min, f_max, probe_hz, etab);
+          }
+          if constexpr (PHASE) {
+            ph = atan2_table(v.im, v.re, atab);
+            if (wrapped64) wrapped64[oo + k] = ph;
+          }
+        }
+        if constexpr (PHASE) ph_tile[j] = ph;
+      }
+    }
+    if constexpr (PHASE) {
+      __syncthreads();
+      const double carry = tile_total;
+      const long long i0 = base + (long long)UW_PER * t;
+      double c[UW_PER], v[UW_PER];
+      double prev = t == 0 ? prev_last : ph_tile[UW_PER * t - 1];
+#pragma unroll
+      for (int r = 0; r < UW_PER; ++r) v[r] = ph_tile[UW_PER * t + r];
+#pragma unroll
+      for (int r = 0; r < UW_PER; ++r) {
+        const long long i = i0 + r;
+        c[r] = (do_unwrap && i >= 1 && i < n) ? unwrap_correction(prev, v[r]) : 0.0;
+        prev = v[r];
+      }
+      const double add = unwrap_scan(c, carry, wave_tot, lane, wave);
+#pragma unroll
+      for (int r = 0; r < UW_PER; ++r) {
+        const long long i = i0 + r;
+        if (i < n) {
+          const double u = v[r] + (c[r] + add);
+          if (phase32) phase32[oo + i] = (float)(u * out_scale);
+          if (phase64) phase64[oo + i] = u;
+        }
+      }
+      if (t == UW_THREADS - 1) { tile_total = c[3] + add; prev_last = v[3]; }
+    }
   }
+  if (want_stats) stats_finish(acc, sc, n, val, stats + (int64_t)e * 8);
 }
 
 // ---- optional log-frequency smoothing of a dB curve (reference waterfall.py:140-185, frequency_response.py:117-169; default
@@ -696,6 +908,30 @@ extern "C" int32_t ira_spectrum_stats(const float* mag_db_dev, const int64_t* ma
   if (nb <= 0) return nb == 0 ? IRA_OK : IRA_E_SIZE;
   stats_kernel<<<nb, ST_THREADS, 0, (hipStream_t)stream>>>(mag_db_dev, mag_off_dev, L_dev, freq_val_dev,
                                                            (float)f_min_hz, (float)f_max_hz, (float)probe_hz, out_dev);
+  IRA_RETURN_LAUNCH();
+}
+
+extern "C" int32_t ira_spectrum_finish(const double* spec_dev, const int64_t* spec_off_dev, const int32_t* L_dev,
+                                       int32_t nb, double floor_db, const int32_t* packed_dev, float* mag_db_dev,
+                                       const int64_t* out_off_dev, int32_t do_unwrap, int32_t to_degrees,
+                                       float* phase32_dev, double* phase64_dev, double* wrapped64_dev,
+                                       const double* freq_val_dev, double f_min_hz, double f_max_hz, double probe_hz,
+                                       double* stats_dev, void* stream) {
+  IRA_CHECK_PTR(spec_dev); IRA_CHECK_PTR(spec_off_dev); IRA_CHECK_PTR(L_dev); IRA_CHECK_PTR(out_off_dev);
+  const bool phase = phase32_dev != nullptr || phase64_dev != nullptr || wrapped64_dev != nullptr;
+  if (mag_db_dev == nullptr && !phase) return IRA_E_NULL;
+  if (stats_dev != nullptr && (mag_db_dev == nullptr || freq_val_dev == nullptr)) return IRA_E_NULL;
+  if (nb <= 0) return nb == 0 ? IRA_OK : IRA_E_SIZE;
+  const double floor_lin = std::pow(10.0, floor_db / 20.0);
+  const double scale = to_degrees ? (180.0 / kPi) : 1.0;
+  // arithmetic for an output nobody wants is compiled out: no angle without a phase output, no dB without mag_db_dev
+  auto kernel = spectrum_finish_kernel<true, true>;
+  if (!phase) kernel = spectrum_finish_kernel<true, false>;
+  if (mag_db_dev == nullptr) kernel = spectrum_finish_kernel<false, true>;
+  kernel<<<nb, UW_THREADS, 0, (hipStream_t)stream>>>(
+      reinterpret_cast<const cd*>(spec_dev), spec_off_dev, L_dev, floor_lin, packed_dev, mag_db_dev, out_off_dev,
+      do_unwrap ? 1 : 0, scale, phase32_dev, phase64_dev, wrapped64_dev, freq_val_dev, (float)f_min_hz, (float)f_max_hz,
+      (float)probe_hz, stats_dev);
   IRA_RETURN_LAUNCH();
 }
 

@@ -1404,6 +1404,34 @@ class Engine:
                                               self.stream), "ira_spectrum_mag_phase")
         return mag, ph
 
+    def spectrum_finish(self, spec_dev, off: np.ndarray, lengths: np.ndarray, floor_db: float = -120.0,
+                        packed: Optional[np.ndarray] = None, want_mag: bool = True, want_phase: bool = False,
+                        unwrap: bool = True, degrees: bool = True, as_float64: bool = False, want_wrapped: bool = False,
+                        stats: Optional[tuple] = None):
+        """spectrum_mag_phase, phase_unwrap and spectrum_stats as ONE launch (ira_spectrum_finish): every output sits at the
+        spectra's own bin offsets.  Returns dict(mag, phase, wrapped, stats): float32 dB (want_mag), the phase as phase_unwrap
+        gives it (want_phase: float32, in degrees if asked, or float64 radians with as_float64), the wrapped float64 angles
+        (want_wrapped) and, with stats = (freq_val, f_min, f_max, probe_hz), the (n, 8) records of spectrum_stats; None for
+        what was not asked for."""
+        t = self.torch
+        n = int(off.size)
+        lengths = np.ascontiguousarray(lengths, dtype=np.int32)
+        total = int((lengths.astype(np.int64) // 2 + 1).sum())
+        mag = self.empty(total, t.float32) if want_mag else None
+        phase = self.empty(total, t.float64 if as_float64 else t.float32) if want_phase else None
+        wrapped = self.empty(total, t.float64) if want_wrapped else None
+        rec = self.empty(n * 8, t.float64) if stats is not None else None
+        freq_val, f_min, f_max, probe_hz = stats if stats is not None else (None, 0.0, 0.0, 0.0)
+        d_o, d_l, d_pk, d_fv = self.job_tables(off, lengths,
+                                               None if packed is None else np.ascontiguousarray(packed, np.int32),
+                                               None if freq_val is None else np.ascontiguousarray(freq_val, np.float64))
+        check(self.lib.ira_spectrum_finish(_ptr(spec_dev), _ptr(d_o), _ptr(d_l), n, float(floor_db), _ptr(d_pk), _ptr(mag),
+                                           _ptr(d_o), 1 if unwrap else 0, 1 if degrees else 0,
+                                           0 if as_float64 else _ptr(phase), _ptr(phase) if as_float64 else 0,
+                                           _ptr(wrapped), _ptr(d_fv), float(f_min), float(f_max), float(probe_hz),
+                                           _ptr(rec), self.stream), "ira_spectrum_finish")
+        return dict(mag=mag, phase=phase, wrapped=wrapped, stats=None if rec is None else rec[: n * 8].view(n, 8))
+
     def phase_unwrap(self, phase_dev, off: np.ndarray, lengths: np.ndarray, unwrap: bool, degrees: bool,
                      as_float64: bool = False):
         """float32 (optionally degrees) unwrapped phase, or with as_float64 the float64 radians."""

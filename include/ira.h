@@ -271,6 +271,20 @@ int32_t ira_spectrum_stats(const float* mag_db_dev, const int64_t* mag_off_dev, 
                            int32_t nb, const double* freq_val_dev, double f_min_hz, double f_max_hz,
                            double probe_hz, double* out_dev, void* stream);
 
+/* ira_spectrum_mag_phase, ira_phase_unwrap and ira_spectrum_stats in ONE pass over every spectrum (one launch; the wrapped
+ * phase never goes through memory, the dB values are not read back).  Every output sits at out_off_dev[e] (elements of its
+ * own type) and may be NULL, at least one of mag_db_dev / phase32_dev / phase64_dev / wrapped64_dev is not; what nobody wants
+ * is not computed.  mag_db_dev: as ira_spectrum_mag_phase (floor_db, packed_dev).  phase32_dev: float32 of the (unwrapped if
+ * do_unwrap) phase, in degrees if to_degrees; phase64_dev: the same in float64 radians; wrapped64_dev: the angles before the
+ * unwrap.  stats_dev (needs mag_db_dev and freq_val_dev, IRA_E_NULL otherwise): the records of ira_spectrum_stats over the
+ * dB values written.  For plain half spectra every output has the bytes of the three calls; a packed element's bins are
+ * formed with another (shorter) chain of roundings in the twiddle than ira_spectrum_mag_phase's. */
+int32_t ira_spectrum_finish(const double* spec_dev, const int64_t* spec_off_dev, const int32_t* L_dev, int32_t nb,
+                            double floor_db, const int32_t* packed_dev, float* mag_db_dev, const int64_t* out_off_dev,
+                            int32_t do_unwrap, int32_t to_degrees, float* phase32_dev, double* phase64_dev,
+                            double* wrapped64_dev, const double* freq_val_dev, double f_min_hz, double f_max_hz,
+                            double probe_hz, double* stats_dev, void* stream);
+
 /* ---- a14: waterfall slice normalisation ----------------------------------------------------------------
  * mag[e] is the (F, S_e) STFT dB matrix of the S_e selected frames (ira_stft_mag_db with frame_sel_dev);
  * out[e] is (S_e, nsel) float32: clip(mag[k_lo+k, s] - ref, -dyn_db, 0), ref = max over the selected block

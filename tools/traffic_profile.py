@@ -35,7 +35,8 @@ CALLS = [   # (substring of the kernel name, ABI call)
     ("diffusion_mono", "ira_diffusion"), ("diffusion_stereo", "ira_diffusion_stereo"),
     ("edc_sums", "ira_edc_fits"), ("edc_carry", "ira_edc_fits"), ("edc_fit", "ira_edc_fits"), ("edc_emit", "ira_edc_fits"),
     ("crossing_search", "ira_curve_fits"), ("curve_fit", "ira_curve_fits"), ("peak_partial", "ira_peak_index"),
-    ("peak_decode", "ira_peak_index"), ("mag_phase", "ira_spectrum_mag_phase"), ("unwrap", "ira_phase_unwrap"),
+    ("peak_decode", "ira_peak_index"), ("spectrum_finish_kernel", "ira_spectrum_finish"),
+    ("mag_phase", "ira_spectrum_mag_phase"), ("unwrap", "ira_phase_unwrap"),
     ("stats_kernel", "ira_spectrum_stats"), ("waterfall", "ira_waterfall_rel"), ("logbin", "ira_logbin_aggregate"),
     ("host_pull", "ira_host_pull"), ("pcm16", "ira_pcm16_to_channels"),
 ]
