@@ -8,6 +8,7 @@
 #include <cmath>
 
 #include "ira_common.h"
+#include "ira_reduce.h"
 
 namespace {
 
@@ -32,8 +33,7 @@ __global__ __launch_bounds__(DV_THREADS) void deconv_pmax_kernel(const cd* __res
   double m = 0.0;
   for (long long k = (long long)blockIdx.x * DV_THREADS + threadIdx.x; k < nbins; k += (long long)gridDim.x * DV_THREADS)
     m = fmax(m, power_of(x[k]));
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) m = fmax(m, __shfl_xor(m, o, 64));
+  m = ira::wave_max(m);
   if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = m;
   __syncthreads();
   if (threadIdx.x == 0) {

@@ -13,6 +13,7 @@
 #include <cmath>
 
 #include "ira_common.h"
+#include "ira_reduce.h"
 
 namespace {
 
@@ -181,8 +182,7 @@ __device__ double max_abs_lag_sum(const double* cur, const double* lagsrc, int n
     }
   }
   // block max
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) best = fmax(best, __shfl_xor(best, o, 64));
+  best = ira::wave_max(best);
   __syncthreads();
   if ((tid & 63) == 0) wave_max[tid >> 6] = best;
   __syncthreads();

@@ -20,11 +20,12 @@
 //                                             curve keys -> float32 (untouched keys -> NaN)
 // Every chunk boundary, every thread's share of a chunk and every reduction tree is a function of the segment's own
 // onset, length and parameters; the two atomics merge with min / max, which do not depend on arrival order; loads are
-// 16-byte loads at 4-byte alignment (ew_load of ira_energy.hip).  So a segment's record and curve are bit-identical
-// whatever the batch, the segment's place in it or the alignment of its first sample.
+// ira::load_run (16 bytes at 4-byte alignment).  So a segment's record and curve are bit-identical whatever the batch, the
+// segment's place in it or the alignment of its first sample.
 #include <math.h>
 
 #include "ira_common.h"
+#include "ira_reduce.h"
 
 namespace {
 
@@ -106,9 +107,6 @@ __device__ __forceinline__ double echo_power(float x, double n, int mode) {
   return a == 0.0 ? 0.0 : pow(a, n);
 }
 
-typedef float ec_f4 __attribute__((ext_vector_type(4), aligned(4)));       // 16-byte access, 4-byte alignment
-typedef double ec_d2 __attribute__((ext_vector_type(2), aligned(8)));
-
 // s at the thread's 16 positions c0 + 16 t .. + 15 of the chunk that starts at c0 (zeros at and after M): from the
 // samples, or from the stash the partial pass wrote (stash_chunk = that chunk's EC_CHUNK doubles).
 __device__ __forceinline__ void echo_chunk_s(const EchoSeg& g, int64_t c0, const double* __restrict__ stash_chunk,
@@ -117,24 +115,13 @@ __device__ __forceinline__ void echo_chunk_s(const EchoSeg& g, int64_t c0, const
   if (stash_chunk != nullptr) {
 #pragma unroll
     for (int r = 0; r < EC_PER_THREAD; r += 2) {
-      const ec_d2 v = *reinterpret_cast<const ec_d2*>(stash_chunk + i0 + r);
+      const ira::d2u v = *reinterpret_cast<const ira::d2u*>(stash_chunk + i0 + r);
       s[r] = v.x; s[r + 1] = v.y;
     }
     return;
   }
-  const int64_t m0 = c0 + i0;
-  const float* q = g.q + m0;
   float xv[EC_PER_THREAD];
-  if (m0 + EC_PER_THREAD <= g.m) {
-#pragma unroll
-    for (int j = 0; j < EC_PER_THREAD / 4; ++j) {
-      const ec_f4 v = *reinterpret_cast<const ec_f4*>(q + 4 * j);
-      xv[4 * j] = v.x; xv[4 * j + 1] = v.y; xv[4 * j + 2] = v.z; xv[4 * j + 3] = v.w;
-    }
-  } else {
-#pragma unroll
-    for (int r = 0; r < EC_PER_THREAD; ++r) xv[r] = (m0 + r < g.m) ? q[r] : 0.0f;
-  }
+  ira::load_run<EC_PER_THREAD>(g.q + c0, c0, g.m, xv);
 #pragma unroll
   for (int r = 0; r < EC_PER_THREAD; ++r) s[r] = echo_power(xv[r], g.n, g.mode);      // a zero sample gives 0
 }
@@ -153,14 +140,8 @@ __device__ __forceinline__ void echo_chunk_scan(const double s[EC_PER_THREAD], i
     v[r] = v[r - 1] + (m0 + (double)r) * s[r];
   }
   const int lane = t & 63, wave = t >> 6;
-  double iw = w[EC_PER_THREAD - 1], iv = v[EC_PER_THREAD - 1];
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const double uw = __shfl_up(iw, o, 64), uv = __shfl_up(iv, o, 64);
-    if (lane >= o) { iw += uw; iv += uv; }
-  }
-  double ew = __shfl_up(iw, 1, 64), ev = __shfl_up(iv, 1, 64);              // sums over the lanes in front of this one
-  if (lane == 0) { ew = 0.0; ev = 0.0; }
+  double ew, ev;                                             // sums over the lanes in front of this one
+  const double iw = ira::wave_prefix(w[EC_PER_THREAD - 1], lane, ew), iv = ira::wave_prefix(v[EC_PER_THREAD - 1], lane, ev);
   if (lane == 63) { sh.wtot[parity][0][wave] = iw; sh.wtot[parity][1][wave] = iv; }
   __syncthreads();
   double pw = 0.0, pv = 0.0;
@@ -175,14 +156,9 @@ __device__ __forceinline__ void echo_chunk_scan(const double s[EC_PER_THREAD], i
 
 __device__ __forceinline__ double echo_ts(double w, double v, double fs) { return w == 0.0 ? 0.0 : v / (fs * w); }
 
-// float32 -> a key whose unsigned order is the float order (0 is below every key a value can take: "empty")
-__device__ __forceinline__ uint32_t echo_key(float f) {
-  const uint32_t b = __float_as_uint(f);
-  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
+// a curve key is ira::float_key; 0 is below every key a value can take: "empty", read back as NaN
 __device__ __forceinline__ float echo_unkey(uint32_t k) {
-  if (k == 0u) return __uint_as_float(0x7fc00000u);
-  return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
+  return k == 0u ? __uint_as_float(0x7fc00000u) : ira::float_unkey(k);
 }
 
 __device__ __forceinline__ double* echo_scratch(double* scratch, const EchoTables& T, int seg) {
@@ -215,7 +191,7 @@ __global__ __launch_bounds__(EC_THREADS) void echo_partial_kernel(EchoTables T, 
   if (stash != nullptr) {
     double* dst = stash + ((int64_t)seg * T.chunk_stride + c) * EC_CHUNK + EC_PER_THREAD * threadIdx.x;
 #pragma unroll
-    for (int r = 0; r < EC_PER_THREAD; r += 2) *reinterpret_cast<ec_d2*>(dst + r) = ec_d2{s[r], s[r + 1]};
+    for (int r = 0; r < EC_PER_THREAD; r += 2) *reinterpret_cast<ira::d2u*>(dst + r) = ira::d2u{s[r], s[r + 1]};
   }
   echo_chunk_scan(s, c0, sh, 0, w, v);
   if (threadIdx.x == EC_THREADS - 1) {
@@ -239,14 +215,9 @@ __global__ __launch_bounds__(IRA_WAVE) void echo_carry_kernel(EchoTables T, Echo
   double bw = 0.0, bv = 0.0;
   for (int64_t j0 = 0; j0 < nch; j0 += IRA_WAVE) {
     const int64_t j = j0 + lane;
-    double iw = j < nch ? sc[j] : 0.0, iv = j < nch ? sc[cs + j] : 0.0;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const double uw = __shfl_up(iw, o, 64), uv = __shfl_up(iv, o, 64);
-      if (lane >= o) { iw += uw; iv += uv; }
-    }
-    double ew = __shfl_up(iw, 1, 64), ev = __shfl_up(iv, 1, 64);
-    if (lane == 0) { ew = 0.0; ev = 0.0; }
+    double ew, ev;
+    const double iw = ira::wave_prefix(j < nch ? sc[j] : 0.0, lane, ew);
+    const double iv = ira::wave_prefix(j < nch ? sc[cs + j] : 0.0, lane, ev);
     if (j < nch) {
       sc[2 * cs + j] = bw + ew;
       sc[3 * cs + j] = bv + ev;
@@ -322,7 +293,7 @@ __global__ __launch_bounds__(EC_THREADS) void echo_emit_kernel(EchoTables T, Ech
     }
     if (want_curve) {
       if (++rem == g.step || r == EC_PER_THREAD - 1) {
-        if (have && k < ncurve) atomicMax(&crow[k], echo_key((float)run));
+        if (have && k < ncurve) atomicMax(&crow[k], ira::float_key((float)run));
         have = false;
         run = -INFINITY;
         if (rem == g.step) { rem = 0; ++k; }
@@ -331,28 +302,15 @@ __global__ __launch_bounds__(EC_THREADS) void echo_emit_kernel(EchoTables T, Ech
   }
   // first crossings: rare events, wave-uniform test first
   if (__any(f10 != INT64_MAX)) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const long long other = __shfl_xor(f10, o, 64);
-      f10 = other < f10 ? other : f10;
-    }
+    f10 = ira::wave_min(f10);
     if ((tid & 63) == 0) atomicMin(reinterpret_cast<unsigned long long*>(hdr), (unsigned long long)f10);
   }
   if (__any(f50 != INT64_MAX)) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const long long other = __shfl_xor(f50, o, 64);
-      f50 = other < f50 ? other : f50;
-    }
+    f50 = ira::wave_min(f50);
     if ((tid & 63) == 0) atomicMin(reinterpret_cast<unsigned long long*>(hdr) + 1, (unsigned long long)f50);
   }
   // the chunk's maximum, the smallest index on a tie: (greater value, then smaller index) is a total order
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const double ob = __shfl_xor(best, o, 64);
-    const long long oi = __shfl_xor(best_i, o, 64);
-    if (ob > best || (ob == best && oi < best_i)) { best = ob; best_i = oi; }
-  }
+  ira::wave_argmax(best, best_i);
   if ((tid & 63) == 0) { wave_best[tid >> 6] = best; wave_idx[tid >> 6] = best_i; }
   __syncthreads();
   if (tid == 0) {
@@ -380,11 +338,7 @@ __global__ __launch_bounds__(IRA_WAVE) void echo_fold_kernel(EchoTables T, EchoP
     const double b = sc[4 * cs + c], bi = sc[5 * cs + c];
     if (b > best || (b == best && bi < best_i)) { best = b; best_i = bi; }
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const double ob = __shfl_xor(best, o, 64), oi = __shfl_xor(best_i, o, 64);
-    if (ob > best || (ob == best && oi < best_i)) { best = ob; best_i = oi; }
-  }
+  ira::wave_argmax(best, best_i);
   if (lane == 0) {
     const double qnan = __longlong_as_double(0x7ff8000000000000ll);
     const unsigned long long* slot = reinterpret_cast<const unsigned long long*>(hdr);
@@ -405,7 +359,9 @@ __global__ __launch_bounds__(IRA_WAVE) void echo_fold_kernel(EchoTables T, EchoP
   }
 }
 
-inline int64_t ec_chunks(int64_t max_len) { return (max_len + EC_CHUNK - 1) / EC_CHUNK; }
+inline bool ec_shape_ok(int32_t nseg, int64_t max_len) {
+  return nseg >= 0 && nseg <= 65535 && max_len >= 0 && max_len <= EC_MAX_LEN;
+}
 
 // An integer-valued double in [lo, hi] (NaN fails).
 inline bool ec_whole(double v, double lo, double hi) { return v >= lo && v <= hi && v == floor(v); }
@@ -413,8 +369,8 @@ inline bool ec_whole(double v, double lo, double hi) { return v >= lo && v <= hi
 }  // namespace
 
 extern "C" int64_t ira_echo_scratch_doubles(int32_t nseg, int64_t max_len) {
-  if (nseg < 0 || nseg > 65535 || max_len < 0 || max_len > EC_MAX_LEN) return IRA_E_SIZE;
-  return (int64_t)nseg * (EC_HDR + EC_PER_CHUNK * ec_chunks(max_len));
+  if (!ec_shape_ok(nseg, max_len)) return IRA_E_SIZE;
+  return (int64_t)nseg * (EC_HDR + EC_PER_CHUNK * ira::ceil_div(max_len, EC_CHUNK));
 }
 
 extern "C" int32_t ira_echo_criterion(const float* x_dev, const int64_t* base_off_dev, const int64_t* base_len_dev,
@@ -427,7 +383,7 @@ extern "C" int32_t ira_echo_criterion(const float* x_dev, const int64_t* base_of
   IRA_CHECK_PTR(rec_dev);
   if (ncurve > 0) IRA_CHECK_PTR(curve_dev);
   if (nparam < 1 || nparam > IRA_ECHO_MAX_PARAMS) return IRA_E_SIZE;
-  if (nseg < 0 || nseg > 65535 || max_len < 0 || max_len > EC_MAX_LEN) return IRA_E_SIZE;
+  if (!ec_shape_ok(nseg, max_len)) return IRA_E_SIZE;
   if (ncurve < 0 || ncurve > EC_MAX_LEN) return IRA_E_SIZE;
   EchoParamTable P;
   for (int p = 0; p < IRA_ECHO_MAX_PARAMS; ++p) {
@@ -444,7 +400,7 @@ extern "C" int32_t ira_echo_criterion(const float* x_dev, const int64_t* base_of
   }
   if (nseg == 0) return IRA_OK;
   hipStream_t st = (hipStream_t)stream;
-  const int64_t chunks = ec_chunks(max_len);
+  const int64_t chunks = ira::ceil_div(max_len, EC_CHUNK);
   const EchoTables T{x_dev, base_off_dev, base_len_dev, chan_of_seg_dev, param_of_seg_dev, onset_dev, nparam, chunks};
   uint32_t* keys = ncurve > 0 ? reinterpret_cast<uint32_t*>(curve_dev) : nullptr;
   {

@@ -363,6 +363,7 @@ __global__ __launch_bounds__(NED_THREADS) void ned_record_kernel(const int64_t* 
     for (int q = 0; q < IRA_NED_MAX_THRESHOLDS; ++q)
       if (q < nthr && first[q] == none && (double)v >= thr.v[q]) first[q] = j;
   }
+  // not ira::wave_argmax: a lane that saw no finite value carries idx == none and must lose whatever its `best`
 #pragma unroll
   for (int s = 32; s > 0; s >>= 1) {
     const float ob = __shfl_xor(best, s, 64);

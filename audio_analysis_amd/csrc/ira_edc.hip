@@ -3,6 +3,7 @@
 // NumPy's (no fused multiply-add), see reference analyse/decay.py:173-260.
 #include "ira_common.h"
 #include "ira_log.h"
+#include "ira_reduce.h"
 
 namespace {
 
@@ -121,21 +122,9 @@ struct EdcShared {
   double wave_tot[2][EDC_WAVES];     // double-buffered by tile parity: one barrier per tile is enough
 };
 
-typedef float edc_f4 __attribute__((ext_vector_type(4), aligned(4)));   // 16-byte access, 4-byte alignment
-
 // The thread's 16 samples of a tile of tile_len valid samples (zeros beyond): local indices 16t .. 16t+15.
 __device__ __forceinline__ void tile_load(const float* __restrict__ src, int tile_len, float x[EDC_PER_THREAD]) {
-  const int i0 = EDC_PER_THREAD * threadIdx.x;
-  if (i0 + EDC_PER_THREAD <= tile_len) {
-#pragma unroll
-    for (int j = 0; j < EDC_PER_THREAD / 4; ++j) {
-      const edc_f4 v = *reinterpret_cast<const edc_f4*>(src + i0 + 4 * j);
-      x[4 * j] = v.x; x[4 * j + 1] = v.y; x[4 * j + 2] = v.z; x[4 * j + 3] = v.w;
-    }
-  } else {
-#pragma unroll
-    for (int r = 0; r < EDC_PER_THREAD; ++r) x[r] = (i0 + r < tile_len) ? src[i0 + r] : 0.0f;
-  }
+  ira::load_run<EDC_PER_THREAD>(src, 0, tile_len, x);
 }
 
 // Inclusive suffix sums (within the tile) of the squared samples at the thread's 16 positions.  parity = tile
@@ -154,14 +143,8 @@ __device__ __forceinline__ void tile_suffix_scan(const float x[EDC_PER_THREAD], 
   }
   // inclusive suffix scan of thread totals across the wave (towards higher lanes)
   const int lane = t & 63, wave = t >> 6;
-  double incl = s[0];
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const double up = __shfl_down(incl, o, 64);
-    if (lane + o < 64) incl += up;
-  }
-  double excl = __shfl_down(incl, 1, 64);  // sum over the lanes after this one
-  if (lane == 63) excl = 0.0;
+  double excl;                             // sum over the lanes after this one
+  const double incl = ira::wave_suffix(s[0], lane, excl);
   if (lane == 0) sh.wave_tot[parity][wave] = incl;
   __syncthreads();
   double later_waves = 0.0;
@@ -221,9 +204,9 @@ __global__ __launch_bounds__(128) void edc_tiles_from_parts_kernel(const int64_t
   }
 }
 
-// numpy.maximum semantics: a NaN operand gives NaN (fmax would drop it).  A NaN sample makes the reference's whole
-// curve NaN (decay.py:151-166), an infinite one NaN before it and the floor after it.
-__device__ __forceinline__ double np_max(double a, double b) { return (a != a) ? a : fmax(a, b); }
+// ira::np_max keeps a NaN: a NaN sample makes the reference's whole curve NaN (decay.py:151-166), an infinite one NaN
+// before it and the floor after it.
+using ira::np_max;
 
 // One wave per segment: exclusive prefix sums of the tile totals (in blocks of 64 with a shuffle scan; any fixed
 // association will do, every later kernel reads THESE carries) and the normaliser edc[0] = tot[T-1] + carry[T-1],
@@ -242,14 +225,8 @@ __global__ __launch_bounds__(IRA_WAVE) void edc_carry_kernel(const int64_t* __re
   for (int j0 = 0; j0 < ntiles; j0 += IRA_WAVE) {
     const int j = j0 + lane;
     const double tot = j < ntiles ? sc[j] : 0.0;
-    double incl = tot;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const double dn = __shfl_up(incl, o, 64);
-      if (lane >= o) incl += dn;
-    }
-    double excl = __shfl_up(incl, 1, 64);
-    if (lane == 0) excl = 0.0;
+    double excl;
+    const double incl = ira::wave_prefix(tot, lane, excl);
     const double carry = base + excl;
     if (j < ntiles) {
       sc[q + j] = carry;
@@ -307,8 +284,8 @@ __global__ __launch_bounds__(EDC_THREADS) void edc_emit_kernel(
     if (i0 + EDC_PER_THREAD <= tl) {
 #pragma unroll
       for (int jj = 0; jj < EDC_PER_THREAD / 4; ++jj) {
-        const edc_f4 v = {o[4 * jj], o[4 * jj + 1], o[4 * jj + 2], o[4 * jj + 3]};
-        *reinterpret_cast<edc_f4*>(dst + i0 + 4 * jj) = v;
+        const ira::f4u v = {o[4 * jj], o[4 * jj + 1], o[4 * jj + 2], o[4 * jj + 3]};
+        *reinterpret_cast<ira::f4u*>(dst + i0 + 4 * jj) = v;
       }
     } else {
 #pragma unroll
@@ -453,12 +430,7 @@ __global__ __launch_bounds__(XS_THREADS) void crossing_search_kernel(const float
 #pragma unroll
   for (int k = 0; k < FIT_MAX_TARGETS; ++k) {
     if (k < ntargets && __any(first[k] < n)) {          // wave-uniform: crossings are rare events
-      long long f = first[k];
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) {
-        const long long other = __shfl_xor(f, o, 64);
-        f = other < f ? other : f;
-      }
+      const long long f = ira::wave_min(first[k]);
       if ((tid & 63) == 0) atomicMin(&sl[k], (unsigned long long)f);
     }
   }
@@ -554,12 +526,7 @@ __global__ void curve_fit_kernel(const float* __restrict__ ybase, const int64_t*
 #pragma unroll
     for (int k = 0; k < FIT_MAX_TARGETS; ++k) {
       if (k < ntargets) {
-        long long f = first[k];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-          const long long other = __shfl_xor(f, o, 64);
-          f = other < f ? other : f;
-        }
+        const long long f = ira::wave_min(first[k]);
         if ((tid & 63) == 0 && f < n) atomicMin(&sh.idx[k], f);
       }
     }
@@ -869,11 +836,7 @@ __global__ __launch_bounds__(EDC_THREADS) __attribute__((amdgpu_waves_per_eu(4, 
       int f = tlen;
       for (int i = tid; i < tlen; i += EDC_THREADS)
         if (sh.db[i] <= t32) { f = i; break; }             // ascending per thread: its first hit is its smallest
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) {
-        const int other = __shfl_xor(f, o, 64);
-        f = other < f ? other : f;
-      }
+      f = ira::wave_min(f);
       if ((tid & 63) == 0 && f < tlen) atomicMin(&sh.found[k], (unsigned long long)f);
     }
     __syncthreads();

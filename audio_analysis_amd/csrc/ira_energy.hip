@@ -2,6 +2,7 @@
 // energy sums.  Nothing in the reference computes these; the host side is audio_analysis_amd/analyse/energy.py.
 // Compiled with -ffp-contract=off: the float64 products and sums must round one operation at a time, like NumPy's.
 #include "ira_common.h"
+#include "ira_reduce.h"
 
 namespace {
 
@@ -48,11 +49,7 @@ __global__ __launch_bounds__(ON_THREADS) void onset_search_kernel(const float* _
     if (i <= p && d * d >= thr) first = i;
   }
   if (__any(first != INT64_MAX)) {                    // wave-uniform
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const int64_t other = __shfl_xor(first, o, 64);
-      first = other < first ? other : first;
-    }
+    first = ira::wave_min(first);
     if ((tid & 63) == 0) atomicMin(reinterpret_cast<unsigned long long*>(&onset[s]), (unsigned long long)first);
   }
 }
@@ -65,9 +62,8 @@ __global__ __launch_bounds__(ON_THREADS) void onset_search_kernel(const float* _
 //   energy_fold_kernel    (1 wave / segment)   the records folded in a fixed order -> out
 // Every chunk boundary, every thread's share of a chunk and every reduction tree is a function of the segment's own length
 // only: a segment's result does not depend on the batch, its place in it or the alignment of its first sample (the loads
-// are 16-byte loads at 4-byte alignment, like tile_load in ira_edc.hip, so the order of the sums never changes with the
-// address).  Only a chunk that straddles a limit tests per sample which partition a sample falls in; every other chunk
-// lies in one partition and forms one sum.
+// are ira::load_quads, so the order of the sums never changes with the address).  Only a chunk that straddles a limit tests
+// per sample which partition a sample falls in; every other chunk lies in one partition and forms one sum.
 // ------------------------------------------------------------------------------------------------
 constexpr int EW_THREADS = 256;
 constexpr int EW_QUADS = 16;                                  // 16-byte loads per thread per chunk, all in flight together
@@ -77,27 +73,8 @@ constexpr int EW_MAX_LIMITS = 4;
 constexpr int EW_MAX_REC = EW_MAX_LIMITS + 2;                 // P_0 .. P_K, S1
 constexpr int64_t EW_MAX_LEN = (int64_t)1 << 31;
 
-typedef float ew_f4 __attribute__((ext_vector_type(4), aligned(4)));   // 16-byte access, 4-byte alignment
-
-// The thread's samples of a chunk of cnt valid samples, quad u = local samples 4 (tid + 256 u) .. + 3 (zeros past cnt).
-template <bool FULL>
-__device__ __forceinline__ void ew_load(const float* __restrict__ q, int cnt, ew_f4 a[EW_QUADS]) {
-#pragma unroll
-  for (int u = 0; u < EW_QUADS; ++u) {
-    const int b = 4 * (threadIdx.x + EW_THREADS * u);
-    if (FULL || b + 4 <= cnt) {
-      a[u] = *reinterpret_cast<const ew_f4*>(q + b);
-    } else {
-      a[u] = ew_f4{0.0f, 0.0f, 0.0f, 0.0f};
-      if (b < cnt) a[u].x = q[b];
-      if (b + 1 < cnt) a[u].y = q[b + 1];
-      if (b + 2 < cnt) a[u].z = q[b + 2];
-    }
-  }
-}
-
 // One partition: acc = sum e, s1 = sum (local index) e, in the thread's fixed sample order.
-__device__ __forceinline__ void ew_sum_one(const ew_f4 a[EW_QUADS], double& acc, double& s1) {
+__device__ __forceinline__ void ew_sum_one(const ira::f4u a[EW_QUADS], double& acc, double& s1) {
 #pragma unroll
   for (int u = 0; u < EW_QUADS; ++u) {
     const int b = 4 * (threadIdx.x + EW_THREADS * u);
@@ -112,7 +89,7 @@ __device__ __forceinline__ void ew_sum_one(const ew_f4 a[EW_QUADS], double& acc,
 }
 
 // A chunk that straddles a limit (one or two chunks per limit and segment): every sample goes to partition
-// #{k : N_k <= c0 + local index}.  The same samples in the same order as ew_load + ew_sum_one, read one quad at a time.
+// #{k : N_k <= c0 + local index}.  The same samples in the same order as load_quads + ew_sum_one, read one quad at a time.
 __device__ __forceinline__ void ew_sum_split(const float* __restrict__ q, int cnt, int64_t c0,
                                              const int64_t lim[EW_MAX_LIMITS], int nlim, double acc[EW_MAX_LIMITS + 1],
                                              double& s1) {
@@ -165,9 +142,9 @@ __global__ __launch_bounds__(EW_THREADS) void energy_partial_kernel(
   if (split) {                                                 // workgroup-uniform
     ew_sum_split(q, cnt, c0, lim, nlim, acc, s1);
   } else {
-    ew_f4 a[EW_QUADS];
-    if (cnt == EW_CHUNK) ew_load<true>(q, cnt, a);
-    else ew_load<false>(q, cnt, a);
+    ira::f4u a[EW_QUADS];
+    if (cnt == EW_CHUNK) ira::load_quads<EW_THREADS, EW_QUADS, true>(q, cnt, a);
+    else ira::load_quads<EW_THREADS, EW_QUADS, false>(q, cnt, a);
     double one = 0.0;
     ew_sum_one(a, one, s1);
 #pragma unroll
@@ -201,7 +178,7 @@ __global__ __launch_bounds__(EW_THREADS) void energy_partial_kernel(
   }
 }
 
-// One wave per segment: lane l folds chunks l, l + 64, ... in ascending order, then a fixed butterfly across the lanes.
+// One wave per segment: ira::fold_records over the segment's records.
 __global__ __launch_bounds__(IRA_WAVE) void energy_fold_kernel(const int64_t* __restrict__ base_len,
                                                                const int32_t* __restrict__ chan_of_seg,
                                                                const int64_t* __restrict__ onset, int nseg, int nlim,
@@ -209,20 +186,10 @@ __global__ __launch_bounds__(IRA_WAVE) void energy_fold_kernel(const int64_t* __
                                                                double* __restrict__ out) {
   const int seg = blockIdx.x;
   if (seg >= nseg) return;
-  const int64_t n = base_len[seg] - onset[chan_of_seg[seg]];
-  const int64_t nch = n > 0 ? (n + EW_CHUNK - 1) / EW_CHUNK : 0;
-  const int nrec = nlim + 2;
-  const double* rec = scratch + (int64_t)seg * chunk_stride * nrec;
-  const int lane = threadIdx.x;
-  for (int r = 0; r < nrec; ++r) {
-    double v = 0.0;
-    for (int64_t c = lane; c < nch; c += IRA_WAVE) v += rec[c * nrec + r];
-    v = ira::wave_sum(v);
-    if (lane == 0) out[(int64_t)seg * nrec + r] = v;
-  }
+  ira::fold_records(scratch, seg, base_len[seg] - onset[chan_of_seg[seg]], EW_CHUNK, chunk_stride, nlim + 2, out);
 }
 
-static inline int64_t ew_chunks(int64_t max_len) { return (max_len + EW_CHUNK - 1) / EW_CHUNK; }
+inline bool ew_shape_ok(int32_t nseg, int64_t max_len) { return nseg <= 65535 && max_len >= 0 && max_len <= EW_MAX_LEN; }
 
 }  // namespace
 
@@ -236,7 +203,7 @@ extern "C" int32_t ira_onset_index(const float* x_dev, const int64_t* off_dev, c
   if (nseg > 65535 || max_len < 0 || max_len > 0xFFFFFFFFll) return IRA_E_SIZE;
   hipStream_t st = (hipStream_t)stream;
   onset_init_kernel<<<(nseg + 255) / 256, 256, 0, st>>>(peak_dev, nseg, onset_dev);
-  const int64_t chunks = max_len > 0 ? (max_len + ON_CHUNK - 1) / ON_CHUNK : 0;
+  const int64_t chunks = ira::ceil_div(max_len, ON_CHUNK);
   if (chunks > 0)
     onset_search_kernel<<<dim3((unsigned)chunks, nseg), ON_THREADS, 0, st>>>(x_dev, off_dev, len_dev, peak_dev,
                                                                              peak_abs_dev, rel_energy, onset_dev);
@@ -244,9 +211,8 @@ extern "C" int32_t ira_onset_index(const float* x_dev, const int64_t* off_dev, c
 }
 
 extern "C" int64_t ira_energy_scratch_doubles(int32_t nseg, int64_t max_len, int32_t nlim) {
-  if (nseg < 0 || nseg > 65535 || max_len < 0 || max_len > EW_MAX_LEN || nlim < 1 || nlim > EW_MAX_LIMITS)
-    return IRA_E_SIZE;
-  return (int64_t)nseg * ew_chunks(max_len) * (nlim + 2);
+  if (nseg < 0 || !ew_shape_ok(nseg, max_len) || nlim < 1 || nlim > EW_MAX_LIMITS) return IRA_E_SIZE;
+  return (int64_t)nseg * ira::ceil_div(max_len, EW_CHUNK) * (nlim + 2);
 }
 
 extern "C" int32_t ira_energy_windows(const float* x_dev, const int64_t* base_off_dev, const int64_t* base_len_dev,
@@ -257,9 +223,9 @@ extern "C" int32_t ira_energy_windows(const float* x_dev, const int64_t* base_of
   IRA_CHECK_PTR(onset_dev); IRA_CHECK_PTR(limits_dev); IRA_CHECK_PTR(scratch_dev); IRA_CHECK_PTR(out_dev);
   if (nlim < 1 || nlim > EW_MAX_LIMITS) return IRA_E_SIZE;
   if (nseg <= 0) return nseg == 0 ? IRA_OK : IRA_E_SIZE;
-  if (nseg > 65535 || max_len < 0 || max_len > EW_MAX_LEN) return IRA_E_SIZE;
+  if (!ew_shape_ok(nseg, max_len)) return IRA_E_SIZE;
   hipStream_t st = (hipStream_t)stream;
-  const int64_t chunks = ew_chunks(max_len);
+  const int64_t chunks = ira::ceil_div(max_len, EW_CHUNK);
   if (chunks > 0)
     energy_partial_kernel<<<dim3((unsigned)chunks, nseg), EW_THREADS, 0, st>>>(
         x_dev, base_off_dev, base_len_dev, chan_of_seg_dev, onset_dev, limits_dev, nlim, chunks, scratch_dev);

@@ -3,6 +3,7 @@
 // Nothing in the reference computes these; the host side, with the definitions, is audio_analysis_amd/analyse/harmonics.py.
 // Contraction is off (build.py): a segment sample is one float64 product rounded once to float32, like NumPy's.
 #include "ira_common.h"
+#include "ira_reduce.h"
 
 namespace {
 
@@ -12,9 +13,6 @@ constexpr int HW_TILE = HW_THREADS * HW_PER_THREAD;           // 1024 samples of
 constexpr int HARM_MAX_SEG = 1 << 21;                         // the longest response the deconvolution makes
 constexpr int HARM_MAX_BANDS = 4096;
 constexpr int HARM_MAX_BINS = (1 << 20) + 1;
-
-typedef float hw_f4 __attribute__((ext_vector_type(4), aligned(4)));     // 16-byte access, 4-byte alignment
-typedef double hw_d2 __attribute__((ext_vector_type(2), aligned(8)));    // 16-byte access, 8-byte alignment
 
 // ------------------------------------------------------------------------------------------------
 // harm_windows_kernel (tiles x rows): row r = c * nharm + k of out is
@@ -52,15 +50,15 @@ __global__ __launch_bounds__(HW_THREADS) void harm_windows_kernel(const float* _
     if (j >= n) j %= n;                                       // a row longer than its channel's buffer
   }
   if (left >= HW_PER_THREAD && j + HW_PER_THREAD <= n) {
-    const hw_f4 a = *reinterpret_cast<const hw_f4*>(src + j);
-    const hw_d2 w0 = *reinterpret_cast<const hw_d2*>(win + i0);
-    const hw_d2 w1 = *reinterpret_cast<const hw_d2*>(win + i0 + 2);
-    hw_f4 v;
+    const ira::f4u a = *reinterpret_cast<const ira::f4u*>(src + j);
+    const ira::d2u w0 = *reinterpret_cast<const ira::d2u*>(win + i0);
+    const ira::d2u w1 = *reinterpret_cast<const ira::d2u*>(win + i0 + 2);
+    ira::f4u v;
     v.x = (float)((double)a.x * w0.x);
     v.y = (float)((double)a.y * w0.y);
     v.z = (float)((double)a.z * w1.x);
     v.w = (float)((double)a.w * w1.y);
-    *reinterpret_cast<hw_f4*>(dst) = v;
+    *reinterpret_cast<ira::f4u*>(dst) = v;
   } else {
     for (int r = 0; r < HW_PER_THREAD && r < left; ++r) {
       dst[r] = (float)((double)src[j] * win[i0 + r]);
@@ -100,19 +98,19 @@ __global__ __launch_bounds__(BP_THREADS) void harm_band_powers_kernel(const doub
     if (lane == 0) *dst = __builtin_nan("");
     return;
   }
-  const hw_d2* z = reinterpret_cast<const hw_d2*>(spec) + ira::uniform(spec_off[row]) + lo;
+  const ira::d2u* z = reinterpret_cast<const ira::d2u*>(spec) + ira::uniform(spec_off[row]) + lo;
   double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
   int b = lane;
   for (; b + 3 * IRA_WAVE < cnt; b += 4 * IRA_WAVE) {
-    const hw_d2 v0 = z[b], v1 = z[b + IRA_WAVE], v2 = z[b + 2 * IRA_WAVE], v3 = z[b + 3 * IRA_WAVE];
+    const ira::d2u v0 = z[b], v1 = z[b + IRA_WAVE], v2 = z[b + 2 * IRA_WAVE], v3 = z[b + 3 * IRA_WAVE];
     a0 += v0.x * v0.x + v0.y * v0.y;
     a1 += v1.x * v1.x + v1.y * v1.y;
     a2 += v2.x * v2.x + v2.y * v2.y;
     a3 += v3.x * v3.x + v3.y * v3.y;
   }
-  if (b < cnt) { const hw_d2 v = z[b]; a0 += v.x * v.x + v.y * v.y; b += IRA_WAVE; }
-  if (b < cnt) { const hw_d2 v = z[b]; a1 += v.x * v.x + v.y * v.y; b += IRA_WAVE; }
-  if (b < cnt) { const hw_d2 v = z[b]; a2 += v.x * v.x + v.y * v.y; }
+  if (b < cnt) { const ira::d2u v = z[b]; a0 += v.x * v.x + v.y * v.y; b += IRA_WAVE; }
+  if (b < cnt) { const ira::d2u v = z[b]; a1 += v.x * v.x + v.y * v.y; b += IRA_WAVE; }
+  if (b < cnt) { const ira::d2u v = z[b]; a2 += v.x * v.x + v.y * v.y; }
   const double s = ira::wave_sum((a0 + a1) + (a2 + a3));
   if (lane == 0) *dst = s / (double)cnt;
 }

@@ -15,6 +15,7 @@
 // address.  No atomics; every reduction tree is fixed.
 #include "ira_common.h"
 #include "ira_log.h"
+#include "ira_reduce.h"
 
 namespace {
 
@@ -150,11 +151,7 @@ __device__ __forceinline__ double lb_sum(double v, LbShared& sh) {
 }
 
 __device__ __forceinline__ long long lb_min(long long v, LbShared& sh) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const long long other = __shfl_xor(v, o, 64);
-    v = other < v ? other : v;
-  }
+  v = ira::wave_min(v);
   __syncthreads();
   if ((threadIdx.x & 63) == 0) sh.wi[threadIdx.x >> 6] = v;
   __syncthreads();
@@ -166,12 +163,7 @@ __device__ __forceinline__ long long lb_min(long long v, LbShared& sh) {
 
 // (largest value, its first index); values are finite
 __device__ __forceinline__ void lb_argmax(double& v, long long& idx, LbShared& sh) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const double ov = __shfl_xor(v, o, 64);
-    const long long oi = __shfl_xor(idx, o, 64);
-    if (ov > v || (ov == v && oi < idx)) { v = ov; idx = oi; }
-  }
+  ira::wave_argmax(v, idx);
   __syncthreads();
   if ((threadIdx.x & 63) == 0) { sh.w[threadIdx.x >> 6] = v; sh.wi[threadIdx.x >> 6] = idx; }
   __syncthreads();
@@ -409,8 +401,6 @@ __global__ __launch_bounds__(LB_THREADS) void lundeby_estimate_kernel(
 // and leave with 16-byte stores.  A band row may be written over the signal it is read from: a workgroup has read its chunk
 // before it writes it, and no other workgroup touches that chunk.
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ double lb_np_max(double a, double b) { return (a != a) ? a : fmax(a, b); }
-
 __global__ __launch_bounds__(LB_THREADS) void edc_truncated_kernel(
     const float* x, const int64_t* __restrict__ base_off, const int64_t* __restrict__ base_len,
     const int32_t* __restrict__ chan_of_seg, const int64_t* __restrict__ start, const int32_t* __restrict__ blk_size,
@@ -435,7 +425,7 @@ __global__ __launch_bounds__(LB_THREADS) void edc_truncated_kernel(
   __syncthreads();
   const double* base = suffix + ira::uniform(blk_off[row]);
   const double first = ira::uniform(rec_in[(int64_t)row * IRA_LUNDEBY_DOUBLES + 14]);
-  const double norm = lb_np_max(first, eps);
+  const double norm = ira::np_max(first, eps);
   const bool fast = norm > 1e-300 && norm < 1e300;
   const double lnorm = fast ? ira::log2_table(norm, ltab) : 0.0;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -450,14 +440,8 @@ __global__ __launch_bounds__(LB_THREADS) void edc_truncated_kernel(
       const double d = (double)stage[b0 + i];
       acc = d * d + acc;
     }
-    double incl = acc;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const double up = __shfl_down(incl, o, 64);
-      if (lane + o < 64) incl += up;
-    }
-    double run = __shfl_down(incl, 1, 64);            // the lanes after this one
-    if (lane == 63) run = 0.0;
+    double run;                                       // the lanes after this one
+    ira::wave_suffix(acc, lane, run);
     const double bj = base[j0 + jl];
     for (int i = hi - 1; i >= lo; --i) {
       const double d = (double)stage[b0 + i];
@@ -465,10 +449,10 @@ __global__ __launch_bounds__(LB_THREADS) void edc_truncated_kernel(
       // edc[0] sums the same energies in another order (the estimate's E[0] + base[0]): a later sample may come out one
       // float64 rounding above it, and is held to it, so that no sample of the curve lies above 0 dB
       const double sum = (c0 + b0 + i == 0) ? first : fmin(run + bj, first);
-      const double v = lb_np_max(sum, eps);
+      const double v = ira::np_max(sum, eps);
       const double db = (fast && v > 1e-300 && v < 1e300) ? 3.0102999566398120 * (ira::log2_table(v, ltab) - lnorm)
                                                            : 10.0 * log10(v / norm);
-      stage[b0 + i] = (float)lb_np_max(db, floor_db);
+      stage[b0 + i] = (float)ira::np_max(db, floor_db);
     }
   }
   __syncthreads();

@@ -3,6 +3,7 @@
 // e = float64(x)^2.  Nothing in the reference computes these; the host side is audio_analysis_amd/analyse/sti.py.
 // Contraction stays on: nothing here is compared bit for bit with NumPy, only with itself.
 #include "ira_common.h"
+#include "ira_reduce.h"
 
 namespace {
 
@@ -10,7 +11,7 @@ namespace {
 //   mtf_partial_kernel (chunks x rows)  one MT_CHUNK-sample chunk per workgroup -> one record of 2 nf + 1 doubles
 //   mtf_fold_kernel    (1 wave / row)   the records folded in a fixed order -> out
 // Thread tid of a chunk that starts at sample c0 holds quads u < MT_QUADS: samples n = c0 + 4 tid + 1024 u + r, r < 4 (the
-// layout of ira_energy.hip: 16-byte loads at 4-byte alignment, so the order of the sums never changes with the address).
+// layout of ira_energy.hip: ira::load_quads, so the order of the sums never changes with the address).
 // The phasor of sample n is the product of three unit phasors, each evaluated directly from a phase reduced to a fraction
 // of a turn (mt_cis), never by a recurrence:
 //   cis(w n) = base(c0 + 4 tid) * stride(1024 u) * quad(r)
@@ -31,8 +32,6 @@ constexpr int MT_TAB = MT_QUADS + 4;                          // per frequency: 
 constexpr int MT_MAX_REC = 2 * IRA_MTF_MAX_FREQS + 1;         // E, A_0, B_0, ...
 constexpr int64_t MT_MAX_LEN = (int64_t)1 << 31;
 static_assert(MT_CHUNK == IRA_MTF_CHUNK, "include/ira.h states the chunk size");
-
-typedef float mt_f4 __attribute__((ext_vector_type(4), aligned(4)));   // 16-byte access, 4-byte alignment
 
 // cis(2 pi frac(w n)), n an integer below 2^32 held exactly in float64.  p + lo is w n exactly (the FMA recovers what the
 // product rounded away); the whole turns leave p before anything is evaluated, so the phase error is that of one rounding
@@ -70,22 +69,16 @@ __global__ __launch_bounds__(MT_THREADS) void mtf_partial_kernel(const float* __
   }
 
   double e[MT_QUADS][4];
+  {
+    ira::f4u a[MT_QUADS];
+    ira::load_quads<MT_THREADS, MT_QUADS, false>(q, cnt, a);
 #pragma unroll
-  for (int u = 0; u < MT_QUADS; ++u) {
-    const int b = 4 * (tid + MT_THREADS * u);
-    mt_f4 a;
-    if (b + 4 <= cnt) {
-      a = *reinterpret_cast<const mt_f4*>(q + b);
-    } else {
-      a = mt_f4{0.0f, 0.0f, 0.0f, 0.0f};
-      if (b < cnt) a.x = q[b];
-      if (b + 1 < cnt) a.y = q[b + 1];
-      if (b + 2 < cnt) a.z = q[b + 2];
-    }
+    for (int u = 0; u < MT_QUADS; ++u) {
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const double d = (double)a[r];
-      e[u][r] = d * d;
+      for (int r = 0; r < 4; ++r) {
+        const double d = (double)a[u][r];
+        e[u][r] = d * d;
+      }
     }
   }
   const int lane = tid & 63, wave = tid >> 6;
@@ -136,34 +129,22 @@ __global__ __launch_bounds__(MT_THREADS) void mtf_partial_kernel(const float* __
   }
 }
 
-// One wave per row: lane l folds chunks l, l + 64, ... in ascending order, then a fixed butterfly across the lanes.
+// One wave per row: ira::fold_records over the row's records.
 __global__ __launch_bounds__(IRA_WAVE) void mtf_fold_kernel(const int64_t* __restrict__ len, int nseg, int nf,
                                                             int64_t chunk_stride, const double* __restrict__ scratch,
                                                             double* __restrict__ out) {
   const int seg = blockIdx.x;
   if (seg >= nseg) return;
-  const int64_t n = len[seg];
-  int64_t nch = n > 0 ? (n + MT_CHUNK - 1) / MT_CHUNK : 0;
-  if (nch > chunk_stride) nch = chunk_stride;                 // a row longer than max_len: never read past its records
-  const int nrec = 2 * nf + 1;
-  const double* rec = scratch + (int64_t)seg * chunk_stride * nrec;
-  const int lane = threadIdx.x;
-  for (int r = 0; r < nrec; ++r) {
-    double v = 0.0;
-    for (int64_t c = lane; c < nch; c += IRA_WAVE) v += rec[c * nrec + r];
-    v = ira::wave_sum(v);
-    if (lane == 0) out[(int64_t)seg * nrec + r] = v;
-  }
+  ira::fold_records(scratch, seg, len[seg], MT_CHUNK, chunk_stride, 2 * nf + 1, out);
 }
 
-static inline int64_t mt_chunks(int64_t max_len) { return (max_len + MT_CHUNK - 1) / MT_CHUNK; }
+inline bool mt_shape_ok(int32_t nseg, int64_t max_len) { return nseg <= 65535 && max_len >= 0 && max_len <= MT_MAX_LEN; }
 
 }  // namespace
 
 extern "C" int64_t ira_mtf_scratch_doubles(int32_t nseg, int64_t max_len, int32_t nf) {
-  if (nseg < 0 || nseg > 65535 || max_len < 0 || max_len > MT_MAX_LEN || nf < 1 || nf > IRA_MTF_MAX_FREQS)
-    return IRA_E_SIZE;
-  return (int64_t)nseg * mt_chunks(max_len) * (2 * nf + 1);
+  if (nseg < 0 || !mt_shape_ok(nseg, max_len) || nf < 1 || nf > IRA_MTF_MAX_FREQS) return IRA_E_SIZE;
+  return (int64_t)nseg * ira::ceil_div(max_len, MT_CHUNK) * (2 * nf + 1);
 }
 
 extern "C" int32_t ira_mtf_sums(const float* x_dev, const int64_t* off_dev, const int64_t* len_dev, const double* w_dev,
@@ -173,9 +154,9 @@ extern "C" int32_t ira_mtf_sums(const float* x_dev, const int64_t* off_dev, cons
   IRA_CHECK_PTR(scratch_dev); IRA_CHECK_PTR(out_dev);
   if (nf < 1 || nf > IRA_MTF_MAX_FREQS) return IRA_E_SIZE;
   if (nseg <= 0) return nseg == 0 ? IRA_OK : IRA_E_SIZE;
-  if (nseg > 65535 || max_len < 0 || max_len > MT_MAX_LEN) return IRA_E_SIZE;
+  if (!mt_shape_ok(nseg, max_len)) return IRA_E_SIZE;
   hipStream_t st = (hipStream_t)stream;
-  const int64_t chunks = mt_chunks(max_len);
+  const int64_t chunks = ira::ceil_div(max_len, MT_CHUNK);
   if (chunks > 0)
     mtf_partial_kernel<<<dim3((unsigned)chunks, nseg), MT_THREADS, 0, st>>>(x_dev, off_dev, len_dev, w_dev, nf, chunks,
                                                                            scratch_dev);

@@ -6,6 +6,7 @@
 
 #include "ira_fft_reg.h"
 #include "ira_log.h"
+#include "ira_reduce.h"
 
 namespace {
 
@@ -168,14 +169,8 @@ constexpr int UW_TILE = UW_THREADS * UW_PER;
 // by a shuffle scan, then the wave totals in order.  ONE barrier inside: every thread of the workgroup calls it.
 __device__ __forceinline__ double unwrap_scan(double (&c)[UW_PER], double carry, double* wave_tot, int lane, int wave) {
   c[1] += c[0]; c[2] += c[1]; c[3] += c[2];
-  double incl = c[3];
-#pragma unroll
-  for (int o2 = 1; o2 < 64; o2 <<= 1) {
-    const double dn = __shfl_up(incl, o2, 64);
-    if (lane >= o2) incl += dn;
-  }
-  double excl = __shfl_up(incl, 1, 64);
-  if (lane == 0) excl = 0.0;
+  double excl;
+  const double incl = ira::wave_prefix(c[3], lane, excl);
   if (lane == 63) wave_tot[wave] = incl;
   __syncthreads();
   double before = 0.0;
@@ -463,12 +458,8 @@ __global__ __launch_bounds__(OS_THREADS) void order_stats_kernel(const double* _
       const int l = leader[r];
       const long long rem = remaining[r];
       const long long c = tid < 256 ? (long long)hist[l][tid] : 0ll;
-      long long incl = c;
-#pragma unroll
-      for (int o2 = 1; o2 < 64; o2 <<= 1) {
-        const long long up = __shfl_up(incl, o2, 64);
-        if (lane >= o2) incl += up;
-      }
+      long long in_wave;                                  // unused: the exclusive count below spans the four waves
+      long long incl = ira::wave_prefix(c, lane, in_wave);
       if (tid < 256 && lane == 63) scan_tot[tid >> 6] = incl;
       __syncthreads();
       if (tid < 256) {
@@ -517,8 +508,7 @@ __device__ __forceinline__ void stats_bin(StatsAcc& a, long long k, float db, do
   a.near_db = nk < a.near ? db : a.near_db;
   a.near = nk < a.near ? nk : a.near;
   if (f >= f_min && f <= f_max) {
-    uint32_t uu = __float_as_uint(db);
-    uu = (uu & 0x80000000u) ? ~uu : (uu | 0x80000000u);  // monotone map float -> uint
+    uint32_t uu = ira::float_key(db);
     if (db != db) uu = 0xFFFFFFFFu;                      // numpy.argmax: the first NaN wins, whatever its sign or payload
     const unsigned long long key = ((unsigned long long)uu << 32) | (unsigned long long)(0xFFFFFFFFu - (uint32_t)k);
     a.best = key > a.best ? key : a.best;

@@ -4,6 +4,7 @@
 // Compiled with -ffp-contract=off.  The lag products are written as fma() on purpose: the product of two float32 samples is
 // exact in float64 (48 significant bits), so fma(l, r, acc) and acc + l * r round identically, bit for bit.
 #include "ira_common.h"
+#include "ira_reduce.h"
 
 namespace {
 
@@ -49,7 +50,7 @@ inline int xc_lags_per_thread(int nlag) {
   }
   return best;
 }
-inline int64_t xc_chunks(int64_t max_len) { return (max_len + XC_CHUNK - 1) / XC_CHUNK; }
+inline bool xc_shape_ok(int32_t nseg, int64_t max_len) { return nseg <= 65535 && max_len >= 0 && max_len <= XC_MAX_LEN; }
 // LDS doubles: l rows | r rows + W; the partials ([nsub][W] <= 512 * 13 doubles, then El / Er per wave) reuse the space
 inline size_t xc_lds_doubles(int w) { return (size_t)2 * XC_CHUNK + w; }
 
@@ -193,7 +194,8 @@ __global__ __launch_bounds__(XC_THREADS) void xcorr_partial_kernel(
 }
 
 // One wave per (segment, partition): lane q owns entries q, q + 64, ... of the record and adds the partition's chunks in
-// ascending order (coalesced reads, no cross-lane step).  A partition without samples gives zeros.
+// ascending order (coalesced reads, no cross-lane step).  A partition without samples gives zeros.  Not ira::fold_records:
+// a lane owns entries, not chunks, and the chunk range comes from the partition's limits.
 __global__ __launch_bounds__(IRA_WAVE) void xcorr_fold_kernel(
     const int64_t* __restrict__ len, const int32_t* __restrict__ lchan, const int32_t* __restrict__ rchan,
     const int64_t* __restrict__ onset, const int64_t* __restrict__ limits, int nlim, int T, int64_t rec_stride,
@@ -220,10 +222,10 @@ __global__ __launch_bounds__(IRA_WAVE) void xcorr_fold_kernel(
 }  // namespace
 
 extern "C" int64_t ira_xcorr_scratch_doubles(int32_t nseg, int64_t max_len, int32_t nlim, int32_t max_lag) {
-  if (nseg < 0 || nseg > 65535 || max_len < 0 || max_len > XC_MAX_LEN || nlim < 1 || nlim > XC_MAX_LIMITS ||
-      max_lag < 1 || max_lag > IRA_XCORR_MAX_LAG)
+  if (nseg < 0 || !xc_shape_ok(nseg, max_len) || nlim < 1 || nlim > XC_MAX_LIMITS || max_lag < 1 ||
+      max_lag > IRA_XCORR_MAX_LAG)
     return IRA_E_SIZE;
-  return (int64_t)nseg * (xc_chunks(max_len) + nlim) * (2 * max_lag + 3);
+  return (int64_t)nseg * (ira::ceil_div(max_len, XC_CHUNK) + nlim) * (2 * max_lag + 3);
 }
 
 extern "C" int32_t ira_xcorr_windows(const float* x_dev, const int64_t* l_off_dev, const int64_t* r_off_dev,
@@ -237,9 +239,9 @@ extern "C" int32_t ira_xcorr_windows(const float* x_dev, const int64_t* l_off_de
   if (nlim < 1 || nlim > XC_MAX_LIMITS) return IRA_E_SIZE;
   if (max_lag < 1 || max_lag > IRA_XCORR_MAX_LAG) return IRA_E_SIZE;
   if (nseg <= 0) return nseg == 0 ? IRA_OK : IRA_E_SIZE;
-  if (nseg > 65535 || max_len < 0 || max_len > XC_MAX_LEN) return IRA_E_SIZE;
+  if (!xc_shape_ok(nseg, max_len)) return IRA_E_SIZE;
   hipStream_t st = (hipStream_t)stream;
-  const int64_t chunks = xc_chunks(max_len);
+  const int64_t chunks = ira::ceil_div(max_len, XC_CHUNK);
   const int64_t rec_stride = chunks + nlim;
   const int nlag = 2 * max_lag + 1;
   const int lpt = xc_lags_per_thread(nlag);

@@ -621,6 +621,13 @@ class Engine:
               "ira_edc_fits")
         return views + (out, edc_off)
 
+    def _scratch(self, sizer: str, *shape):
+        """Float64 device scratch of the size the library's entry point `sizer` states for `shape` (a negative answer is
+        its status code)."""
+        nsc = int(getattr(self.lib, sizer)(*shape))
+        check(min(nsc, 0), sizer)
+        return self.empty(nsc, self.torch.float64)
+
     def _fit_outputs(self, n: int, ranges: Sequence[Tuple[float, float]], cross: Sequence[float]):
         """What ira_edc_fits and ira_curve_fits share: the record arrays fit (n, nranges, 8) and cr (n, ncross) (float64
         device, at least one record each), the fit ranges and crossing levels as C double arrays, and the result views
@@ -662,9 +669,7 @@ class Engine:
             raise ValueError("limits must be (nseg, nlim)")
         nlim = int(limits.shape[1])
         max_len = int(base_len.max()) if nseg else 0
-        nsc = int(self.lib.ira_energy_scratch_doubles(nseg, max_len, nlim))
-        check(min(nsc, 0), "ira_energy_scratch_doubles")
-        scratch = self.empty(nsc, t.float64)
+        scratch = self._scratch("ira_energy_scratch_doubles", nseg, max_len, nlim)
         out = self.empty(nseg * (nlim + 2), t.float64)
         d_off, d_len, d_ch, d_lim = self.job_tables(base_off, base_len, np.ascontiguousarray(chan_of_seg, np.int32),
                                                     limits.reshape(-1))
@@ -706,9 +711,7 @@ class Engine:
             steps = np.where(step > 0, np.ceil(m_up / np.where(step > 0, step, 1.0)), 0.0)
         max_len = int(np.nan_to_num(m_up).max()) if nseg else 0
         ncurve = int(np.nan_to_num(steps).max()) if nseg else 0
-        nsc = int(self.lib.ira_echo_scratch_doubles(nseg, max_len))
-        check(min(nsc, 0), "ira_echo_scratch_doubles")
-        scratch = self.empty(nsc, t.float64)
+        scratch = self._scratch("ira_echo_scratch_doubles", nseg, max_len)
         stash = self.empty(nseg * (-(-max_len // ECHO_CHUNK)) * ECHO_CHUNK, t.float64) if self.echo_stash else None
         rec = self.empty(nseg * ECHO_DOUBLES, t.float64)
         curve = self.empty(nseg * ncurve, t.float32)
@@ -822,10 +825,8 @@ class Engine:
             raise ValueError("l_off, r_off, seg_len must be (nseg,) and limits (nseg, nlim)")
         nlim, max_lag = int(limits.shape[1]), int(max_lag)
         max_len = int(seg_len.max()) if nseg else 0
-        nsc = int(self.lib.ira_xcorr_scratch_doubles(nseg, max_len, nlim, max_lag))
-        check(min(nsc, 0), "ira_xcorr_scratch_doubles")
+        scratch = self._scratch("ira_xcorr_scratch_doubles", nseg, max_len, nlim, max_lag)
         nrec = 2 * max_lag + 3
-        scratch = self.empty(nsc, t.float64)
         out = self.empty(nseg * (nlim + 1) * nrec, t.float64)
         d_lo, d_ro, d_len, d_lc, d_rc, d_lim = self.job_tables(
             l_off, r_off, seg_len, np.ascontiguousarray(lchan_of_seg, np.int32),
@@ -853,10 +854,8 @@ class Engine:
         if not np.all((w >= 0.0) & (w <= 0.5)):
             raise ValueError("modulation frequencies must lie in 0 .. 0.5 turns per sample")
         max_len = int(seg_len.max()) if nseg else 0
-        nsc = int(self.lib.ira_mtf_scratch_doubles(nseg, max_len, nf))
-        check(min(nsc, 0), "ira_mtf_scratch_doubles")
+        scratch = self._scratch("ira_mtf_scratch_doubles", nseg, max_len, nf)
         nrec = 2 * nf + 1
-        scratch = self.empty(nsc, t.float64)
         out = self.empty(nseg * nrec, t.float64)
         d_off, d_len, d_w = self.job_tables(seg_off, seg_len, w.reshape(-1))
         check(self.lib.ira_mtf_sums(_ptr(x_dev), _ptr(d_off), _ptr(d_len), _ptr(d_w), nseg, max_len, nf, _ptr(scratch),

@@ -306,6 +306,48 @@ def test_bit_identical_whatever_the_batch():
     assert np.array_equal(many[200].view(np.uint64), alone[0].view(np.uint64))
 
 
+def _windows_raw(eng, flat_dev, off, length, limits, max_len):
+    """ira_energy_windows through the bound library, onsets 0, with the caller's max_len and a scratch of exactly
+    ira_energy_scratch_doubles(nseg, max_len, nlim) doubles carved from the front of a larger NaN-filled buffer
+    (Engine.energy_windows always passes the true maximum length).  Returns (records, the buffer past the scratch)."""
+    from audio_analysis_amd.engine import _ptr, check
+    t = eng.torch
+    nseg, nlim = len(off), len(limits[0])
+    nsc = int(eng.lib.ira_energy_scratch_doubles(nseg, max_len, nlim))
+    assert nsc == nseg * (-(-max_len // 16384)) * (nlim + 2)
+    big = t.full((nsc + 64,), float("nan"), dtype=t.float64, device=eng.device)
+    out = t.full((nseg * (nlim + 2),), float("nan"), dtype=t.float64, device=eng.device)
+    d_off, d_len, d_ch, d_on, d_lim = (eng.to_dev(np.asarray(a, dt)) for a, dt in (
+        (off, np.int64), (length, np.int64), (np.arange(nseg), np.int32), (np.zeros(nseg), np.int64),
+        (np.asarray(limits).reshape(-1), np.int64)))
+    check(eng.lib.ira_energy_windows(_ptr(flat_dev), _ptr(d_off), _ptr(d_len), _ptr(d_ch), _ptr(d_on), nseg, max_len,
+                                     _ptr(d_lim), nlim, _ptr(big), _ptr(out), eng.stream), "ira_energy_windows")
+    return out.cpu().numpy().reshape(nseg, nlim + 2), big[nsc:].cpu().numpy()
+
+
+def test_fold_reads_only_the_records_max_len_paid_for():
+    """A row longer than the max_len the caller stated: the fold stops at the records the scratch holds for the row (the
+    partial pass wrote exactly those), so the row comes out as if cut at max_len, its neighbour is untouched and nothing
+    past the scratch is read or written."""
+    eng = _eng()
+    c = 16384
+    rng = np.random.default_rng(41)
+    rows = [(rng.standard_normal(n) * np.exp(-4.0 * np.arange(n) / n)).astype(np.float32) for n in (3 * c, c)]
+    off = [1, 1 + 3 * c + 2]
+    flat = np.full(off[1] + c + 8, 0.5, np.float32)
+    for o, r in zip(off, rows):
+        flat[o : o + r.size] = r
+    x = eng.to_dev(flat)
+    lim = [2400]
+    both, past = _windows_raw(eng, x, off, [3 * c, c], [lim, lim], 2 * c)
+    cut, _ = _windows_raw(eng, x, off[:1], [2 * c], [lim], 2 * c)
+    solo, _ = _windows_raw(eng, x, off[1:], [c], [lim], c)
+    print("row 0:", both[0], "cut at max_len:", cut[0])
+    assert np.all(np.isfinite(both[0])) and np.array_equal(both[0].view(np.uint64), cut[0].view(np.uint64))
+    assert np.array_equal(both[1].view(np.uint64), solo[0].view(np.uint64))
+    assert np.all(np.isnan(past))
+
+
 def test_mixed_sample_rates_in_one_launch():
     from audio_analysis_amd.synth import synth_ir
     eng = _eng()

@@ -121,6 +121,43 @@ def test_bit_identical_whatever_the_batch_and_alignment():
     assert np.array_equal(again.view(np.uint64), alone.view(np.uint64))
 
 
+def _sums_raw(eng, flat_dev, off, length, w, max_len):
+    """ira_mtf_sums through the bound library with the caller's max_len and a scratch of exactly
+    ira_mtf_scratch_doubles(nseg, max_len, nf) doubles carved from the front of a larger NaN-filled buffer
+    (Engine.mtf_sums always passes the true maximum length).  Returns (records, the buffer past the scratch)."""
+    from audio_analysis_amd.engine import _ptr, check
+    t = eng.torch
+    nseg, nf = len(off), len(w)
+    nsc = int(eng.lib.ira_mtf_scratch_doubles(nseg, max_len, nf))
+    assert nsc == nseg * (-(-max_len // C)) * (2 * nf + 1)
+    big = t.full((nsc + 64,), float("nan"), dtype=t.float64, device=eng.device)
+    out = t.full((nseg * (2 * nf + 1),), float("nan"), dtype=t.float64, device=eng.device)
+    d_off, d_len = eng.to_dev(np.asarray(off, np.int64)), eng.to_dev(np.asarray(length, np.int64))
+    d_w = eng.to_dev(np.tile(np.asarray(w, np.float64), nseg))
+    check(eng.lib.ira_mtf_sums(_ptr(flat_dev), _ptr(d_off), _ptr(d_len), _ptr(d_w), nseg, max_len, nf, _ptr(big), _ptr(out),
+                               eng.stream), "ira_mtf_sums")
+    return out.cpu().numpy().reshape(nseg, 2 * nf + 1), big[nsc:].cpu().numpy()
+
+
+def test_fold_reads_only_the_records_max_len_paid_for():
+    """A row longer than the max_len the caller stated comes out as if cut at max_len (the fold stops at the records the
+    scratch holds for it), its neighbour is untouched and nothing past the scratch is read or written."""
+    eng = _eng()
+    rows = [_noise_row(61, 3 * C), _noise_row(62, C)]
+    off = [1, 1 + 3 * C + 2]
+    flat = np.full(off[1] + C + 8, 0.5, np.float32)
+    for o, r in zip(off, rows):
+        flat[o : o + r.size] = r
+    x = eng.to_dev(flat)
+    w = R.turns(R.FREQS, SR)
+    both, past = _sums_raw(eng, x, off, [3 * C, C], w, 2 * C)
+    cut, _ = _sums_raw(eng, x, off[:1], [2 * C], w, 2 * C)
+    solo, _ = _sums_raw(eng, x, off[1:], [C], w, C)
+    assert np.all(np.isfinite(both[0])) and np.array_equal(both[0].view(np.uint64), cut[0].view(np.uint64))
+    assert np.array_equal(both[1].view(np.uint64), solo[0].view(np.uint64))
+    assert np.all(np.isnan(past))
+
+
 def test_closed_forms_on_the_device():
     eng = _eng()
     w = R.turns(R.FREQS, SR)

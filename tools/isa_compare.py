@@ -6,7 +6,8 @@
 Each file is compiled in both checkouts with the flags build.py uses for it (build.COMMON + build.SOURCES[file], from the
 checkout this tool lives in) plus --cuda-device-only -S.  Per kernel: identical or not -- instruction lines only; comment
 lines, assembler directives, labels and with them the per-compilation __hip_cuid_* symbol are ignored -- then VGPR, SGPR,
-scratch bytes and instruction counts by class, as "A -> B" where they differ."""
+scratch bytes and instruction counts by class, as "A -> B" where they differ.  A kernel that differs but executes the same
+number of every opcode is marked "same opcodes": the two differ in instruction order and register numbers only."""
 import collections, re, shutil, subprocess, sys, tempfile
 from concurrent.futures import ThreadPoolExecutor
 from pathlib import Path
@@ -90,7 +91,8 @@ def main():
             ca, cb = (collections.Counter(classify(l.split()[0]) for l in x) for x in (ia, ib))
             cols = [(k, ra[k], rb[k]) for k in ("VGPR", "SGPR", "scratch")] + [("instructions", len(ia), len(ib))]
             cols += [(k, ca[k], cb[k]) for k in CLASSES + (("other",) if ca["other"] or cb["other"] else ())]
-            print(f"   {name}: {'identical' if ident else 'DIFFERENT'}")
+            same_opcodes = collections.Counter(l.split()[0] for l in ia) == collections.Counter(l.split()[0] for l in ib)
+            print(f"   {name}: {'identical' if ident else 'DIFFERENT (same opcodes)' if same_opcodes else 'DIFFERENT'}")
             print("      " + "  ".join(f"{k} {x}" if x == y else f"{k} {x} -> {y}" for k, x, y in cols))
     print(f"{same} kernels identical, {differ} different")
 
