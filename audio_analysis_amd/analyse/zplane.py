@@ -84,6 +84,7 @@ def _fit_ar_least_squares(x: np.ndarray, order: int, ridge_lambda: float = 0.0) 
     return co.cpu().numpy()[0].copy()
 
 
+# IRA_AR_STATUS_NOT_FINITE of include/ira.h, restated: Python does not parse the header
 AR_STATUS_NOT_FINITE = 3.0      # ira_ar_solve (any order, any ridge): the Gram matrix holds NaN / infinity
 
 

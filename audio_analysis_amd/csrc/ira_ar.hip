@@ -3,30 +3,64 @@
 // The reference solves the covariance-method least squares  min || A a + x ||,  A[n,k] = x[n-k] (n = p..N-1,
 // k = 1..p) with an SVD (numpy.linalg.lstsq) over an (N-p) x p matrix -- 4 s of LAPACK per 10 s channel.
 // Here:
-//   1. ar_lag_kernel    (default) the normal equations of the covariance method have SHIFT structure: with
+//   1. ar_lag_kernel    (the product's path) the normal equations of the covariance method have SHIFT structure: with
 //                       Phi[a][b] = sum_{n=p}^{N-1} s[n-a] s[n-b],  G[i][j] = Phi[i+1][j+1],  r[j] = -Phi[0][j+1] and
 //                         Phi[a+1][b+1] = Phi[a][b] + s[p-1-a] s[p-1-b] - s[N-1-a] s[N-1-b],
 //                       so p+1 lag sums Phi[0][0..p] (one pass over the samples, float64 FMAs on exact products of
 //                       float32 samples) plus O(p^2) head/tail corrections give all of G: 2(p+1)N flops instead
 //                       of p(p+1)N.  The corrections are accumulated with compensated (Neumaier) sums.
-//   1'. ar_gram_kernel  (IRA_AR_DENSE=1, cross-check) G = A^T A and r = A^T y as a dense float64 contraction on the matrix cores
+//   1'. ar_gram_kernel  (flags & IRA_AR_DENSE_GRAM, cross-check) G = A^T A and r = A^T y as a dense float64 contraction on the matrix cores
 //                       (v_mfma_f64_16x16x4_f64).  A is an implicit Hankel view of the signal: every operand
 //                       fragment is a shifted window of the LDS-staged samples, nothing is materialised.
 //   2. ar_solve_kernel  deterministic reduction of the per-chunk partial Grams, optional ridge, Cholesky,
-//                       two triangular solves -> a[0..p] (a[0] = 1).
-//   3. poly_roots_kernel  all roots of the monic polynomial by Aberth-Ehrlich iteration in float64
-//                       (numpy.roots uses companion-matrix eigenvalues; root ORDER is unspecified there, so
-//                       parity is on the sorted set and on the radius statistics).
-//   4. fir_numerator_kernel  b[n] = sum_k a[k] h[n-k], n <= Q   (zplane.py:123-142, --zeros option).
+//                       two triangular solves -> a[0..p] (a[0] = 1).  ar_solve_wave_kernel is the same solve on one wave
+//                       (lag-sum record, p <= 64; flags & IRA_AR_WORKGROUP_SOLVE keeps the workgroup kernel).
+//   2'. rare paths, for the elements the solve flagged in info[0] only: ar_grad_kernel + a second solve (refinement), ar_lag_dd_kernel /
+//                       ar_solve_dd_kernel (double-double normal equations), ar_minnorm_kernel (rank-deficient fits).
+// The roots of a(z) and the FIR numerator that follow the fit are in ira_roots.hip, the double-double arithmetic in ira_dd.h.
 // Float32 is not an option for G: on coloured IRs a float32 Gram loses the poles entirely (SURVEY.md
 // section 7, hard part 1).
 #include <cmath>
 
 #include "ira_common.h"
+#include "ira_dd.h"
 
 namespace {
 
 typedef double d4 __attribute__((ext_vector_type(4)));
+
+// ---- what the kernels of this file share -----------------------------------------------------------------------------------
+// The samples of element e: float32 or float64 storage, divided by the element's divisor in float64.
+struct ar_source { const float* xs; const double* xd; double div; };
+__device__ __forceinline__ ar_source ar_source_of(const float* x, const double* x64, const int64_t* xoff,
+                                                  const double* divisor, int e) {
+  return {x ? x + xoff[e] : nullptr, x64 ? x64 + xoff[e] : nullptr, divisor ? divisor[e] : 1.0};
+}
+__device__ __forceinline__ double ar_sample(const float* xs, const double* xd, double div, long long idx) {   // 0 <= idx < N
+  return (xd ? xd[idx] : (double)xs[idx]) / div;
+}
+__device__ __forceinline__ double ar_sample(const float* xs, const double* xd, double div, long long idx, long long N) {
+  return (idx >= 0 && idx < N) ? ar_sample(xs, xd, div, idx) : 0.0;                                          // zero outside [0, N)
+}
+
+// Rows [row0, n_end) of chunk `chunk`: the rows of the covariance method start at p; a chunk past the end has row0 >= N.
+struct ar_rows { long long row0, n_end; };
+__device__ __forceinline__ ar_rows chunk_rows(long long N, int p, int chunk, int CHUNK) {
+  const long long row0 = (long long)p + (long long)chunk * CHUNK;
+  return {row0, (row0 + CHUNK < N) ? row0 + CHUNK : N};
+}
+
+// info[0] of element e (IRA_AR_STATUS_*), and the whole record
+__device__ __forceinline__ double ar_status(const double* info, int e) { return info[IRA_AR_INFO_DOUBLES * e + 0]; }
+__device__ __forceinline__ void ar_status_store(double* info, int e, int status) { info[IRA_AR_INFO_DOUBLES * e + 0] = (double)status; }
+__device__ __forceinline__ void ar_info_store(double* info, int e, int status, double a, double b, double c) {
+  ar_status_store(info, e, status);
+  info[IRA_AR_INFO_DOUBLES * e + 1] = a; info[IRA_AR_INFO_DOUBLES * e + 2] = b; info[IRA_AR_INFO_DOUBLES * e + 3] = c;
+}
+// what a first solve reports: a NaN or infinite sample wins over a pivot that was not positive
+__device__ __forceinline__ int ar_solve_status(bool not_finite, int pivot_failed) {
+  return not_finite ? IRA_AR_STATUS_NOT_FINITE : pivot_failed ? IRA_AR_STATUS_PIVOT : IRA_AR_STATUS_SOLVED;
+}
 
 constexpr int GR_KC = 1024;       // rows (samples n) staged in LDS per tile
 constexpr int GR_CHUNK = 8192;    // rows per workgroup (one wave); ~4 waves per SIMD at batch 64 x 10 s
@@ -36,6 +70,7 @@ constexpr int GR_MAX_P = 1024;
 
 __host__ __device__ inline int groups_side(int p) { return (p + GR_GROUP - 1) / GR_GROUP; }
 __host__ __device__ inline int groups_total(int p) { const int g = groups_side(p); return g * (g + 1) / 2; }
+__host__ __device__ inline int gram_chunks(long long len, int p) { return (int)((len - p + GR_CHUNK - 1) / GR_CHUNK); }
 
 // Operand fragments of one k-step (4 rows n0..n0+3): lane (i = lane & 15, kk = lane >> 4) holds s[n0+kk-1-(16b+i)]
 // for each 16-wide block b; the A fragment of block row b and the B fragment of block column b are the SAME value.
@@ -73,9 +108,8 @@ __global__ __launch_bounds__(64) void ar_gram_kernel(const float* __restrict__ x
   const int e = blockIdx.z;
   const int chunk = blockIdx.x;
   const long long N = nlen[e];
-  const long long row0 = (long long)p + (long long)chunk * GR_CHUNK;
+  const auto [row0, n_end] = chunk_rows(N, p, chunk, GR_CHUNK);
   if (row0 >= N) return;
-  const long long n_end = (row0 + GR_CHUNK < N) ? row0 + GR_CHUNK : N;
   int gi, gj;
   if (DIAG) {
     gi = gj = blockIdx.y;
@@ -86,9 +120,7 @@ __global__ __launch_bounds__(64) void ar_gram_kernel(const float* __restrict__ x
   }
   const int gid = gi * (gi + 1) / 2 + gj;            // slot in the lower-triangular partial record
   const int halo = GR_GROUP * groups_side(p) + 1;    // largest lag touched (padded) + 1
-  const float* xs = x ? x + xoff[e] : nullptr;
-  const double* xd = x64 ? x64 + xoff[e] : nullptr;
-  const double div = divisor ? divisor[e] : 1.0;
+  const ar_source src = ar_source_of(x, x64, xoff, divisor, e);
   const int lane = threadIdx.x;
 
   constexpr int NACC = DIAG ? 10 : 16;
@@ -102,10 +134,7 @@ __global__ __launch_bounds__(64) void ar_gram_kernel(const float* __restrict__ x
     const int kc = (int)((n_end - t0 < GR_KC) ? n_end - t0 : GR_KC);
     const int kc4 = (kc + 3) & ~3;
     __syncthreads();
-    for (int m = lane; m < halo + kc4; m += 64) {
-      const long long idx = origin + m;
-      lds[m] = (idx >= 0 && idx < N) ? (xd ? xd[idx] : (double)xs[idx]) / div : 0.0;
-    }
+    for (int m = lane; m < halo + kc4; m += 64) lds[m] = ar_sample(src.xs, src.xd, src.div, origin + m, N);
     __syncthreads();
 
     double fa[4], fb[4], na[4], nb[4];
@@ -165,7 +194,6 @@ __global__ __launch_bounds__(64) void ar_gram_kernel(const float* __restrict__ x
 // unrolling nor fewer instructions moved its 0.28 ms (64 x 10 s, p = 64); LPT = 13 (65 lags = 5 x 13) reads 3.25x less.
 // The window lives in registers under compile-time renaming (an LPT-row unrolled body, no moves).  Every accumulator sees
 // its rows in order, so the sums do not depend on LPT.  Sub-range sums are combined in a fixed order.
-// Partial record of element e (doubles):  [nchunks_max][p+1] lag sums | head s[0..p] | tail s[N-1], s[N-2] .. s[N-1-p]
 // ------------------------------------------------------------------------------------------------------------
 constexpr int LAG_CHUNK = 4096;
 constexpr int LAG_THREADS = 256;
@@ -175,6 +203,20 @@ __host__ __device__ inline int lag_chunks(long long max_len, int p) {
 }
 __host__ __device__ inline long long lag_record_doubles(long long max_len, int p) {
   return (long long)lag_chunks(max_len, p) * (p + 1) + 2ll * (p + 1);
+}
+// Partial record of element e (doubles):  [nchunks_max][p+1] lag sums | head s[0..p] | tail s[N-1], s[N-2] .. s[N-1-p]
+// rec[ch * (p+1) + d] is chunk ch's share of Phi[0][d]; the element's own chunks are the first `lchunks`.
+template <typename T>                                 // double where the record is written, const double where it is read
+struct lag_record {
+  T* rec;
+  int nchunks_max, nlag, lchunks;
+  __device__ __forceinline__ T* head() const { return rec + (long long)nchunks_max * nlag; }
+  __device__ __forceinline__ T* tail() const { return head() + nlag; }
+};
+template <typename T>
+__device__ __forceinline__ lag_record<T> lag_record_of(T* part, int e, long long rec_doubles, int nchunks_max, long long N,
+                                                       int p) {
+  return {part + (long long)e * rec_doubles, nchunks_max, p + 1, lag_chunks(N, p)};
 }
 // lags per thread: the candidate that wastes the fewest lag slots (ties: the wider one)
 inline int lag_per_thread(int nlag) {
@@ -198,20 +240,21 @@ __global__ __launch_bounds__(LAG_THREADS) void ar_lag_kernel(const float* __rest
   const int e = blockIdx.z;
   const int chunk = blockIdx.x;
   const long long N = nlen[e];
-  const long long row0 = (long long)p + (long long)chunk * LAG_CHUNK;
+  const auto [row0, n_end] = chunk_rows(N, p, chunk, LAG_CHUNK);
   if (row0 >= N) return;
-  const long long n_end = (row0 + LAG_CHUNK < N) ? row0 + LAG_CHUNK : N;
   const int rows = (int)(n_end - row0);
   const int nlag = p + 1, ngroups = (nlag + LPT - 1) / LPT;
   const int halo = LPT * ngroups;                      // the last group's window reaches back LPT * ngroups - 1 samples
   const long long origin = row0 - halo;              // sample index of lds[0]
   double* lds = reinterpret_cast<double*>(smem_raw);                 // halo + LAG_CHUNK samples; reused for the partials
   const int nsub = ngroups >= LAG_THREADS ? 1 : LAG_THREADS / ngroups;
+  // (the set-up in place, not ar_source_of: with both that and ar_sample inlined here the head / tail loop below is scheduled
+  // differently and loses a hazard nop -- no longer the parent's opcodes, which profiles/ar_dedup_isa.txt holds this kernel to)
   const float* xs = x ? x + xoff[e] : nullptr;
   const double* xd = x64 ? x64 + xoff[e] : nullptr;
   const double div = divisor ? divisor[e] : 1.0;
   const int tid = threadIdx.x;
-  double* rec = part + (long long)e * rec_doubles;
+  const lag_record<double> lr = lag_record_of(part, e, rec_doubles, nchunks_max, N, p);
 
   // Staging in batches of nine loads (index clamped, value dropped afterwards: a load inside the range test is waited
   // for on the spot, i.e. one memory round trip per sample and thread -- 17 of them in a row before).
@@ -238,11 +281,10 @@ __global__ __launch_bounds__(LAG_THREADS) void ar_lag_kernel(const float* __rest
   if (xd) stage(xd); else stage(xs);
   if (chunk == 0) {
     // head and tail samples for the O(p^2) corrections of the solve kernel
-    double* head = rec + (long long)nchunks_max * nlag;
-    double* tail = head + nlag;
+    double *head = lr.head(), *tail = lr.tail();
     for (int m = tid; m < nlag; m += LAG_THREADS) {
-      head[m] = (xd ? xd[m] : (double)xs[m]) / div;                         // m <= p < N
-      tail[m] = (xd ? xd[N - 1 - m] : (double)xs[N - 1 - m]) / div;
+      head[m] = ar_sample(xs, xd, div, m);                                  // m <= p < N
+      tail[m] = ar_sample(xs, xd, div, N - 1 - m);
     }
   }
   __syncthreads();
@@ -296,7 +338,7 @@ __global__ __launch_bounds__(LAG_THREADS) void ar_lag_kernel(const float* __rest
   for (int b = tid; b < nlag; b += LAG_THREADS) {
     double sum = 0.0;
     for (int sb = 0; sb < nsub; ++sb) sum += lds[(size_t)sb * (LPT * ngroups) + b];
-    rec[(long long)chunk * nlag + b] = sum;
+    lr.rec[(long long)chunk * nlag + b] = sum;
   }
 }
 
@@ -309,9 +351,9 @@ __global__ __launch_bounds__(LAG_THREADS) void ar_lag_kernel(const float* __rest
 // Same grid and chunking as ar_lag_kernel; partial layout [nchunks_max][p+1] per element (entry 0 unused).
 // ------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ bool ar_needs_refinement(const double* info, int e, double cond_threshold) {
-  const double status = info[IRA_AR_INFO_DOUBLES * e + 0];
-  if (status != 0.0 && status != 2.0) return false;                    // no float64 factorisation to refine with (1, 3, 4), or
-                                                                       // already solved in double-double (5)
+  const double status = ar_status(info, e);
+  if (status != IRA_AR_STATUS_SOLVED && status != IRA_AR_STATUS_REFINED) return false;   // no float64 factorisation to refine
+                                                      // with (PIVOT, NOT_FINITE, MINNORM), or solved in double-double (EXACT)
   return info[IRA_AR_INFO_DOUBLES * e + 3] > cond_threshold;            // trace(G) * ||G^-1|| estimate
 }
 
@@ -327,9 +369,8 @@ __global__ __launch_bounds__(LAG_THREADS) void ar_grad_kernel(const float* __res
   if (!ar_needs_refinement(info, e, cond_threshold)) return;
   const int chunk = blockIdx.x;
   const long long N = nlen[e];
-  const long long row0 = (long long)p + (long long)chunk * LAG_CHUNK;
+  const auto [row0, n_end] = chunk_rows(N, p, chunk, LAG_CHUNK);
   if (row0 >= N) return;
-  const long long n_end = (row0 + LAG_CHUNK < N) ? row0 + LAG_CHUNK : N;
   const int rows = (int)(n_end - row0);
   const int halo = p + 3;
   const long long origin = row0 - halo;
@@ -339,14 +380,9 @@ __global__ __launch_bounds__(LAG_THREADS) void ar_grad_kernel(const float* __res
   double* res = lds + halo + LAG_CHUNK;                              // LAG_CHUNK residuals
   double* co = res + LAG_CHUNK;                                      // p + 1 coefficients
   double* red = co + nlag;                                           // [nsub][4 * ngroups]
-  const float* xs = x ? x + xoff[e] : nullptr;
-  const double* xd = x64 ? x64 + xoff[e] : nullptr;
-  const double div = divisor ? divisor[e] : 1.0;
+  const ar_source src = ar_source_of(x, x64, xoff, divisor, e);
   const int tid = threadIdx.x;
-  for (int m = tid; m < halo + rows; m += LAG_THREADS) {
-    const long long idx = origin + m;
-    lds[m] = (idx >= 0 && idx < N) ? (xd ? xd[idx] : (double)xs[idx]) / div : 0.0;
-  }
+  for (int m = tid; m < halo + rows; m += LAG_THREADS) lds[m] = ar_sample(src.xs, src.xd, src.div, origin + m, N);
   for (int m = tid; m < nlag; m += LAG_THREADS) co[m] = coeffs[(long long)e * nlag + m];
   __syncthreads();
   for (int r = tid; r < rows; r += LAG_THREADS) {
@@ -396,20 +432,61 @@ __global__ __launch_bounds__(LAG_THREADS) void ar_grad_kernel(const float* __res
 constexpr int SV_THREADS = 256;
 constexpr int SV_LDS_P = 128;
 
-// L y = r (forward), L^T a = y (backward), column oriented, in place on vec; all threads of the workgroup call.
-__device__ __forceinline__ void chol_solve_inplace(const double* G, double* vec, int p, int tid) {
+// G and r of the normal equations from the lag record: thread tid of NTHREADS owns diagonals d = tid, tid + NTHREADS, ...; it
+// sums the chunks' lag sums to Phi[0][d] (r[d-1] = -Phi[0][d]) and walks down the diagonal with a Neumaier compensated sum,
+//   Phi[a][a+d] = Phi[0][d] + sum_{m<a} (s[p-1-m] s[p-1-m-d] - s[N-1-m] s[N-1-m-d]).
+// store_g(r, c, v) gets G[r][c] for r >= c, store_r(j, v) gets r[j]; RIDGE adds `ridge` on diagonal 0.  One copy: every caller's
+// G holds the same bits.
+template <int NTHREADS, bool RIDGE, typename StoreG, typename StoreR>
+__device__ __forceinline__ void gram_from_lags(const lag_record<const double>& lr, int p, int tid, double ridge,
+                                               StoreG store_g, StoreR store_r) {
+  const int nlag = p + 1;
+  const double *head = lr.head(), *tail = lr.tail();
+  for (int d = tid; d < nlag; d += NTHREADS) {
+    double c = 0.0;
+    for (int ch = 0; ch < lr.lchunks; ++ch) c += lr.rec[(long long)ch * nlag + d];      // Phi[0][d]
+    if (d >= 1) store_r(d - 1, -c);
+    double run = c, comp = 0.0;
+    for (int a = 1; a + d <= p; ++a) {
+      const int m = a - 1;
+      const double t1 = head[p - 1 - m] * head[p - 1 - m - d];
+      const double t2 = -tail[m] * tail[m + d];
+#pragma unroll
+      for (int q = 0; q < 2; ++q) {
+        const double term = q == 0 ? t1 : t2;
+        const double t = run + term;
+        comp += (fabs(run) >= fabs(term)) ? (run - t) + term : (term - t) + run;
+        run = t;
+      }
+      double v = run + comp;
+      if (RIDGE && d == 0) v += ridge;
+      store_g(a + d - 1, a - 1, v);
+    }
+  }
+}
+
+// L y = r (forward), L^T a = y (backward), column oriented, in place on vec; all threads of the workgroup call.  T is double
+// (I = int: the matrix fits LDS) or dd (I = long long: p^2 entries of global scratch); the double expressions contract to
+// FMAs as written in place, the dd operations carry their own contract(off).
+__device__ __forceinline__ double sv_div(double a, double b) { return a / b; }
+__device__ __forceinline__ double sv_sub_mul(double v, double l, double y) { return v - l * y; }
+__device__ __forceinline__ dd sv_div(dd a, dd b) { return dd_div(a, b); }
+__device__ __forceinline__ dd sv_sub_mul(dd v, dd l, dd y) { return dd_add(v, dd_neg(dd_mul(l, y))); }
+
+template <typename T, typename I>
+__device__ __forceinline__ void chol_solve_inplace(const T* G, T* vec, int p, int tid) {
   for (int k = 0; k < p; ++k) {
-    if (tid == 0) vec[k] = vec[k] / G[k * p + k];
+    if (tid == 0) vec[k] = sv_div(vec[k], G[(I)k * p + k]);
     __syncthreads();
-    const double yk = vec[k];
-    for (int i = k + 1 + tid; i < p; i += SV_THREADS) vec[i] -= G[i * p + k] * yk;
+    const T yk = vec[k];
+    for (int i = k + 1 + tid; i < p; i += SV_THREADS) vec[i] = sv_sub_mul(vec[i], G[(I)i * p + k], yk);
     __syncthreads();
   }
   for (int k = p - 1; k >= 0; --k) {
-    if (tid == 0) vec[k] = vec[k] / G[k * p + k];
+    if (tid == 0) vec[k] = sv_div(vec[k], G[(I)k * p + k]);
     __syncthreads();
-    const double ak = vec[k];
-    for (int i = tid; i < k; i += SV_THREADS) vec[i] -= G[k * p + i] * ak;
+    const T ak = vec[k];
+    for (int i = tid; i < k; i += SV_THREADS) vec[i] = sv_sub_mul(vec[i], G[(I)k * p + i], ak);
     __syncthreads();
   }
 }
@@ -561,43 +638,17 @@ __global__ __launch_bounds__(SV_THREADS) void ar_solve_kernel(const double* __re
   // refinement call (gpart != null): only flagged elements; rhs = gradient of the current residual, a += G^-1 rhs
   if (gpart != nullptr && !ar_needs_refinement(info, e, cond_threshold)) return;
   const long long N = nlen[e];
-  const int nchunks = (int)((N - p + GR_CHUNK - 1) / GR_CHUNK);
+  const int nchunks = gram_chunks(N, p);
   const int ng = groups_total(p);
   double* vec = reinterpret_cast<double*>(smem_raw);            // rhs / solution, p doubles
   double* G = (p <= SV_LDS_P) ? vec + p : gscratch + (long long)e * p * p;
   const double* pe = part + (long long)e * nchunks_max * ng * GR_PART;
 
   if (lag_mode) {
-    // ---- G and r from the p+1 lag sums and the head/tail samples (see ar_lag_kernel) -----------------------------------
-    const int nlag = p + 1;
-    const double* rec = part + (long long)e * lag_rec_doubles;
-    const double* head = rec + (long long)lag_nchunks_max * nlag;
-    const double* tail = head + nlag;
-    const int lchunks = lag_chunks(N, p);
-    for (int d = tid; d < nlag; d += SV_THREADS) {
-      double c = 0.0;
-      for (int ch = 0; ch < lchunks; ++ch) c += rec[(long long)ch * nlag + d];      // Phi[0][d]
-      if (d >= 1) vec[d - 1] = -c;
-      // walk down diagonal d:  Phi[a][a+d] = Phi[0][d] + sum_{m<a} (s[p-1-m] s[p-1-m-d] - s[N-1-m] s[N-1-m-d])
-      double run = c, comp = 0.0;                                                     // Neumaier compensated sum
-      for (int a = 1; a + d <= p; ++a) {
-        const int m = a - 1;
-        const double t1 = head[p - 1 - m] * head[p - 1 - m - d];
-        const double t2 = -tail[m] * tail[m + d];
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-          const double term = q == 0 ? t1 : t2;
-          const double t = run + term;
-          comp += (fabs(run) >= fabs(term)) ? (run - t) + term : (term - t) + run;
-          run = t;
-        }
-        double v = run + comp;
-        const int r = a + d - 1, cidx = a - 1;                                        // G[r][cidx], r >= cidx
-        if (d == 0) v += ridge;
-        G[r * p + cidx] = v;
-        G[cidx * p + r] = v;
-      }
-    }
+    // ---- G (mirrored) and r from the p+1 lag sums and the head/tail samples (see ar_lag_kernel) ------------------------
+    gram_from_lags<SV_THREADS, true>(
+        lag_record_of(part, e, lag_rec_doubles, lag_nchunks_max, N, p), p, tid, ridge,
+        [=](int r, int c, double v) { G[r * p + c] = v; G[c * p + r] = v; }, [=](int j, double v) { vec[j] = v; });
   } else {
     // ---- deterministic reduction over chunks (fixed order), lower triangle + mirror -------------------------
     for (int idx = tid; idx < p * p; idx += SV_THREADS) {
@@ -675,12 +726,12 @@ __global__ __launch_bounds__(SV_THREADS) void ar_solve_kernel(const double* __re
     }
     __syncthreads();
   }
-  if (in_lds) chol_solve_inplace(G, vec, p, tid); else chol_solve_blocked(G, vec, p, blk, tid);
+  if (in_lds) chol_solve_inplace<double, int>(G, vec, p, tid); else chol_solve_blocked(G, vec, p, blk, tid);
   double* co = coeffs + (long long)e * (p + 1);
   if (gpart != nullptr) {
     if (!fail)
       for (int j = tid; j < p; j += SV_THREADS) co[j + 1] += vec[j];
-    if (tid == 0 && !fail) info[IRA_AR_INFO_DOUBLES * e + 0] = 2.0;  // refined
+    if (tid == 0 && !fail) ar_status_store(info, e, IRA_AR_STATUS_REFINED);
     return;
   }
   // not finite (status 3): NaN coefficients, as ar_minnorm_kernel reports it -- but at every order, with a ridge and with the
@@ -711,7 +762,7 @@ __global__ __launch_bounds__(SV_THREADS) void ar_solve_kernel(const double* __re
       const double inv = 1.0 / nrm_s;
       for (int j = tid; j < p; j += SV_THREADS) vec[j] *= inv;
       __syncthreads();
-      if (in_lds) chol_solve_inplace(G, vec, p, tid); else chol_solve_blocked(G, vec, p, blk, tid);
+      if (in_lds) chol_solve_inplace<double, int>(G, vec, p, tid); else chol_solve_blocked(G, vec, p, blk, tid);
     }
     if (tid == 0) {
       double q = 0.0;
@@ -719,12 +770,7 @@ __global__ __launch_bounds__(SV_THREADS) void ar_solve_kernel(const double* __re
       cond_est = trace_s * sqrt(q);
     }
   }
-  if (tid == 0) {
-    info[IRA_AR_INFO_DOUBLES * e + 0] = bad ? 3.0 : (double)fail;
-    info[IRA_AR_INFO_DOUBLES * e + 1] = dmax;   // largest / smallest Cholesky pivot
-    info[IRA_AR_INFO_DOUBLES * e + 2] = dmin;
-    info[IRA_AR_INFO_DOUBLES * e + 3] = cond_est;
-  }
+  if (tid == 0) ar_info_store(info, e, ar_solve_status(bad, fail), dmax, dmin, cond_est);   // largest / smallest Cholesky pivot
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -779,40 +825,17 @@ __global__ __launch_bounds__(64) void ar_solve_wave_kernel(const double* __restr
   const int e = blockIdx.x, lane = threadIdx.x;
   if (gpart != nullptr && !ar_needs_refinement(info, e, cond_threshold)) return;
   const long long N = nlen[e];
-  const int nlag = p + 1;
-  const double* rec = part + (long long)e * lag_rec_doubles;
-  const double* head = rec + (long long)lag_nchunks_max * nlag;
-  const double* tail = head + nlag;
-  const int lchunks = lag_chunks(N, p);
-  // ---- G (lower triangle) and r from the lag sums and the head / tail samples: lane d walks diagonal d, as ar_solve_kernel ----
-  for (int d = lane; d < nlag; d += 64) {
-    double c = 0.0;
-    for (int ch = 0; ch < lchunks; ++ch) c += rec[(long long)ch * nlag + d];
-    if (d >= 1) rhs[d - 1] = -c;
-    double run = c, comp = 0.0;
-    for (int a = 1; a + d <= p; ++a) {
-      const int m = a - 1;
-      const double t1 = head[p - 1 - m] * head[p - 1 - m - d];
-      const double t2 = -tail[m] * tail[m + d];
-#pragma unroll
-      for (int q = 0; q < 2; ++q) {
-        const double term = q == 0 ? t1 : t2;
-        const double t = run + term;
-        comp += (fabs(run) >= fabs(term)) ? (run - t) + term : (term - t) + run;
-        run = t;
-      }
-      double v = run + comp;
-      if (d == 0) v += ridge;
-      G[(a + d - 1) * SW_LD + (a - 1)] = v;                      // G[r][c], r >= c
-    }
-  }
+  const lag_record<const double> lr = lag_record_of(part, e, lag_rec_doubles, lag_nchunks_max, N, p);
+  // ---- G (lower triangle) and r from the lag sums and the head / tail samples: lane d walks diagonal d ----------------------
+  gram_from_lags<64, true>(
+      lr, p, lane, ridge, [=](int r, int c, double v) { G[r * SW_LD + c] = v; }, [=](int j, double v) { rhs[j] = v; });
   __builtin_amdgcn_wave_barrier();
   double vec = lane < p ? rhs[lane] : 0.0;
   if (gpart != nullptr) {
     const double* ge = gpart + (long long)e * lag_nchunks_max * (p + 1);
     double c = 0.0;
     if (lane < p)
-      for (int ch = 0; ch < lchunks; ++ch) c += ge[(long long)ch * (p + 1) + lane + 1];
+      for (int ch = 0; ch < lr.lchunks; ++ch) c += ge[(long long)ch * (p + 1) + lane + 1];
     vec = c;
   }
   double trace = 0.0;
@@ -839,7 +862,7 @@ __global__ __launch_bounds__(64) void ar_solve_wave_kernel(const double* __restr
   double* co = coeffs + (long long)e * (p + 1);
   if (gpart != nullptr) {
     if (!fail && lane < p) co[lane + 1] += vec;
-    if (lane == 0 && !fail) info[IRA_AR_INFO_DOUBLES * e + 0] = 2.0;  // refined
+    if (lane == 0 && !fail) ar_status_store(info, e, IRA_AR_STATUS_REFINED);
     return;
   }
   const bool bad = !(trace - trace == 0.0);                            // not finite (status 3), see ar_solve_kernel
@@ -860,12 +883,7 @@ __global__ __launch_bounds__(64) void ar_solve_wave_kernel(const double* __restr
     for (int j = 0; j < p; ++j) { const double vj = wave_bcast(vec, j); q += vj * vj; }
     cond_est = trace * sqrt(q);
   }
-  if (lane == 0) {
-    info[IRA_AR_INFO_DOUBLES * e + 0] = bad ? 3.0 : (double)fail;
-    info[IRA_AR_INFO_DOUBLES * e + 1] = dmax;
-    info[IRA_AR_INFO_DOUBLES * e + 2] = dmin;
-    info[IRA_AR_INFO_DOUBLES * e + 3] = cond_est;
-  }
+  if (lane == 0) ar_info_store(info, e, ar_solve_status(bad, fail), dmax, dmin, cond_est);
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -887,62 +905,10 @@ __global__ __launch_bounds__(64) void ar_solve_wave_kernel(const double* __restr
 // to the reference's working precision -- the element is
 // given status 1 (whatever brought it here) and ira_ar_minnorm returns lstsq's minimum-norm solution as before.
 // ------------------------------------------------------------------------------------------------------------
-struct dd { double hi, lo; };
-// `#pragma clang fp contract(off)` in every routine: this file is compiled with fused multiply-add contraction on, and a
-// product that gets fused into the addition of an error-free transformation (s = a + b*c computed as ONE fma while the error
-// term assumes s = fl(a + fl(b*c))) silently turns double-double into plain float64 -- seen as a 6e-8 instead of 1e-15
-// agreement with an exact rational solve.
-__device__ __forceinline__ dd dd_two_sum(double a, double b) {
-#pragma clang fp contract(off)
-  const double s = a + b, bb = s - a;
-  return {s, (a - (s - bb)) + (b - bb)};
-}
-__device__ __forceinline__ dd dd_fast_two_sum(double a, double b) {      // |a| >= |b|
-#pragma clang fp contract(off)
-  const double s = a + b;
-  return {s, b - (s - a)};
-}
-__device__ __forceinline__ dd dd_two_prod(double a, double b) {
-#pragma clang fp contract(off)
-  const double p = a * b;
-  return {p, fma(a, b, -p)};
-}
-__device__ __forceinline__ dd dd_add(dd x, dd y) {
-#pragma clang fp contract(off)
-  const dd s = dd_two_sum(x.hi, y.hi);
-  const dd t = dd_two_sum(x.lo, y.lo);
-  const dd u = dd_fast_two_sum(s.hi, s.lo + t.hi);
-  return dd_fast_two_sum(u.hi, u.lo + t.lo);
-}
-__device__ __forceinline__ dd dd_neg(dd x) { return {-x.hi, -x.lo}; }
-__device__ __forceinline__ dd dd_mul(dd x, dd y) {
-#pragma clang fp contract(off)
-  dd p = dd_two_prod(x.hi, y.hi);
-  p.lo += x.hi * y.lo + x.lo * y.hi;
-  return dd_fast_two_sum(p.hi, p.lo);
-}
-__device__ __forceinline__ dd dd_div(dd x, dd y) {
-#pragma clang fp contract(off)
-  const double q1 = x.hi / y.hi;
-  dd r = dd_add(x, dd_neg(dd_mul(y, dd{q1, 0.0})));
-  const double q2 = r.hi / y.hi;
-  r = dd_add(r, dd_neg(dd_mul(y, dd{q2, 0.0})));
-  const double q3 = r.hi / y.hi;
-  const dd q = dd_fast_two_sum(q1, q2);
-  return dd_add(q, dd{q3, 0.0});
-}
-__device__ __forceinline__ dd dd_sqrt(dd x) {                            // x > 0
-#pragma clang fp contract(off)
-  const double s = sqrt(x.hi);
-  const dd r = dd_add(x, dd_neg(dd_two_prod(s, s)));
-  return dd_fast_two_sum(s, r.hi / (2.0 * s));
-}
-
-constexpr double AR_DD_SOLVED = 5.0;          // info[0]: solved by the double-double normal equations
 __device__ __forceinline__ bool ar_needs_dd(const double* info, int e, double cond_threshold) {
-  const double status = info[IRA_AR_INFO_DOUBLES * e + 0];
-  if (status == 1.0) return true;                                      // the float64 factorisation broke down
-  if (status != 0.0) return false;                                     // not finite / already handled
+  const double status = ar_status(info, e);
+  if (status == IRA_AR_STATUS_PIVOT) return true;                      // the float64 factorisation broke down
+  if (status != IRA_AR_STATUS_SOLVED) return false;                    // not finite / already handled
   return !(info[IRA_AR_INFO_DOUBLES * e + 3] <= cond_threshold);        // estimate above the threshold (or NaN)
 }
 
@@ -956,19 +922,14 @@ __global__ __launch_bounds__(LAG_THREADS) void ar_lag_dd_kernel(const float* __r
   const int e = blockIdx.z, chunk = blockIdx.x;
   if (!ar_needs_dd(info, e, cond_threshold)) return;
   const long long N = nlen[e];
-  const long long row0 = (long long)p + (long long)chunk * LAG_CHUNK;
+  const auto [row0, n_end] = chunk_rows(N, p, chunk, LAG_CHUNK);
   if (row0 >= N) return;
-  const long long n_end = (row0 + LAG_CHUNK < N) ? row0 + LAG_CHUNK : N;
   const int rows = (int)(n_end - row0);
   double* lds = reinterpret_cast<double*>(smem_raw);                   // samples row0 - p .. n_end - 1
-  const float* xs = x ? x + xoff[e] : nullptr;
-  const double* xd = x64 ? x64 + xoff[e] : nullptr;
-  const double div = divisor ? divisor[e] : 1.0;
+  const ar_source src = ar_source_of(x, x64, xoff, divisor, e);
   const int tid = threadIdx.x;
-  for (int m = tid; m < p + rows; m += LAG_THREADS) {
-    const long long idx = row0 - p + m;                                // >= 0
-    lds[m] = (xd ? xd[idx] : (double)xs[idx]) / div;                   // the same rounded values every other AR kernel uses
-  }
+  for (int m = tid; m < p + rows; m += LAG_THREADS)                    // index >= 0; the same rounded values every other
+    lds[m] = ar_sample(src.xs, src.xd, src.div, row0 - p + m);                             // AR kernel uses
   __syncthreads();
   double* out = ddpart + (((long long)e * nchunks_max + chunk) * (p + 1)) * 2;
   for (int l = tid; l <= p; l += LAG_THREADS) {
@@ -998,19 +959,19 @@ __global__ __launch_bounds__(SV_THREADS) void ar_solve_dd_kernel(const double* _
   if (!ar_needs_dd(info, e, cond_threshold)) return;
   const long long N = nlen[e];
   const int nlag = p + 1;
-  const double* rec = part + (long long)e * lag_rec_doubles;
-  const double* head = rec + (long long)lag_nchunks_max * nlag;
-  const double* tail = head + nlag;
+  const lag_record<const double> lr = lag_record_of(part, e, lag_rec_doubles, lag_nchunks_max, N, p);
+  const double *head = lr.head(), *tail = lr.tail();
   const double* pe = ddpart + ((long long)e * lag_nchunks_max * nlag) * 2;
-  const int lchunks = lag_chunks(N, p);
   dd* G = reinterpret_cast<dd*>(ddscratch + (long long)e * 2 * ((long long)p * p + p));   // p x p, then the vector
   dd* vec = G + (long long)p * p;
+  // The diagonal walk of gram_from_lags, but its own code: the lag sums come from ddpart as (hi, lo) pairs and every step is a
+  // dd_add of an EXACT product (dd_two_prod) -- there is no compensation term to carry, and no double rounding to share.
   for (int d = tid; d < nlag; d += SV_THREADS) {
     dd c = {0.0, 0.0};
-    for (int ch = 0; ch < lchunks; ++ch) c = dd_add(c, dd{pe[((long long)ch * nlag + d) * 2], pe[((long long)ch * nlag + d) * 2 + 1]});
+    for (int ch = 0; ch < lr.lchunks; ++ch) c = dd_add(c, dd{pe[((long long)ch * nlag + d) * 2], pe[((long long)ch * nlag + d) * 2 + 1]});
     if (d >= 1) vec[d - 1] = dd_neg(c);                                  // r = -Phi[0][d]
     dd run = c;
-    for (int a = 1; a + d <= p; ++a) {                                   // Phi[a][a+d], see ar_solve_kernel
+    for (int a = 1; a + d <= p; ++a) {                                   // Phi[a][a+d]
       const int m = a - 1;
       run = dd_add(run, dd_two_prod(head[p - 1 - m], head[p - 1 - m - d]));
       run = dd_add(run, dd_neg(dd_two_prod(tail[m], tail[m + d])));
@@ -1041,6 +1002,7 @@ __global__ __launch_bounds__(SV_THREADS) void ar_solve_dd_kernel(const double* _
   // sigma / sigma_max ~ eps * rows, which the double-double arithmetic resolves (cond(G) * 1e-32).
   const double rc = 2.220446049250313e-16 * (double)((N - p) > p ? (N - p) : p);
   const double tiny = fmax(1e-26, rc * rc) * trace_s.hi;
+  // (apart from ar_solve_kernel's factorisation: the pivot rule is this relative cut, not "> 0", and no dmax / dmin is kept)
   for (int k = 0; k < p; ++k) {
     if (tid == 0) {
       const dd d = G[(long long)k * p + k];
@@ -1066,27 +1028,14 @@ __global__ __launch_bounds__(SV_THREADS) void ar_solve_dd_kernel(const double* _
     // element that came here on its condition estimate alone still carries status 0 (its float64 pivots stayed positive by
     // rounding noise) and would otherwise be refined from a meaningless float64 factor and reported as solved.  Status 1
     // hands it to ira_ar_minnorm, which returns lstsq's minimum-norm solution (status 4 + rank).
-    if (tid == 0) info[IRA_AR_INFO_DOUBLES * e + 0] = 1.0;
+    if (tid == 0) ar_status_store(info, e, IRA_AR_STATUS_PIVOT);
     return;
   }
-  for (int k = 0; k < p; ++k) {                         // L y = r
-    if (tid == 0) vec[k] = dd_div(vec[k], G[(long long)k * p + k]);
-    __syncthreads();
-    const dd yk = vec[k];
-    for (int i = k + 1 + tid; i < p; i += SV_THREADS) vec[i] = dd_add(vec[i], dd_neg(dd_mul(G[(long long)i * p + k], yk)));
-    __syncthreads();
-  }
-  for (int k = p - 1; k >= 0; --k) {                    // L^T a = y
-    if (tid == 0) vec[k] = dd_div(vec[k], G[(long long)k * p + k]);
-    __syncthreads();
-    const dd ak = vec[k];
-    for (int i = tid; i < k; i += SV_THREADS) vec[i] = dd_add(vec[i], dd_neg(dd_mul(G[(long long)k * p + i], ak)));
-    __syncthreads();
-  }
+  chol_solve_inplace<dd, long long>(G, vec, p, tid);    // L y = r, L^T a = y
   double* co = coeffs + (long long)e * (p + 1);
   if (tid == 0) co[0] = 1.0;
   for (int j = tid; j < p; j += SV_THREADS) co[j + 1] = vec[j].hi + vec[j].lo;
-  if (tid == 0) info[IRA_AR_INFO_DOUBLES * e + 0] = AR_DD_SOLVED;
+  if (tid == 0) ar_status_store(info, e, IRA_AR_STATUS_EXACT);
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -1118,40 +1067,14 @@ __global__ __launch_bounds__(SV_THREADS) void ar_minnorm_kernel(const double* __
   __shared__ double off_s, diag_s;
   __shared__ int bad_s;
   const int e = blockIdx.x, tid = threadIdx.x;
-  if (info[IRA_AR_INFO_DOUBLES * e + 0] != 1.0) return;
+  if (ar_status(info, e) != IRA_AR_STATUS_PIVOT) return;
   const long long N = nlen[e];
   double* A = scratch2 + (long long)e * 2 * p * p;
   double* V = A + (long long)p * p;
-  // ---- G and r from the lag sums and the head/tail samples, exactly as ar_solve_kernel assembles them --------------------
-  {
-    const int nlag = p + 1;
-    const double* rec = part + (long long)e * lag_rec_doubles;
-    const double* head = rec + (long long)lag_nchunks_max * nlag;
-    const double* tail = head + nlag;
-    const int lchunks = lag_chunks(N, p);
-    for (int d = tid; d < nlag; d += SV_THREADS) {
-      double c = 0.0;
-      for (int ch = 0; ch < lchunks; ++ch) c += rec[(long long)ch * nlag + d];
-      if (d >= 1) vec[d - 1] = -c;
-      double run = c, comp = 0.0;
-      for (int a = 1; a + d <= p; ++a) {
-        const int m = a - 1;
-        const double t1 = head[p - 1 - m] * head[p - 1 - m - d];
-        const double t2 = -tail[m] * tail[m + d];
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-          const double term = q == 0 ? t1 : t2;
-          const double t = run + term;
-          comp += (fabs(run) >= fabs(term)) ? (run - t) + term : (term - t) + run;
-          run = t;
-        }
-        const double v = run + comp;
-        const int r = a + d - 1, cidx = a - 1;
-        A[r * p + cidx] = v;
-        A[cidx * p + r] = v;
-      }
-    }
-  }
+  // ---- G (no ridge, mirrored into A) and r from the lag sums and the head/tail samples, by ar_solve_kernel's own assembly ----
+  gram_from_lags<SV_THREADS, false>(
+      lag_record_of(part, e, lag_rec_doubles, lag_nchunks_max, N, p), p, tid, 0.0,
+      [=](int r, int c, double v) { A[r * p + c] = v; A[c * p + r] = v; }, [=](int j, double v) { vec[j] = v; });
   for (int idx = tid; idx < p * p; idx += SV_THREADS) V[idx] = (idx / p == idx % p) ? 1.0 : 0.0;
   if (tid == 0) bad_s = 0;
   __syncthreads();
@@ -1167,7 +1090,7 @@ __global__ __launch_bounds__(SV_THREADS) void ar_minnorm_kernel(const double* __
     // a NaN or infinite sample: the reference's lstsq raises LinAlgError ("SVD did not converge"); status 3, NaN coefficients
     const double qn = __longlong_as_double(0x7ff8000000000000ll);
     for (int j = tid; j < p; j += SV_THREADS) co[j + 1] = qn;
-    if (tid == 0) { co[0] = 1.0; info[IRA_AR_INFO_DOUBLES * e + 0] = 3.0; }
+    if (tid == 0) { co[0] = 1.0; ar_status_store(info, e, IRA_AR_STATUS_NOT_FINITE); }
     return;
   }
   // ---- cyclic Jacobi, round-robin pairing (circle method: player m-1 fixed, the others rotate) ------------------------------
@@ -1257,187 +1180,18 @@ __global__ __launch_bounds__(SV_THREADS) void ar_minnorm_kernel(const double* __
     int rank = 0;
     double lmin = INFINITY;
     for (int k = 0; k < p; ++k) { const double lam = A[k * p + k]; if (lam > cut && lam > 0.0) { ++rank; lmin = fmin(lmin, lam); } }
-    info[IRA_AR_INFO_DOUBLES * e + 0] = 4.0;                         // minimum-norm solution over `rank` directions
-    info[IRA_AR_INFO_DOUBLES * e + 1] = lmax;
-    info[IRA_AR_INFO_DOUBLES * e + 2] = rank ? lmin : 0.0;
-    info[IRA_AR_INFO_DOUBLES * e + 3] = (double)rank;
-  }
-}
-
-// ------------------------------------------------------------------------------------------------------------
-// Aberth-Ehrlich: all roots of c[0] z^n + ... + c[n] (descending powers), float64 complex.
-// One workgroup per polynomial, one thread per root (n <= 1024).  Jacobi-style sweeps (all corrections from
-// the previous iterate) keep it deterministic.  Leading/trailing handling follows the reference: trailing
-// |c| < trail_eps coefficients are dropped first (zplane.py:153-155), then numpy.roots semantics (leading
-// zeros stripped; exact trailing zeros become roots at 0).
-// ------------------------------------------------------------------------------------------------------------
-constexpr int RT_MAX_DEG = 1024;
-constexpr int RT_MAX_ITERS = 200;
-constexpr double RT_ZERO_TOL = 2.0 * 1.1102230246251565e-16;   // 2 u, u = 2^-53
-
-struct cdbl { double re, im; };
-__device__ __forceinline__ cdbl c_mul(cdbl a, cdbl b) { return {a.re * b.re - a.im * b.im, a.re * b.im + a.im * b.re}; }
-__device__ __forceinline__ cdbl c_div(cdbl a, cdbl b) {
-  // Smith's algorithm
-  if (fabs(b.re) >= fabs(b.im)) {
-    const double r = b.im / b.re, d = b.re + b.im * r;
-    return {(a.re + a.im * r) / d, (a.im - a.re * r) / d};
-  }
-  const double r = b.re / b.im, d = b.re * r + b.im;
-  return {(a.re * r + a.im) / d, (a.im * r - a.re) / d};
-}
-
-// LPR lanes per root (round 4): the sum over the other roots, 1 / (z_k - z_j) -- a float64 reciprocal per pair, four fifths
-// of an iteration -- is dealt to LPR neighbouring lanes and combined with two DPP shuffles; the Horner chain (serial by
-// nature) is evaluated by every lane of the group.  One lane per root kept a 64-root polynomial on ONE wave for ~20
-// iterations of ~14 k cycles each: 0.15-0.18 ms per 256 polynomials at a quarter of the SIMDs.
-template <int LPR>
-__global__ void poly_roots_kernel(const double* __restrict__ coeffs, int stride, int ncoef, double trail_eps,
-                                  double* __restrict__ roots, int32_t* __restrict__ nroots_out) {
-  __shared__ double c[RT_MAX_DEG + 1];
-  __shared__ cdbl z[2][RT_MAX_DEG];
-  __shared__ int sh_lo, sh_hi, sh_changed;
-  const int e = blockIdx.x, nt = blockDim.x / LPR;
-  const int tid = threadIdx.x / LPR, part = threadIdx.x % LPR;     // root slot and the lane's share of the pair sum
-  const double* ce = coeffs + (long long)e * stride;
-  double* re = roots + (long long)e * 2 * (ncoef - 1);
-  if (threadIdx.x == 0) {
-    int hi = ncoef;   // exclusive end after trimming tiny trailing coefficients
-    while (hi > 1 && fabs(ce[hi - 1]) < trail_eps) --hi;
-    int lo = 0;       // strip leading exact zeros (numpy.roots)
-    while (lo < hi && ce[lo] == 0.0) ++lo;
-    sh_lo = lo; sh_hi = hi;
-  }
-  __syncthreads();
-  int lo = sh_lo, hi = sh_hi;
-  if (hi - lo <= 1 || hi <= 1) {
-    if (threadIdx.x == 0) nroots_out[e] = 0;
-    return;
-  }
-  // exact trailing zeros -> roots at the origin
-  int tz = 0;
-  while (hi - 1 - tz > lo && ce[hi - 1 - tz] == 0.0) ++tz;
-  const int n = hi - lo - 1 - tz;   // degree of the deflated polynomial
-  const double lead = ce[lo];
-  for (int k = threadIdx.x; k <= n; k += blockDim.x) c[k] = ce[lo + k] / lead;   // monic
-  __syncthreads();
-  if (n >= 1) {
-    // initial radius: geometric mean of the root moduli, |c_n|^(1/n), kept in a sane range
-    double r0 = pow(fabs(c[n]), 1.0 / (double)n);
-    if (!(r0 > 1e-3)) r0 = 1e-3;
-    if (r0 > 1e3) r0 = 1e3;
-    for (int k = threadIdx.x; k < n; k += blockDim.x) {
-      double s, co;
-      sincos(2.0 * 3.14159265358979323846 * (double)k / (double)n + 0.4, &s, &co);
-      z[0][k] = {r0 * co, r0 * s};
-    }
-    __syncthreads();
-    int cur = 0;
-    for (int it = 0; it < RT_MAX_ITERS; ++it) {
-      if (threadIdx.x == 0) sh_changed = 0;
-      __syncthreads();
-      int changed = 0;
-      // (every lane of a group runs the same trip count: the shuffles below need the whole group)
-      for (int k0 = tid; k0 < ((n + nt - 1) / nt) * nt; k0 += nt) {
-        const bool live = k0 < n;
-        const int k = live ? k0 : n - 1;
-        const cdbl zk = z[cur][k];
-        // Newton ratio p / p' and "p(zk) != 0".  The lanes of a group share zk: every branch here is uniform across them.
-        // p counts as zero, and the iterate stays where it is, once |p| is within RT_ZERO_TOL (two units roundoff) of
-        // sv = sum_k |c_k| |zk|^(n-k): Horner's own rounding error is of that size, a correction computed from such a p is noise.
-        // At an m-fold root every sweep is noise once the iterates are within u^(1/m) of it; this test is what ends them there.
-        // Outside the unit circle |zk|^n overflows long before the iterate is unreasonable (|zk| > 2 at n = 1024), and one NaN
-        // iterate enters every other root's pair sum.  There, with y = 1 / zk and q(y) = 1 + c_1 y + ... + c_n y^n,
-        // p(z) = z^n q(y) and p / p' = 1 / (y (n - y q'(y) / q(y))), every power at most 1 in modulus: the same Horner
-        // recurrence on the coefficients in reverse order at y (one loop for both, so that a wave with iterates on both
-        // sides of the circle does not run two).
-        const bool outside = zk.re * zk.re + zk.im * zk.im > 1.0;
-        const cdbl x = outside ? c_div(cdbl{1.0, 0.0}, zk) : zk;
-        const double ax = sqrt(x.re * x.re + x.im * x.im);
-        const int step = outside ? -1 : 1;
-        int idx = outside ? n : 0;
-        cdbl pv = {c[idx], 0.0}, dv = {0.0, 0.0};           // p and p' at zk, or q and q' at y
-        double sv = fabs(c[idx]);
-        for (int m = 1; m <= n; ++m) {
-          idx += step;
-          const double cm = c[idx];
-          dv = c_mul(dv, x); dv.re += pv.re; dv.im += pv.im;
-          pv = c_mul(pv, x); pv.re += cm;
-          sv = sv * ax + fabs(cm);
-        }
-        const bool nonzero = fabs(pv.re) + fabs(pv.im) > RT_ZERO_TOL * sv;
-        cdbl ratio;
-        if (outside) {
-          const cdbl t = c_mul(x, c_div(dv, pv));
-          ratio = c_div(cdbl{1.0, 0.0}, c_mul(x, cdbl{(double)n - t.re, -t.im}));
-        } else {
-          ratio = c_div(pv, dv);
-        }
-        cdbl w = {0.0, 0.0};
-        if (nonzero) {
-          cdbl sum = {0.0, 0.0};
-          for (int j = part; j < n; j += LPR) {
-            if (j == k) continue;
-            const cdbl zj = z[cur][j];
-            const double dr = zk.re - zj.re, di = zk.im - zj.im;
-            const double d2 = dr * dr + di * di;
-            // 1/(zk - zj) = conj(d)/|d|^2; coincident iterates (a multiple root) add nothing instead of 0 * inf
-            const double inv = d2 != 0.0 ? 1.0 / d2 : 0.0;
-            sum.re += dr * inv; sum.im -= di * inv;
-          }
-          if (LPR > 1) {
-#pragma unroll
-            for (int o = 1; o < LPR; o <<= 1) {                // the group's lanes are neighbours: xor 1, xor 2
-              sum.re += __shfl_xor(sum.re, o, 64);
-              sum.im += __shfl_xor(sum.im, o, 64);
-            }
-          }
-          const cdbl rs = c_mul(ratio, sum);
-          w = c_div(ratio, cdbl{1.0 - rs.re, -rs.im});
-        }
-        if (live && part == 0) z[cur ^ 1][k] = {zk.re - w.re, zk.im - w.im};
-        const double wm = fabs(w.re) + fabs(w.im), zm = fabs(zk.re) + fabs(zk.im);
-        if (live && wm > 2e-13 * zm) changed = 1;
-      }
-      if (changed) sh_changed = 1;   // benign race: every writer stores 1
-      __syncthreads();
-      cur ^= 1;
-      const int any = sh_changed;
-      __syncthreads();
-      if (!any) break;
-    }
-    for (int k = threadIdx.x; k < n; k += blockDim.x) { re[2 * k] = z[cur][k].re; re[2 * k + 1] = z[cur][k].im; }
-  }
-  for (int k = n + threadIdx.x; k < n + tz; k += blockDim.x) { re[2 * k] = 0.0; re[2 * k + 1] = 0.0; }
-  if (threadIdx.x == 0) nroots_out[e] = n + tz;
-}
-
-// b[n] = sum_{k=0..p} a[k] h[n-k], 0 <= n-k < N; h = x / divisor (float64)
-__global__ void fir_numerator_kernel(const double* __restrict__ coeffs, int p, const float* __restrict__ x,
-                                     const int64_t* __restrict__ xoff, const int32_t* __restrict__ nlen,
-                                     const double* __restrict__ divisor, int q, double* __restrict__ b) {
-  const int e = blockIdx.x;
-  const double* a = coeffs + (long long)e * (p + 1);
-  const float* xs = x + xoff[e];
-  const double div = divisor ? divisor[e] : 1.0;
-  const long long N = nlen[e];
-  for (int n = threadIdx.x; n <= q; n += blockDim.x) {
-    double acc = 0.0;
-    for (int k = 0; k <= p; ++k) {
-      const long long m = (long long)n - k;
-      if (m < 0 || m >= N) continue;
-      acc += a[k] * ((double)xs[m] / div);
-    }
-    b[(long long)e * (q + 1) + n] = acc;
+    ar_info_store(info, e, IRA_AR_STATUS_MINNORM, lmax, rank ? lmin : 0.0, (double)rank);   // over `rank` directions
   }
 }
 
 }  // namespace
 
+// an order and a longest element the kernels take: the sizers return 0 otherwise, the entry points IRA_E_SIZE
+static inline bool ar_order_ok(int32_t order, int32_t max_len) { return order >= 1 && order <= GR_MAX_P && max_len > order; }
+
 extern "C" int64_t ira_ar_partial_doubles(int32_t p, int32_t max_len) {
-  if (p < 1 || p > GR_MAX_P || max_len <= p) return 0;
-  const int64_t nchunks = ((int64_t)max_len - p + GR_CHUNK - 1) / GR_CHUNK;
-  const int64_t dense = nchunks * groups_total(p) * (int64_t)GR_PART;       // MFMA Gram partials (IRA_AR_DENSE)
+  if (!ar_order_ok(p, max_len)) return 0;
+  const int64_t dense = (int64_t)gram_chunks(max_len, p) * groups_total(p) * (int64_t)GR_PART;   // MFMA Gram partials
   const int64_t lag = lag_record_doubles(max_len, p);                        // lag sums + head/tail samples
   return dense > lag ? dense : lag;
 }
@@ -1452,8 +1206,33 @@ static inline bool ar_wave_solve(int32_t flags, int order) {
 
 static int32_t ar_check(int32_t nb, int32_t max_len, int32_t order) {
   if (nb < 0) return IRA_E_SIZE;
-  if (order < 1 || order > GR_MAX_P || max_len <= order) return IRA_E_SIZE;
+  if (!ar_order_ok(order, max_len)) return IRA_E_SIZE;
   if (nb > 65535 || groups_total(order) > 65535) return IRA_E_SIZE;
+  return IRA_OK;
+}
+
+// dynamic LDS of ar_solve_kernel: the vector, then G itself (order <= SV_LDS_P) or the blocked factorisation's panel + diagonal block
+static size_t solve_lds_bytes(int order) {
+  return sizeof(double) * ((size_t)order + (order <= SV_LDS_P ? (size_t)order * order : sv_blocked_lds_doubles(order)));
+}
+
+// One solve over the partial record: a first solve (grad_dev == nullptr) or a refinement step, on one wave per element or on
+// a workgroup (ar_wave_solve).  Returns the status of the LDS opt-in; the caller reports the launch.
+static int32_t launch_solve(const double* partial_dev, const int32_t* len_dev, int32_t nb, int32_t max_len, int32_t order,
+                            double ridge, double* gscratch_dev, double* coeffs_dev, double* info_dev, int32_t flags,
+                            const double* grad_dev, double cond_threshold, hipStream_t st) {
+  const int lchunks = lag_chunks(max_len, order);
+  const long long rec_doubles = lag_record_doubles(max_len, order);
+  if (ar_wave_solve(flags, order)) {
+    ar_solve_wave_kernel<<<nb, 64, 0, st>>>(partial_dev, len_dev, order, ridge, coeffs_dev, info_dev, lchunks, rec_doubles,
+                                            grad_dev, cond_threshold);
+    return IRA_OK;
+  }
+  const size_t lds = solve_lds_bytes(order);
+  IRA_TRY_HIP(allow_lds(&ar_solve_kernel, lds));
+  ar_solve_kernel<<<nb, SV_THREADS, lds, st>>>(partial_dev, len_dev, order, gram_chunks(max_len, order), ridge, gscratch_dev,
+                                               coeffs_dev, info_dev, ar_dense(flags) ? 0 : 1, lchunks, rec_doubles, grad_dev,
+                                               cond_threshold);
   return IRA_OK;
 }
 
@@ -1487,7 +1266,7 @@ extern "C" int32_t ira_ar_gram(const float* x_dev, const double* x64_dev, const 
     if (lrc != IRA_OK) return lrc;
     IRA_RETURN_LAUNCH();
   }
-  const int nchunks = (int)(((int64_t)max_len - order + GR_CHUNK - 1) / GR_CHUNK);
+  const int nchunks = gram_chunks(max_len, order);
   const int gs = groups_side(order);
   ar_gram_kernel<true><<<dim3(nchunks, gs, nb), 64, 0, (hipStream_t)stream>>>(
       x64_dev ? nullptr : x_dev, x64_dev, xoff_dev, len_dev, divisor_dev, order, nchunks, partial_dev);
@@ -1504,21 +1283,9 @@ extern "C" int32_t ira_ar_solve(const double* partial_dev, const int32_t* len_de
   const int32_t rc = ar_check(nb, max_len, order);
   if (rc != IRA_OK || nb == 0) return rc;
   if (order > SV_LDS_P && gscratch_dev == nullptr) return IRA_E_NULL;
-  const int nchunks = (int)(((int64_t)max_len - order + GR_CHUNK - 1) / GR_CHUNK);
-  size_t lds = sizeof(double) * (size_t)order;
-  if (order <= SV_LDS_P) lds += sizeof(double) * (size_t)order * order;
-  else lds += sizeof(double) * sv_blocked_lds_doubles(order);        // panel + diagonal block of the blocked factorisation
-  IRA_TRY_HIP(allow_lds(&ar_solve_kernel, lds));
-  if (ar_wave_solve(flags, order)) {
-    ar_solve_wave_kernel<<<nb, 64, 0, (hipStream_t)stream>>>(partial_dev, len_dev, order, ridge, coeffs_dev, info_dev,
-                                                              lag_chunks(max_len, order), lag_record_doubles(max_len, order),
-                                                              nullptr, 0.0);
-    IRA_RETURN_LAUNCH();
-  }
-  ar_solve_kernel<<<nb, SV_THREADS, lds, (hipStream_t)stream>>>(partial_dev, len_dev, order, nchunks, ridge,
-                                                                 gscratch_dev, coeffs_dev, info_dev,
-                                                                 ar_dense(flags) ? 0 : 1, lag_chunks(max_len, order),
-                                                                 lag_record_doubles(max_len, order), nullptr, 0.0);
+  const int32_t lrc = launch_solve(partial_dev, len_dev, nb, max_len, order, ridge, gscratch_dev, coeffs_dev, info_dev, flags,
+                                   nullptr, 0.0, (hipStream_t)stream);
+  if (lrc != IRA_OK) return lrc;
   IRA_RETURN_LAUNCH();
 }
 
@@ -1538,7 +1305,7 @@ extern "C" int32_t ira_ar_minnorm(const double* partial_dev, const int32_t* len_
 
 
 extern "C" int64_t ira_ar_exact_doubles(int32_t order, int32_t max_len, int32_t which) {
-  if (order < 1 || order > GR_MAX_P || max_len <= order) return 0;
+  if (!ar_order_ok(order, max_len)) return 0;
   if (which == 0) return 2ll * lag_chunks(max_len, order) * (order + 1);          // double-double lag-sum partials
   return 2ll * ((int64_t)order * order + order);                                    // Gram matrix + vector
 }
@@ -1582,23 +1349,14 @@ extern "C" int32_t ira_ar_refine(const float* x_dev, const double* x64_dev, cons
   const int nsub = ngroups >= LAG_THREADS ? 1 : LAG_THREADS / ngroups;
   const size_t lds_g = sizeof(double) * ((size_t)(order + 3) + 2 * LAG_CHUNK + nlag + (size_t)nsub * 4 * ngroups);
   IRA_TRY_HIP(allow_lds(&ar_grad_kernel, lds_g));
-  const int nchunks = (int)(((int64_t)max_len - order + GR_CHUNK - 1) / GR_CHUNK);
-  size_t lds_s = sizeof(double) * (size_t)order;
-  if (order <= SV_LDS_P) lds_s += sizeof(double) * (size_t)order * order;
-  else lds_s += sizeof(double) * sv_blocked_lds_doubles(order);
-  IRA_TRY_HIP(allow_lds(&ar_solve_kernel, lds_s));
   hipStream_t st = (hipStream_t)stream;
   for (int it = 0; it < steps; ++it) {
     ar_grad_kernel<<<dim3(lchunks, 1, nb), LAG_THREADS, lds_g, st>>>(x64_dev ? nullptr : x_dev, x64_dev, xoff_dev, len_dev,
                                                                       divisor_dev, order, lchunks, coeffs_dev, info_dev,
                                                                       cond_threshold, grad_dev);
-    if (ar_wave_solve(flags, order))
-      ar_solve_wave_kernel<<<nb, 64, 0, st>>>(partial_dev, len_dev, order, 0.0, coeffs_dev, info_dev, lchunks,
-                                              lag_record_doubles(max_len, order), grad_dev, cond_threshold);
-    else
-      ar_solve_kernel<<<nb, SV_THREADS, lds_s, st>>>(partial_dev, len_dev, order, nchunks, 0.0, gscratch_dev, coeffs_dev,
-                                                      info_dev, ar_dense(flags) ? 0 : 1, lchunks,
-                                                      lag_record_doubles(max_len, order), grad_dev, cond_threshold);
+    const int32_t lrc = launch_solve(partial_dev, len_dev, nb, max_len, order, 0.0, gscratch_dev, coeffs_dev, info_dev, flags,
+                                     grad_dev, cond_threshold, st);
+    if (lrc != IRA_OK) return lrc;
   }
   IRA_RETURN_LAUNCH();
 }
@@ -1610,33 +1368,4 @@ extern "C" int32_t ira_ar_fit(const float* x_dev, const double* x64_dev, const i
   int32_t rc = ira_ar_gram(x_dev, x64_dev, xoff_dev, len_dev, divisor_dev, nb, max_len, order, partial_dev, flags, stream);
   if (rc != IRA_OK) return rc;
   return ira_ar_solve(partial_dev, len_dev, nb, max_len, order, ridge, gscratch_dev, coeffs_dev, info_dev, flags, stream);
-}
-
-extern "C" int32_t ira_poly_roots(const double* coeffs_dev, int32_t npoly, int32_t ncoef, double trail_eps,
-                                  double* roots_dev, int32_t* nroots_dev, void* stream) {
-  IRA_CHECK_PTR(coeffs_dev); IRA_CHECK_PTR(roots_dev); IRA_CHECK_PTR(nroots_dev);
-  if (npoly <= 0) return npoly == 0 ? IRA_OK : IRA_E_SIZE;
-  if (ncoef < 2 || ncoef - 1 > RT_MAX_DEG) return IRA_E_SIZE;
-  int threads = 64;
-  while (threads < ncoef - 1 && threads < 1024) threads <<= 1;
-  if (threads <= 256) {                                      // four lanes per root while a workgroup can hold them
-    poly_roots_kernel<4><<<npoly, 4 * threads, 0, (hipStream_t)stream>>>(coeffs_dev, ncoef, ncoef, trail_eps, roots_dev,
-                                                                        nroots_dev);
-    IRA_RETURN_LAUNCH();
-  }
-  poly_roots_kernel<1><<<npoly, threads, 0, (hipStream_t)stream>>>(coeffs_dev, ncoef, ncoef, trail_eps, roots_dev,
-                                                               nroots_dev);
-  IRA_RETURN_LAUNCH();
-}
-
-extern "C" int32_t ira_fir_numerator(const double* coeffs_dev, int32_t order, const float* x_dev,
-                                     const int64_t* xoff_dev, const int32_t* len_dev, const double* divisor_dev,
-                                     int32_t nb, int32_t zero_order, double* b_dev, void* stream) {
-  IRA_CHECK_PTR(coeffs_dev); IRA_CHECK_PTR(x_dev); IRA_CHECK_PTR(xoff_dev); IRA_CHECK_PTR(len_dev);
-  IRA_CHECK_PTR(b_dev);
-  if (nb <= 0) return nb == 0 ? IRA_OK : IRA_E_SIZE;
-  if (order < 0 || zero_order < 0) return IRA_E_SIZE;
-  fir_numerator_kernel<<<nb, 128, 0, (hipStream_t)stream>>>(coeffs_dev, order, x_dev, xoff_dev, len_dev,
-                                                            divisor_dev, zero_order, b_dev);
-  IRA_RETURN_LAUNCH();
 }

@@ -335,6 +335,12 @@ int32_t ira_log_smooth_db(float* mag_dev, const int64_t* off_dev, const int32_t*
  * start vector is orthogonal to the weak direction; the tests hold it above 0.25 cond(G), the smallest ratio measured
  * is recorded in tests/test_gpu_ar.py).  1 <= order <= 1024 < len. */
 #define IRA_AR_INFO_DOUBLES 4
+#define IRA_AR_STATUS_SOLVED 0       /* info[0], as listed above (stored as a double) */
+#define IRA_AR_STATUS_PIVOT 1
+#define IRA_AR_STATUS_REFINED 2
+#define IRA_AR_STATUS_NOT_FINITE 3
+#define IRA_AR_STATUS_MINNORM 4
+#define IRA_AR_STATUS_EXACT 5
 #define IRA_AR_DENSE_GRAM 1   /* flags: form G = A^T A as a dense contraction on the FP64 matrix cores (v_mfma_f64_16x16x4_f64)
                                * instead of the O(order * len) lag-sum form: the cross-check of the default path.  gram, solve
                                * and refine of one fit take the same flags (layout of partial_dev). */

@@ -1,5 +1,5 @@
 """
-Reference for the polynomial root finder and the FIR numerator (ira_ar.hip: poly_roots_kernel, fir_numerator_kernel): the
+Reference for the polynomial root finder and the FIR numerator (ira_roots.hip: poly_roots_kernel, fir_numerator_kernel): the
 yardsticks, the polynomial generators and the case lists of tests/test_gpu_roots.py.  Helper module, like decay_ref.py /
 sti_ref.py: it holds no tests and imports nothing of the product; tests/test_roots_ref_cpu.py pins it without a GPU.
 

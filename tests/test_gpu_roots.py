@@ -1,4 +1,4 @@
-"""poly_roots_kernel (Aberth-Ehrlich) and fir_numerator_kernel of ira_ar.hip, through Engine.poly_roots and
+"""poly_roots_kernel (Aberth-Ehrlich) and fir_numerator_kernel of ira_roots.hip, through Engine.poly_roots and
 Engine.fir_numerator, against the yardsticks of tests/roots_ref.py: the backward error of every returned root in long double
 (bound 4 n u, derived there), a Vieta completeness check (a duplicated root passes the backward error), and for the numerator
 a long-double convolution with the bound (p + 3) u sum_k |a_k h_(n-k)|.  numpy.roots is NOT the reference above degree 129:

@@ -7,7 +7,9 @@ Each file is compiled in both checkouts with the flags build.py uses for it (bui
 checkout this tool lives in) plus --cuda-device-only -S.  Per kernel: identical or not -- instruction lines only; comment
 lines, assembler directives, labels and with them the per-compilation __hip_cuid_* symbol are ignored -- then VGPR, SGPR,
 scratch bytes and instruction counts by class, as "A -> B" where they differ.  A kernel that differs but executes the same
-number of every opcode is marked "same opcodes": the two differ in instruction order and register numbers only."""
+number of every opcode is marked "same opcodes": the two differ in instruction order and register numbers only.
+A kernel is looked up in A by its symbol among ALL the files given, so one that moved to another file (or to a new one, which
+A does not have) is compared with the kernel it was: name both the file it left and the file it went to."""
 import collections, re, shutil, subprocess, sys, tempfile
 from concurrent.futures import ThreadPoolExecutor
 from pathlib import Path
@@ -30,6 +32,8 @@ def classify(op):
 
 
 def assembly(root, name, tuning, tmp):
+    if not (Path(root) / "audio_analysis_amd" / "csrc" / name).exists():      # a file only the other checkout has
+        return ""
     out = Path(tmp) / f"{Path(root).name}_{abs(hash(str(root)))}_{Path(name).stem}.s"
     cmd = [build._hipcc(), *build.COMMON, *(["-DIRA_TUNING_BUILD"] if tuning else []), *build.SOURCES[name],
            "--cuda-device-only", "-S", str(Path(root) / "audio_analysis_amd" / "csrc" / name), "-o", str(out)]
@@ -49,7 +53,8 @@ def kernels(text):
         for line in body.splitlines():
             line = line.split(";")[0].strip()
             if line and not line.startswith(".") and not line.endswith(":"):
-                ins.append(" ".join(line.split()))
+                ins.append(re.sub(r"\.LBB\d+_", ".LBB_", " ".join(line.split())))   # branch targets carry the function's
+                                                                                    # position in its file: not the kernel's own
         res = {key: int(re.search(r";\s*%s:\s*(\d+)" % tag, tail).group(1))
                for key, tag in (("VGPR", "NumVgprs"), ("SGPR", "TotalNumSgprs"), ("scratch", "ScratchSize"))}
         found[name] = (ins, res)
@@ -76,16 +81,20 @@ def main():
     with tempfile.TemporaryDirectory() as tmp, ThreadPoolExecutor(max_workers=8) as ex:
         texts = list(ex.map(lambda rf: assembly(rf[0], rf[1], tuning, tmp), [(r, f) for f in files for r in roots]))
     print(f"A = {roots[0]}   B = {roots[1]}   flags: {' '.join(build.COMMON)}{' -DIRA_TUNING_BUILD' if tuning else ''} + per file")
-    for i, f in enumerate(files):
-        a, b = kernels(texts[2 * i]), kernels(texts[2 * i + 1])
-        names = demangle(sorted(set(a) | set(b)))
+    per_file = [(kernels(texts[2 * i]), kernels(texts[2 * i + 1])) for i in range(len(files))]
+    in_a = {sym: (f, k) for f, (a, _) in zip(files, per_file) for sym, k in a.items()}      # symbol -> (A's file, kernel)
+    in_b = {sym for _, b in per_file for sym in b}
+    for f, (a, b) in zip(files, per_file):
+        names = demangle(sorted({s for s in a if s not in in_b} | set(b)))
         print(f"== {f}  {' '.join(build.SOURCES[f])}")
         for sym, name in names.items():
-            if sym not in a or sym not in b:
+            if sym not in in_a or sym not in b:
                 print(f"   {name}: only in {'A' if sym in a else 'B'}")
                 differ += 1
                 continue
-            (ia, ra), (ib, rb) = a[sym], b[sym]
+            (fa, (ia, ra)), (ib, rb) = in_a[sym], b[sym]
+            if fa != f:
+                name += f" (A: {fa})"
             ident = ia == ib
             same, differ = same + ident, differ + (not ident)
             ca, cb = (collections.Counter(classify(l.split()[0]) for l in x) for x in (ia, ib))
