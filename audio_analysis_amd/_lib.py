@@ -87,6 +87,9 @@ PROTOTYPES = {
     "ira_block_energy": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp]),
     "ira_lundeby_estimate": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, vp, i32, vp, vp, vp, vp]),
     "ira_edc_truncated": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, f64, f64, vp, vp, vp]),
+    "ira_multislope_points": (i32, [vp, vp, vp, vp, vp, vp, i32, vp, f64, vp, vp, vp, vp]),
+    "ira_multislope_gram": (i32, [vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, i32, vp, vp, i32, i32, i32, f64, i32, vp, vp]),
+    "ira_multislope_search": (i32, [i32, vp, vp, i32, vp, vp, i32, i32, i32, vp, i32, f64, f64, vp, vp, vp, vp]),
     "ira_mtf_scratch_doubles": (C.c_int64, [i32, C.c_int64, i32]),
     "ira_mtf_sums": (i32, [vp, vp, vp, vp, i32, C.c_int64, i32, vp, vp, vp]),
     "ira_harmonic_windows": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]),

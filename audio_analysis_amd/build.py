@@ -47,6 +47,9 @@ SOURCES = {
     "ira_xcorr.hip": ["-ffp-contract=off"],
     # float64 block energies, regression sums and suffix sums round one operation at a time
     "ira_lundeby.hip": ["-ffp-contract=off"],
+    # multi-slope fits: sums and solves are compared with a long-double restatement that rounds one operation at a time, and
+    # the search's argmin must not depend on what the optimiser fused; the Gram sums call fma themselves
+    "ira_multislope.hip": ["-ffp-contract=off"],
     # modulation transfer sums: compared only with themselves and to 1e-10 with a long-double restatement; FMAs wanted
     "ira_mtf.hip": [],
     # a harmonic segment sample is one float64 product rounded once to float32, bit for bit NumPy's

@@ -41,6 +41,12 @@ LUNDEBY_DOUBLES = 16          # IRA_LUNDEBY_DOUBLES
 LUNDEBY_MAX_BLOCKS = 4096     # IRA_LUNDEBY_MAX_BLOCKS
 LUNDEBY_STAGE = 4096          # samples a workgroup of the two sample passes stages; the largest block size
 LUNDEBY_MAX_LEN = 2047 * 4096
+MS_DOUBLES = 16               # IRA_MS_DOUBLES
+MS_MAX_GRID = 128             # IRA_MS_MAX_GRID
+MS_MAX_ORDER = 3              # IRA_MS_MAX_ORDER
+MS_TILE = 32                  # IRA_MS_TILE: points of j a workgroup of ira_multislope_gram stages at a time
+MS_REFINE_R = 3               # IRA_MS_REFINE_R
+MS_REFINED = 21               # IRA_MS_REFINED: (2 R + 1) * MS_MAX_ORDER, the stride of the refined grids
 ECHO_DOUBLES = 8              # IRA_ECHO_DOUBLES
 ECHO_CHUNK = 4096             # IRA_ECHO_CHUNK: samples per workgroup of the two sample passes, counted from the onset
 ECHO_MAX_LAG = 2048           # IRA_ECHO_MAX_LAG: the largest D (the halo the emit pass keeps of the chunk in front)
@@ -120,6 +126,27 @@ def lundeby_layout(base_off, base_len, chan_of_seg, blk_size, nblk, first_m) -> 
     per_chunk = LUNDEBY_STAGE // np.maximum(b, 1)
     tabs["max_chunks"] = int(np.max(-(-(nb + 1) // per_chunk))) if n else 1
     return tabs
+
+
+def multislope_slot_doubles(max_g: int) -> int:
+    """Doubles of a Gram slot of ira_multislope_gram for grids of at most max_g decay times: the lower triangle over the
+    g decays, the noise term and the constant 1."""
+    return (int(max_g) + 2) * (int(max_g) + 3) // 2
+
+
+def multislope_jobs(jobs, width: int, nseg: int, ngrids: int, nslots: int, max_g: int) -> np.ndarray:
+    """A job table of ira_multislope_gram (width 3: row, grid slot, Gram slot) or ira_multislope_search (width 4: row,
+    order, Gram slot, grid slot) as int32 (njobs, width), checked on the host: ValueError for an index out of range."""
+    jobs = np.ascontiguousarray(jobs, dtype=np.int32).reshape(-1, width)
+    if not 1 <= int(max_g) <= MS_MAX_GRID:
+        raise ValueError(f"a grid holds 1 .. {MS_MAX_GRID} decay times")
+    if jobs.size:
+        limits = (nseg, ngrids, nslots) if width == 3 else (nseg, MS_MAX_ORDER + 1, nslots, ngrids)
+        lows = (0, 0, 0) if width == 3 else (0, 1, 0, 0)
+        for col, (lo, hi) in enumerate(zip(lows, limits)):
+            if jobs[:, col].min() < lo or jobs[:, col].max() >= hi:
+                raise ValueError(f"column {col} of the job table must lie in [{lo}, {hi})")
+    return jobs
 
 
 @dataclass
@@ -982,6 +1009,74 @@ class Engine:
                                              _ptr(d_nb), _ptr(d_boff), n, rows["max_chunks"], _ptr(rec_dev), _ptr(lens_dev),
                                              _ptr(suffix_dev), float(eps), float(floor_db), _ptr(edc_dev), _ptr(d_eoff),
                                              self.stream), "ira_edc_truncated")
+
+    # ------------------------------------------------------------------ multi-slope decay fits
+    def multislope_points(self, rows, start_dev, blk_dev, fit_fraction: float):
+        """The Schroeder points of every row of the block-energy tables (ira_multislope_points).  Returns (d float64 device,
+        laid out like blk_dev; info int32 device (nseg, 2): row status and J; records float64 device
+        (nseg, MS_MAX_ORDER, MS_DOUBLES), which multislope_search fills)."""
+        t = self.torch
+        n = rows["nseg"]
+        if not 0.0 < float(fit_fraction) <= 1.0:
+            raise ValueError("fit_fraction must satisfy 0 < fit_fraction <= 1")
+        d = self.empty(rows["table_doubles"], t.float64)
+        info = self.empty(2 * n, t.int32)
+        rec = self.empty(n * MS_MAX_ORDER * MS_DOUBLES, t.float64)
+        if n:
+            _, d_len, d_ch, d_b, d_nb, _, d_boff = rows["dev"]
+            check(self.lib.ira_multislope_points(_ptr(d_len), _ptr(d_ch), _ptr(start_dev), _ptr(d_b), _ptr(d_nb), _ptr(d_boff),
+                                                 n, _ptr(blk_dev), float(fit_fraction), _ptr(d), _ptr(info), _ptr(rec),
+                                                 self.stream), "ira_multislope_points")
+        return d, info[: 2 * n].view(n, 2), rec[: n * MS_MAX_ORDER * MS_DOUBLES].view(n, MS_MAX_ORDER, MS_DOUBLES)
+
+    def multislope_gram(self, rows, start_dev, d_dev, info_dev, jobs, grid_dev, grid_n_dev, grid_stride: int, ngrids: int,
+                        max_g: int, sample_rate_hz: float, nslots: int, gram_dev=None):
+        """Gram matrices and right-hand sides (ira_multislope_gram).  jobs (njobs, 3): row, grid slot, Gram slot.  Returns
+        the float64 device array of nslots slots of multislope_slot_doubles(max_g) doubles (gram_dev if given)."""
+        t = self.torch
+        n = rows["nseg"]
+        jobs = multislope_jobs(jobs, 3, n, ngrids, nslots, max_g)
+        if int(grid_stride) < int(max_g):
+            raise ValueError("grid_stride must be at least max_g")
+        if not float(sample_rate_hz) > 0.0:
+            raise ValueError("the sample rate must be positive")
+        if gram_dev is None:
+            gram_dev = self.empty(int(nslots) * multislope_slot_doubles(max_g), t.float64)
+        if n and jobs.size:
+            _, d_len, d_ch, d_b, d_nb, _, d_boff = rows["dev"]
+            d_job, = self.job_tables(jobs.reshape(-1))
+            check(self.lib.ira_multislope_gram(_ptr(d_len), _ptr(d_ch), _ptr(start_dev), _ptr(d_b), _ptr(d_nb), _ptr(d_boff), n,
+                                               _ptr(d_dev), _ptr(info_dev), _ptr(d_job), int(jobs.shape[0]), _ptr(grid_dev),
+                                               _ptr(grid_n_dev), int(grid_stride), int(ngrids), int(max_g),
+                                               float(sample_rate_hz), int(nslots), _ptr(gram_dev), self.stream),
+                  "ira_multislope_gram")
+        return gram_dev
+
+    def multislope_search(self, nseg: int, info_dev, jobs, grid_dev, grid_n_dev, grid_stride: int, ngrids: int, max_g: int,
+                          gram_dev, nslots: int, min_ratio: float, rec_dev, refine_step: float = 0.0):
+        """The candidate search (ira_multislope_search) into rec_dev (multislope_points' records).  jobs (njobs, 4): row,
+        order, Gram slot, grid slot.  refine_step > 0: returns the next level's grids (float64 device
+        (nseg * MS_MAX_ORDER, MS_REFINED)) and their sizes (int32 device), slot row * MS_MAX_ORDER + order - 1; else None."""
+        t = self.torch
+        n = int(nseg)
+        jobs = multislope_jobs(jobs, 4, n, ngrids, nslots, max_g)
+        if int(grid_stride) < int(max_g):
+            raise ValueError("grid_stride must be at least max_g")
+        if not float(min_ratio) > 1.0:
+            raise ValueError("min_ratio must exceed 1")
+        if not (float(refine_step) >= 0.0 and math.isfinite(float(refine_step))):
+            raise ValueError("refine_step must be finite and >= 0")
+        out = None
+        if refine_step > 0.0:
+            out = (self.empty(n * MS_MAX_ORDER * MS_REFINED, t.float64), self.empty(n * MS_MAX_ORDER, t.int32))
+        if n and jobs.size:
+            d_job, = self.job_tables(jobs.reshape(-1))
+            check(self.lib.ira_multislope_search(n, _ptr(info_dev), _ptr(d_job), int(jobs.shape[0]), _ptr(grid_dev),
+                                                 _ptr(grid_n_dev), int(grid_stride), int(ngrids), int(max_g), _ptr(gram_dev),
+                                                 int(nslots), float(min_ratio), float(refine_step),
+                                                 _ptr(out[0]) if out else 0, _ptr(out[1]) if out else 0, _ptr(rec_dev),
+                                                 self.stream), "ira_multislope_search")
+        return out
 
     # ------------------------------------------------------------------ a4/a5/a16
     def curve_fits(self, y_dev, off: np.ndarray, lens: np.ndarray, t_mul: float, t_div: float,

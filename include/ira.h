@@ -651,6 +651,59 @@ int32_t ira_edc_truncated(const float* x_dev, const int64_t* base_off_dev, const
                           const double* rec_dev, const int64_t* len_dev, const double* suffix_dev, double eps,
                           double floor_db, float* edc_dev, const int64_t* edc_off_dev, void* stream);
 
+/* ---- Multi-slope decay fits (coupled rooms): sums of exponentials plus a noise term on the Schroeder curve -------------
+ * Nothing in the reference fits more than one slope; the three entry points below replace no reference function.  Host
+ * side and the algorithm they carry out, step by step: audio_analysis_amd/analyse/multislope.py
+ * (`python -m analyse.multislope`).  Rows and their tables (base_len .. blk_off, nseg <= 65535) are those of
+ * ira_block_energy, whose output blk_dev is the input here.  Float64 throughout, no atomics, every sum in an order that
+ * depends on the row alone: a row's records are bit-identical whatever the batch, its place in it or its alignment.
+ * Argument errors (IRA_E_NULL / IRA_E_SIZE) are reported before anything is launched; nseg = 0 or njobs = 0: IRA_OK.
+ * ira_multislope_points: d[j] = tail + E[nb - 1] + .. + E[j] for j < nb at blk_off_dev[row] of d_dev (laid out like
+ *   blk_dev; untouched on an error status); info_dev[2 row] = the row status (IRA_MS_SILENT .. IRA_MS_NON_FINITE, checked in
+ *   the order too short, non-finite, silent, zero in range), info_dev[2 row + 1] = J = max(1, floor(fit_fraction nb)), the
+ *   product rounded to float64, 0 < fit_fraction <= 1.  rec_dev: IRA_MS_MAX_ORDER records of IRA_MS_DOUBLES doubles per
+ *   row, written here as [0] status [1] J [14] d[0] and NaN elsewhere ([1] and [14] NaN too on an error status).
+ *   Rows with an error status are skipped by the two kernels below.
+ * ira_multislope_gram: job i = job_dev[3 i ..] = (row, grid slot, Gram slot).  Grid slot k holds grid_n_dev[k] <= max_g
+ *   ascending decay times in seconds at grid_dev + k grid_stride (grid_stride >= max_g, max_g <= IRA_MS_MAX_GRID).  With
+ *   g = the grid's size, functions 0 .. g - 1 the decays, g the noise term and g + 1 the constant 1, the Gram slot
+ *   (gram_dev + slot (max_g + 2)(max_g + 3) / 2) receives the lower triangle out[i (i + 1) / 2 + k], k <= i <= g + 1, of
+ *   sum_j u_i[j] u_k[j] over the J points: b is row g + 1.  Points are added in ascending j, IRA_MS_TILE of them staged
+ *   at a time.  Entries of job_dev outside [0, nseg), [0, ngrids), [0, nslots) are skipped.
+ * ira_multislope_search: job i = job_dev[4 i ..] = (row, order S in 1..IRA_MS_MAX_ORDER, Gram slot, grid slot): every
+ *   candidate of order S on that grid, with and without the noise term; min_ratio > 1.  The record of (row, S), at
+ *   rec_dev + (row IRA_MS_MAX_ORDER + S - 1) IRA_MS_DOUBLES:
+ *     [0] 0, or IRA_MS_NO_CANDIDATE (then only [0] and [15] are written) [1] J [2] 1 with the noise term, 0 without
+ *     [3] cost c [4..6] grid indices (-1 unused) [7..9] T_s seconds (NaN unused) [10..12] a_s (NaN unused) [13] a_nu (0
+ *     without the noise term) [14] d[0] [15] g.
+ *   refine_step > 0: the next level's grid, the ascending union of T_s exp(k refine_step), k = -IRA_MS_REFINE_R ..
+ *   IRA_MS_REFINE_R (equal values once), goes to grid_out_dev + (row IRA_MS_MAX_ORDER + S - 1) IRA_MS_REFINED, its size to
+ *   grid_n_out_dev at the same index (0 without a candidate); refine_step = 0: neither is touched (both may be NULL). */
+#define IRA_MS_DOUBLES 16
+#define IRA_MS_MAX_GRID 128
+#define IRA_MS_MAX_ORDER 3
+#define IRA_MS_TILE 32
+#define IRA_MS_REFINE_R 3
+#define IRA_MS_REFINED 21
+#define IRA_MS_SILENT 1
+#define IRA_MS_TOO_SHORT 2
+#define IRA_MS_ZERO_IN_RANGE 4
+#define IRA_MS_NON_FINITE 16
+#define IRA_MS_NO_CANDIDATE 32
+int32_t ira_multislope_points(const int64_t* base_len_dev, const int32_t* chan_of_seg_dev, const int64_t* start_dev,
+                              const int32_t* blk_size_dev, const int32_t* nblk_dev, const int64_t* blk_off_dev,
+                              int32_t nseg, const double* blk_dev, double fit_fraction, double* d_dev, int32_t* info_dev,
+                              double* rec_dev, void* stream);
+int32_t ira_multislope_gram(const int64_t* base_len_dev, const int32_t* chan_of_seg_dev, const int64_t* start_dev,
+                            const int32_t* blk_size_dev, const int32_t* nblk_dev, const int64_t* blk_off_dev, int32_t nseg,
+                            const double* d_dev, const int32_t* info_dev, const int32_t* job_dev, int32_t njobs,
+                            const double* grid_dev, const int32_t* grid_n_dev, int32_t grid_stride, int32_t ngrids,
+                            int32_t max_g, double sample_rate_hz, int32_t nslots, double* gram_dev, void* stream);
+int32_t ira_multislope_search(int32_t nseg, const int32_t* info_dev, const int32_t* job_dev, int32_t njobs,
+                              const double* grid_dev, const int32_t* grid_n_dev, int32_t grid_stride, int32_t ngrids,
+                              int32_t max_g, const double* gram_dev, int32_t nslots, double min_ratio, double refine_step,
+                              double* grid_out_dev, int32_t* grid_n_out_dev, double* rec_dev, void* stream);
+
 /* ---- IEC 60268-16 speech transmission index: modulation transfer sums of the squared response -----------------------
  * Nothing in the reference computes a modulation transfer function or an STI; both entry points replace nothing in the
  * reference.  Host side, with the definitions pinned: audio_analysis_amd/analyse/sti.py (`python -m analyse.sti`).
