@@ -12,6 +12,10 @@
 //   E3      the mirror partners Z[M - k] of the lane's bins k = q + 256 i, i < 8
 //   post    (Z[k], Z[M-k]) -> |X[k]|, |X[M-k]| in dB (table log2, ira_log.h), stored at out[t*F + k]; or linear magnitudes
 //           -> log-bin means
+// QUIET FRAMES skip the transform.  While step 1 forms the windowed samples it also sums their squares; |X[k]|^2 <= N sum(xw)^2
+// for every bin, so a frame with 4 N sum(xw)^2 <= floor^2 is floored on every row: it stores the floor (dB mode) or hands
+// the aggregation the floored linear value (log-bin mode) -- the very bytes the full path would have produced, for the
+// price of the loads, one reduction and one barrier.  The decaying tails of impulse responses are such frames.
 // 16-byte LDS accesses are served a quarter wave at a time: in every exchange the 16 lanes of a quarter differ in k1
 // (or in consecutive m), which the strides 129 and 1 map to distinct 16-byte bank groups: conflict free.
 // Why four waves per frame (profiles/r02_stft4_counters.txt): with two waves per frame (32 values per lane, 228 VGPRs, two
@@ -86,17 +90,20 @@ struct __attribute__((aligned(8))) dpair5 { double a, b; };
 // the frame is done once, before the frame loop: the XCD remap and (segment, chunk) decode, the segment's job values (as
 // scalars), the log2 table in LDS, the hull of the log bins and 10^(floor/20).  Only scalar state lives across the loop:
 // the frame's twiddle factors are reloaded per frame (they hit the caches), the frame alone needs 122 of the 128 VGPRs.
-// The loop body is the frame as described at the top of the file, barrier for barrier; its trip count is wave-uniform,
-// so every wave of the workgroup meets the same barriers.  The results do not depend on kfr: a frame's arithmetic reads
-// nothing of its neighbours.
+// The loop body is the frame as described at the top of the file, barrier for barrier, behind one more barrier at which
+// the waves agree whether the frame is quiet; its trip count and that decision are workgroup-uniform, so every wave of
+// the workgroup meets the same barriers.  The results do not depend on kfr: a frame's arithmetic reads nothing of its
+// neighbours.
 __global__ __launch_bounds__(TL5) __attribute__((amdgpu_waves_per_eu(4, 4))) void stft5_kernel(
     const float* __restrict__ x, const int64_t* __restrict__ off, const int32_t* __restrict__ nframes, int hop,
     const double* __restrict__ window, const cdd* __restrict__ tw, double floor_lin, float floor_db,
     float* __restrict__ out, const int64_t* __restrict__ out_off, const int32_t* __restrict__ frame_sel,
     const int64_t* __restrict__ sel_off, int lb_nbins, int lb_kbase, const int32_t* __restrict__ lb_first,
     const int32_t* __restrict__ lb_count, int kfr, int ablate) {
-  // ablate (IRA_STFT5_ABLATE, tuning build, timing only): 1 no window loads, 2 no sample loads, 4 no dB -> linear conversion
+  // ablate (IRA_STFT5_ABLATE, tuning build, timing only): 1 no window loads, 2 no sample loads, 4 no dB -> linear conversion;
+  // 256 (results unchanged: tests and A/B) every frame takes the full path, the quiet-frame shortcut is off
   __shared__ __attribute__((aligned(16))) cdd ex[EXC4];
+  __shared__ double wave_energy[2][TL5 / 64];      // per-wave sums of (xw)^2, one slot per frame parity
   __shared__ ira::LogTabEntry ltab[ira::LOGTAB_N];
   __shared__ int lb_range[2];
   __shared__ int frame_bad;
@@ -164,6 +171,7 @@ __global__ __launch_bounds__(TL5) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
 
     // ---- step 1 -----------------------------------------------------------------------------------------------
     cdd v[16];
+    double energy = 0.0;                           // the lane's share of sum (xw[n])^2, added where the products are made
     {
       float xa[16], xb[16];
       double wa[16], wb[16];
@@ -177,128 +185,183 @@ __global__ __launch_bounds__(TL5) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
       }
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-      for (int n1 = 0; n1 < 16; ++n1) v[n1] = {(double)xa[n1] * wa[n1], (double)xb[n1] * wb[n1]};
-    }
-    dft_dif<double, 16>(v);
-    ira::twiddle16<double, true>(v, tw[2 * q]);                 // W_M^(k1 q) = W_N^(2 q k1), k1 at v[brev(k1)]
-
-    // ---- E1: half-size exchange, lower lanes first --------------------------------------------------------------
-    cdd b[16];
-    if (lower) {
-#pragma unroll
-      for (int k1 = 0; k1 < 16; ++k1) ex[k1 * ROW4 + q] = v[brev_bits(k1, 4)];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int n2 = 0; n2 < 8; ++n2) b[n2] = ex[k1l * ROW4 + n2 * 16 + n3l];
-    __syncthreads();
-    if (!lower) {
-#pragma unroll
-      for (int k1 = 0; k1 < 16; ++k1) ex[k1 * ROW4 + (q - TL4)] = v[brev_bits(k1, 4)];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int n2 = 0; n2 < 8; ++n2) b[8 + n2] = ex[k1l * ROW4 + n2 * 16 + n3l];
-    __syncthreads();
-
-    // ---- step 2 and E2 -------------------------------------------------------------------------------------------
-    dft_dif<double, 16>(b);
-    ira::twiddle16<double, true>(b, tw[32 * n3l]);              // W_M^(16 k2 n3) = W_N^(32 n3 k2)
-    if (lower) {                                                 // n3 < 8
-#pragma unroll
-      for (int k2 = 0; k2 < 16; ++k2) ex[k1l + 16 * k2 + E2N4 * n3l] = b[brev_bits(k2, 4)];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int n3 = 0; n3 < 8; ++n3) v[n3] = ex[q + E2N4 * n3];
-    __syncthreads();
-    if (!lower) {
-#pragma unroll
-      for (int k2 = 0; k2 < 16; ++k2) ex[k1l + 16 * k2 + E2N4 * (n3l - 8)] = b[brev_bits(k2, 4)];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int n3 = 0; n3 < 8; ++n3) v[8 + n3] = ex[q + E2N4 * n3];
-    __syncthreads();
-
-    // ---- step 3: lane r = q holds Z[r + 256 k3] at v[brev(k3)] --------------------------------------------------------
-    dft_dif<double, 16>(v);
-
-    // ---- E3: the mirror partners only.  The post step pairs Z[k] with Z[M - k]; lane q keeps k = q + 256 i, i < 8, which
-    // it already holds (v[brev(i)]), and M - k = (256 - q) + 256 (15 - i) is entry k3 = 15 - i >= 8 of lane 256 - q: every
-    // lane publishes its upper eight values and reads eight of its partner's -- 256 bytes per lane through LDS and one
-    // barrier pair instead of the 512 bytes and two of the round-2 natural-order exchange (real parts, then imaginary
-    // parts, own values included).  Lane 0 pairs with itself: M - 256 i = 256 (16 - i), its own entry 16 - i; i = 0 pairs
-    // Z[0] with Z[0].
-    double zkr[8], zpr[8], zki[8], zpi[8], midr, midi;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) ex[j * TL5 + q] = v[brev_bits(8 + j, 4)];       // k3 = 8 + j
-    __syncthreads();
-    {
-      const int partner = (TL5 - q) & (TL5 - 1);
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        // partner entry k3 = 15 - i (slot 7 - i); lane 0: k3 = 16 - i (slot 8 - i), i = 0 -> Z[0] itself
-        const int slot = q == 0 ? 8 - i : 7 - i;
-        cdd zp = v[0];                                                             // Z[0] (lane 0, i = 0)
-        if (!(q == 0 && i == 0)) zp = ex[slot * TL5 + partner];
-        zkr[i] = v[brev_bits(i, 4)].re; zki[i] = v[brev_bits(i, 4)].im;
-        zpr[i] = zp.re; zpi[i] = zp.im;
+      for (int n1 = 0; n1 < 16; ++n1) {
+        v[n1] = {(double)xa[n1] * wa[n1], (double)xb[n1] * wb[n1]};
+        energy = fma(v[n1].re, v[n1].re, energy);
+        energy = fma(v[n1].im, v[n1].im, energy);
       }
     }
-    {
-      const cdd mid = ex[0];                                                       // Z[2048]: lane 0, k3 = 8
-      midr = mid.re; midi = mid.im;
-    }
-    // A NaN (or infinite) sample anywhere in the frame makes every bin of numpy's rfft NaN (modalcloud.py:150): it shows
-    // in Z[0] = sum of the packed inputs (lane 0, first pair; 0 * NaN at the Hann end points is NaN too).  One check per
-    // frame, written by lane 0 for EVERY frame: the flag of a bad frame does not outlive it.
-    if (q == 0) frame_bad = !((zkr[0] - zkr[0]) + (zki[0] - zki[0]) == 0.0) ? 1 : 0;
-    __syncthreads();                                            // E3 fully read; frame_bad visible
-    const bool bad_frame = frame_bad != 0;
 
-    // ---- post -------------------------------------------------------------------------------------------------
-    const cdd wlane = tw[q];
-    if (lb_nbins <= 0) {
-      // no barrier at the loop's tail here: the next frame's first LDS write (E1; frame_bad is written later still)
-      // follows the barrier above, behind which this frame reads only the table
-      float* fo = os + (int64_t)col * F4;
+    // ---- quiet frame? ---------------------------------------------------------------------------------------------
+    // Every bin obeys |X[k]|^2 <= N sum (xw[n])^2 (triangle inequality, then Cauchy-Schwarz; N = 8192).  When four times
+    // that bound (6 dB over the transform's float64 rounding, ~1e-13 of the bound) is at or under the floor, db_of4 and
+    // lin_of4 would take their floored branch on every row: the frame's output is known here, before any butterfly.  The
+    // bound is over the windowed values themselves and assumes nothing about the window table.  A NaN or an infinity makes
+    // the sum non-finite and the comparison false: such a frame takes the full path and its bad_frame handling.
+    // The waves' sums meet in wave_energy[frame parity]; every lane reads back the same four doubles and adds them in the
+    // same order, so the decision is the same in all four waves and they meet the same barriers.  Two slots because the
+    // dB-mode quiet path has no barrier behind it: a fast wave writes the NEXT frame's slot while a slow one still reads
+    // this one's.  The barrier below orders a slot's writes before its reads in this frame, and its reads in this frame
+    // before its next writes two frames on (the next frame's barrier lies between them).
+    double* we = wave_energy[col & 1];
+    {
+      const double wsum = ira::wave_sum(energy);
+      if ((q & 63) == 0) we[q >> 6] = wsum;
+    }
+    __syncthreads();
+    const double frame_energy = ira::uniform((we[0] + we[1]) + (we[2] + we[3]));
+    const bool quiet = !IRA_ABL(ablate & 256) && frame_energy * (4.0 * (2 * M4)) <= floor_pow;
+
+    bool bad_frame = false;                        // a quiet frame holds finite samples only
+    if (quiet) {
+      if (lb_nbins <= 0) {
+        // dB mode: the floor on all 4097 rows, with the lane mapping of the loud frame's stores.  No LDS access here.
+        float* fo = os + (int64_t)col * F4;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+          const int k = q + TL5 * i;
+          fo[k] = floor_db;
+          fo[M4 - k] = floor_db;                                                   // k = 0 -> bin M
+        }
+        if (q == 0) fo[M4 / 2] = floor_db;
+        continue;
+      }
+      // log-bin mode: the slots the post step fills, with the value lin_of4 gives a floored row; then the aggregation
+      // below, the code that sums a loud frame's rows.  (The previous frame's sums have read exd before its tail barrier.)
+      // The value passes through an empty asm statement as a scalar: taken as a vector register pair it is held across
+      // the frame loop for these stores alone, and the loud frame has no pair to spare (the pair was spilled to scratch).
+      double fl = floor_lin32;
+      asm volatile("" : "+s"(fl));
 #pragma unroll
       for (int i = 0; i < 8; ++i) {
         const int k = q + TL5 * i;
+        if (k >= k_lo && k < k_hi) exd[k] = fl;
+        if ((M4 - k) >= k_lo && (M4 - k) < k_hi) exd[M4 - k] = fl;
+      }
+      if (q == 0 && M4 / 2 >= k_lo && M4 / 2 < k_hi) exd[M4 / 2] = fl;
+    } else {
+      dft_dif<double, 16>(v);
+      ira::twiddle16<double, true>(v, tw[2 * q]);                 // W_M^(k1 q) = W_N^(2 q k1), k1 at v[brev(k1)]
+
+      // ---- E1: half-size exchange, lower lanes first --------------------------------------------------------------
+      cdd b[16];
+      if (lower) {
+#pragma unroll
+        for (int k1 = 0; k1 < 16; ++k1) ex[k1 * ROW4 + q] = v[brev_bits(k1, 4)];
+      }
+      __syncthreads();
+#pragma unroll
+      for (int n2 = 0; n2 < 8; ++n2) b[n2] = ex[k1l * ROW4 + n2 * 16 + n3l];
+      __syncthreads();
+      if (!lower) {
+#pragma unroll
+        for (int k1 = 0; k1 < 16; ++k1) ex[k1 * ROW4 + (q - TL4)] = v[brev_bits(k1, 4)];
+      }
+      __syncthreads();
+#pragma unroll
+      for (int n2 = 0; n2 < 8; ++n2) b[8 + n2] = ex[k1l * ROW4 + n2 * 16 + n3l];
+      __syncthreads();
+
+      // ---- step 2 and E2 -------------------------------------------------------------------------------------------
+      dft_dif<double, 16>(b);
+      ira::twiddle16<double, true>(b, tw[32 * n3l]);              // W_M^(16 k2 n3) = W_N^(32 n3 k2)
+      if (lower) {                                                 // n3 < 8
+#pragma unroll
+        for (int k2 = 0; k2 < 16; ++k2) ex[k1l + 16 * k2 + E2N4 * n3l] = b[brev_bits(k2, 4)];
+      }
+      __syncthreads();
+#pragma unroll
+      for (int n3 = 0; n3 < 8; ++n3) v[n3] = ex[q + E2N4 * n3];
+      __syncthreads();
+      if (!lower) {
+#pragma unroll
+        for (int k2 = 0; k2 < 16; ++k2) ex[k1l + 16 * k2 + E2N4 * (n3l - 8)] = b[brev_bits(k2, 4)];
+      }
+      __syncthreads();
+#pragma unroll
+      for (int n3 = 0; n3 < 8; ++n3) v[8 + n3] = ex[q + E2N4 * n3];
+      __syncthreads();
+
+      // ---- step 3: lane r = q holds Z[r + 256 k3] at v[brev(k3)] --------------------------------------------------------
+      dft_dif<double, 16>(v);
+
+      // ---- E3: the mirror partners only.  The post step pairs Z[k] with Z[M - k]; lane q keeps k = q + 256 i, i < 8, which
+      // it already holds (v[brev(i)]), and M - k = (256 - q) + 256 (15 - i) is entry k3 = 15 - i >= 8 of lane 256 - q: every
+      // lane publishes its upper eight values and reads eight of its partner's -- 256 bytes per lane through LDS and one
+      // barrier pair instead of the 512 bytes and two of the round-2 natural-order exchange (real parts, then imaginary
+      // parts, own values included).  Lane 0 pairs with itself: M - 256 i = 256 (16 - i), its own entry 16 - i; i = 0 pairs
+      // Z[0] with Z[0].
+      double zkr[8], zpr[8], zki[8], zpi[8], midr, midi;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) ex[j * TL5 + q] = v[brev_bits(8 + j, 4)];       // k3 = 8 + j
+      __syncthreads();
+      {
+        const int partner = (TL5 - q) & (TL5 - 1);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+          // partner entry k3 = 15 - i (slot 7 - i); lane 0: k3 = 16 - i (slot 8 - i), i = 0 -> Z[0] itself
+          const int slot = q == 0 ? 8 - i : 7 - i;
+          cdd zp = v[0];                                                             // Z[0] (lane 0, i = 0)
+          if (!(q == 0 && i == 0)) zp = ex[slot * TL5 + partner];
+          zkr[i] = v[brev_bits(i, 4)].re; zki[i] = v[brev_bits(i, 4)].im;
+          zpr[i] = zp.re; zpi[i] = zp.im;
+        }
+      }
+      {
+        const cdd mid = ex[0];                                                       // Z[2048]: lane 0, k3 = 8
+        midr = mid.re; midi = mid.im;
+      }
+      // A NaN (or infinite) sample anywhere in the frame makes every bin of numpy's rfft NaN (modalcloud.py:150): it shows
+      // in Z[0] = sum of the packed inputs (lane 0, first pair; 0 * NaN at the Hann end points is NaN too).  One check per
+      // frame, written by lane 0 for EVERY frame: the flag of a bad frame does not outlive it.
+      if (q == 0) frame_bad = !((zkr[0] - zkr[0]) + (zki[0] - zki[0]) == 0.0) ? 1 : 0;
+      __syncthreads();                                            // E3 fully read; frame_bad visible
+      bad_frame = frame_bad != 0;
+
+      // ---- post -------------------------------------------------------------------------------------------------
+      const cdd wlane = tw[q];
+      if (lb_nbins <= 0) {
+        // no barrier at the loop's tail here: the next frame's first write to ex (E1; frame_bad is written later still)
+        // follows the barrier above and the next frame's energy barrier, behind which this frame reads only the table;
+        // wave_energy is ordered by its own barrier and its two slots (see "quiet frame?")
+        float* fo = os + (int64_t)col * F4;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+          const int k = q + TL5 * i;
+          const cdd e = {0.5 * (zkr[i] + zpr[i]), 0.5 * (zki[i] - zpi[i])};
+          const cdd d = {0.5 * (zkr[i] - zpr[i]), 0.5 * (zki[i] + zpi[i])};
+          const cdd o = {d.im, -d.re};
+          const cdd wk = ira::cmul(wlane, wuni[i]);              // W_N^k = W_N^q W_N^(256 i); second factor wave-uniform
+          const cdd pp = ira::cmul(wk, o);
+          fo[k] = bad_frame ? qnan32 : db_of4(e.re + pp.re, e.im + pp.im, floor_pow, floor_db, ltab);
+          fo[M4 - k] = bad_frame ? qnan32 : db_of4(e.re - pp.re, e.im - pp.im, floor_pow, floor_db, ltab);   // k = 0 -> bin M
+        }
+        if (q == 0) fo[M4 / 2] = bad_frame ? qnan32 : db_of4(midr, midi, floor_pow, floor_db, ltab);
+        continue;
+      }
+      // ---- fused modal-cloud aggregation (reference modalcloud.py:176-207): the frame's dB values never leave the CU.
+      // float32 dB (the reference's STFT output type) -> linear magnitude 10^(dB/20) in float64 -> LDS; then log bin b is
+      // the mean of its rows, added in ascending order, -> 20 log10(max(., 1e-30)) -> float32 at out[b * T + frame].
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        const int k = q + TL5 * i;
+        const bool need_a = k >= k_lo && k < k_hi, need_b = (M4 - k) >= k_lo && (M4 - k) < k_hi;
+        if (!need_a && !need_b) continue;
         const cdd e = {0.5 * (zkr[i] + zpr[i]), 0.5 * (zki[i] - zpi[i])};
         const cdd d = {0.5 * (zkr[i] - zpr[i]), 0.5 * (zki[i] + zpi[i])};
         const cdd o = {d.im, -d.re};
-        const cdd wk = ira::cmul(wlane, wuni[i]);              // W_N^k = W_N^q W_N^(256 i); second factor wave-uniform
+        const cdd wk = ira::cmul(wlane, wuni[i]);
         const cdd pp = ira::cmul(wk, o);
-        fo[k] = bad_frame ? qnan32 : db_of4(e.re + pp.re, e.im + pp.im, floor_pow, floor_db, ltab);
-        fo[M4 - k] = bad_frame ? qnan32 : db_of4(e.re - pp.re, e.im - pp.im, floor_pow, floor_db, ltab);   // k = 0 -> bin M
+        if (IRA_ABL(ablate & 4)) {
+          if (need_a) exd[k] = e.re + pp.re;
+          if (need_b) exd[M4 - k] = e.im - pp.im;
+          continue;
+        }
+        if (need_a) exd[k] = lin_of4(e.re + pp.re, e.im + pp.im, floor_pow, floor_db, floor_lin32, ltab);
+        if (need_b) exd[M4 - k] = lin_of4(e.re - pp.re, e.im - pp.im, floor_pow, floor_db, floor_lin32, ltab);
       }
-      if (q == 0) fo[M4 / 2] = bad_frame ? qnan32 : db_of4(midr, midi, floor_pow, floor_db, ltab);
-      continue;
+      if (q == 0 && M4 / 2 >= k_lo && M4 / 2 < k_hi) exd[M4 / 2] = lin_of4(midr, midi, floor_pow, floor_db, floor_lin32, ltab);
     }
-    // ---- fused modal-cloud aggregation (reference modalcloud.py:176-207): the frame's dB values never leave the CU.
-    // float32 dB (the reference's STFT output type) -> linear magnitude 10^(dB/20) in float64 -> LDS; then log bin b is
-    // the mean of its rows, added in ascending order, -> 20 log10(max(., 1e-30)) -> float32 at out[b * T + frame].
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      const int k = q + TL5 * i;
-      const bool need_a = k >= k_lo && k < k_hi, need_b = (M4 - k) >= k_lo && (M4 - k) < k_hi;
-      if (!need_a && !need_b) continue;
-      const cdd e = {0.5 * (zkr[i] + zpr[i]), 0.5 * (zki[i] - zpi[i])};
-      const cdd d = {0.5 * (zkr[i] - zpr[i]), 0.5 * (zki[i] + zpi[i])};
-      const cdd o = {d.im, -d.re};
-      const cdd wk = ira::cmul(wlane, wuni[i]);
-      const cdd pp = ira::cmul(wk, o);
-      if (IRA_ABL(ablate & 4)) {
-        if (need_a) exd[k] = e.re + pp.re;
-        if (need_b) exd[M4 - k] = e.im - pp.im;
-        continue;
-      }
-      if (need_a) exd[k] = lin_of4(e.re + pp.re, e.im + pp.im, floor_pow, floor_db, floor_lin32, ltab);
-      if (need_b) exd[M4 - k] = lin_of4(e.re - pp.re, e.im - pp.im, floor_pow, floor_db, floor_lin32, ltab);
-    }
-    if (q == 0 && M4 / 2 >= k_lo && M4 / 2 < k_hi) exd[M4 / 2] = lin_of4(midr, midi, floor_pow, floor_db, floor_lin32, ltab);
     __syncthreads();
     for (int bb = q; bb < lb_nbins; bb += TL5) {
       const int c = lb_count[bb];
@@ -320,7 +383,7 @@ __global__ __launch_bounds__(TL5) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
       }
       os[(int64_t)bb * T_out + col] = (bad_frame && c > 0) ? qnan32 : val;
     }
-    __syncthreads();                               // the sums have read the buffer the next frame's E1 writes
+    __syncthreads();                               // the sums have read the buffer the next frame's E1 (or quiet path) writes
   }
 }
 
