@@ -16,6 +16,12 @@
 // for every bin, so a frame with 4 N sum(xw)^2 <= floor^2 is floored on every row: it stores the floor (dB mode) or hands
 // the aggregation the floored linear value (log-bin mode) -- the very bytes the full path would have produced, for the
 // price of the loads, one reduction and one barrier.  The decaying tails of impulse responses are such frames.
+// QUIET CHUNKS skip even that.  Without a frame selection a workgroup's frames are consecutive, and sum (x w)^2 over any of
+// them is at most max(w^2) times sum x^2 over the chunk's whole sample span: one pass over the span (11 776 samples for
+// eight frames at hop 512, against 8 x 8192 samples and as many window values) certifies all of them at once, and the
+// workgroup stores its floored values without a frame loop.  In log-bin mode the value a floored frame leaves in a log bin
+// depends on the bin alone: a quiet frame of an uncertified chunk takes it from a table the workgroup's first quiet frame
+// builds (quiet_val) instead of summing the same constant again.
 // 16-byte LDS accesses are served a quarter wave at a time: in every exchange the 16 lanes of a quarter differ in k1
 // (or in consecutive m), which the strides 129 and 1 map to distinct 16-byte bank groups: conflict free.
 // Why four waves per frame (profiles/r02_stft4_counters.txt): with two waves per frame (32 values per lane, 228 VGPRs, two
@@ -75,6 +81,26 @@ __device__ __forceinline__ double lin_of4(double re, double im, double floor_pow
   return g * fma(t, fma(t, 0.5, 1.0), 1.0);
 }
 
+// Log bin -> float32 dB: the mean of the bin's c rows r[0 .. c), added in ascending order, -> 20 log10(max(., 1e-30)).
+// CONST: every row holds the value cst (a floored frame), r is not read.  Both forms perform the same additions in the
+// same order -- the sum of c copies of cst is formed by c - 1 additions, not by a product -- so a floored frame gets the
+// bits the sum over the exchange buffer would have given it.
+template <bool CONST>
+__device__ __forceinline__ float logbin_mean_db(const double* r, double cst, int c, const ira::LogTabEntry* tab) {
+  double acc = CONST ? cst : r[0];
+  for (int k0 = 1; k0 < c; k0 += 8) {
+    double v8[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) v8[u] = (k0 + u < c) ? (CONST ? cst : r[k0 + u]) : 0.0;
+#pragma unroll
+    for (int u = 0; u < 8; ++u)
+      if (k0 + u < c) acc += v8[u];
+  }
+  // 20 log10 m through the table log2 (series to r^6: a few 1e-16 relative, invisible after the float32 rounding) --
+  // the library log10 was ~130 of the ~1800 instructions of every wave although only 240 lanes of a frame use it
+  return (float)(6.0205999132796239 * ira::log2_table<6>(fmax(acc / (double)c, 1e-30), tab));
+}
+
 constexpr int TL5 = 256;
 // Frames per workgroup (tuning build: IRA_STFT5_K).  Measured on the report step and on the kernel alone at 2, 4, 8, 16
 // (profiles/stft5_chunks_ab.txt): 8 is the fastest on both.  It amortises 7/8 of the per-workgroup set-up; at 16 the
@@ -85,6 +111,11 @@ constexpr int KF5 = 8;
 // frame * hop), so a sample pair is 4-byte aligned only; the window table is only known to be a double array.
 struct __attribute__((aligned(4))) fpair5 { float a, b; };
 struct __attribute__((aligned(8))) dpair5 { double a, b; };
+typedef float fquad5 __attribute__((ext_vector_type(4), aligned(4)));   // four samples of a span that starts at any sample
+// The chunk test is made where the chunk's sample span is at most this many samples: twice n_fft, hop <= 1170 at eight
+// frames.  The bound holds at any hop, but the longer the span the less of it each frame holds: the pass over it costs a
+// loud chunk more and certifies fewer quiet ones (from hop = n_fft on it reads the gaps between the frames as well).
+constexpr int64_t SPAN5_MAX = 2 * (2 * M4);
 
 // One workgroup transforms kfr CONSECUTIVE frames of one segment, one after the other.  Everything that does not depend on
 // the frame is done once, before the frame loop: the XCD remap and (segment, chunk) decode, the segment's job values (as
@@ -92,8 +123,9 @@ struct __attribute__((aligned(8))) dpair5 { double a, b; };
 // the frame's twiddle factors are reloaded per frame (they hit the caches), the frame alone needs 122 of the 128 VGPRs.
 // The loop body is the frame as described at the top of the file, barrier for barrier, behind one more barrier at which
 // the waves agree whether the frame is quiet; its trip count and that decision are workgroup-uniform, so every wave of
-// the workgroup meets the same barriers.  The results do not depend on kfr: a frame's arithmetic reads nothing of its
-// neighbours.
+// the workgroup meets the same barriers.  Before the loop the workgroup tests its whole chunk once ("quiet chunk?"): where
+// that certifies all of its frames there is no loop.  The results do not depend on kfr: a frame's arithmetic reads nothing
+// of its neighbours, and a frame the chunk test certifies gets the bytes its own arithmetic would have produced.
 __global__ __launch_bounds__(TL5) __attribute__((amdgpu_waves_per_eu(4, 4))) void stft5_kernel(
     const float* __restrict__ x, const int64_t* __restrict__ off, const int32_t* __restrict__ nframes, int hop,
     const double* __restrict__ window, const cdd* __restrict__ tw, double floor_lin, float floor_db,
@@ -101,9 +133,14 @@ __global__ __launch_bounds__(TL5) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     const int64_t* __restrict__ sel_off, int lb_nbins, int lb_kbase, const int32_t* __restrict__ lb_first,
     const int32_t* __restrict__ lb_count, int kfr, int ablate) {
   // ablate (IRA_STFT5_ABLATE, tuning build, timing only): 1 no window loads, 2 no sample loads, 4 no dB -> linear conversion;
-  // 256 (results unchanged: tests and A/B) every frame takes the full path, the quiet-frame shortcut is off
+  // results unchanged (tests and A/B): 256 every frame takes the full path -- the quiet-frame rule, the chunk test and the
+  // quiet table are all off; 512 the chunk test alone is off; 1024 the quiet table alone is off (a quiet frame fills the
+  // exchange buffer with the floored value and sums it like a loud one)
   __shared__ __attribute__((aligned(16))) cdd ex[EXC4];
   __shared__ double wave_energy[2][TL5 / 64];      // per-wave sums of (xw)^2, one slot per frame parity
+  __shared__ double chunk_energy[TL5 / 64];        // per-wave sums of x^2 over the chunk's span (written once, before the loop)
+  __shared__ unsigned long long chunk_wmax[TL5 / 64];   // per-wave max of w^2, as bit patterns
+  __shared__ float quiet_val[TL5];                 // log bin q of a floored frame, kept by lane q for lane q (no barrier)
   __shared__ ira::LogTabEntry ltab[ira::LOGTAB_N];
   __shared__ int lb_range[2];
   __shared__ int frame_bad;
@@ -149,6 +186,98 @@ __global__ __launch_bounds__(TL5) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     k_hi = ira::uniform(lb_range[1]);
     floor_lin32 = ira::uniform(exp10((double)floor_db * 0.05));
   }
+  // Log bin bb of a frame that is floored on every row: what the sums at the loop's tail make of the floored linear value
+  // (the same additions, see logbin_mean_db), or the NaN of an empty bin.
+  auto quiet_bin = [&](int bb, double fl) -> float {
+    const int c = lb_count[bb];
+    return c > 0 ? logbin_mean_db<true>(nullptr, fl, c, ltab) : qnan32;
+  };
+
+  // ---- quiet chunk? ------------------------------------------------------------------------------------------------
+  // Without a frame selection the chunk's frames are consecutive and read the samples [col0 hop, (col1 - 1) hop + N) of the
+  // segment and nothing else.  For each of them sum (x w)^2 <= max(w^2) sum x^2 <= wmax2 S, S the sum of x^2 over that
+  // span, so 4 N wmax2 S <= floor^2 puts every frame of the chunk under the per-frame rule of the loop below ("quiet
+  // frame?"; the float64 rounding of S, ~1e-13 relative, disappears in that rule's factor 4).  Their output is known: the
+  // floor on every row, or the floored value's log-bin means.  The pass reads exactly the span -- the last segment of a batch
+  // may end where the buffer ends -- in 16-byte pieces that are 4-byte aligned, like the frames' own pairs.
+  // wmax2 is the maximum over the window table this call was given (a table scaled above 1 must not certify more), and only
+  // chunks whose S passes a 16 times wider pre-test pay for it: a loud chunk pays the pass over the span, one reduction and
+  // one barrier.  A NaN or an infinity in the span makes S non-finite and both comparisons false; the chunk then takes the
+  // frame loop, which finds the frames that hold it.  The maximum is taken over the bit patterns of |w^2|, which order like
+  // the values and put every NaN above infinity: a NaN in the table comes out as a NaN and certifies nothing either.
+  // Every branch here is workgroup-uniform (launch arguments, values read back through ira::uniform from LDS that all lanes
+  // read alike), so all four waves meet the same barriers; a certified chunk leaves behind its last one.
+  // The decision may differ from K to K, the bytes do not: a certified frame gets what the loop would have given it.
+  if (!IRA_ABL(ablate & (256 | 512)) && fsel == nullptr && (int64_t)(col1 - col0 - 1) * hop + 2 * M4 <= SPAN5_MAX) {
+    const int nfr = col1 - col0;
+    const int span = (nfr - 1) * hop + 2 * M4;
+    const float* cx = xs + (int64_t)col0 * hop;
+    const int n4 = span >> 2;
+    double s = 0.0;
+    for (int i0 = 0; i0 < n4; i0 += 4 * TL5) {
+      fquad5 p[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int i = i0 + u * TL5 + q;
+        p[u] = i < n4 ? *reinterpret_cast<const fquad5*>(cx + 4 * i) : fquad5{0.0f, 0.0f, 0.0f, 0.0f};
+      }
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        s = fma((double)p[u].x, (double)p[u].x, s);
+        s = fma((double)p[u].y, (double)p[u].y, s);
+        s = fma((double)p[u].z, (double)p[u].z, s);
+        s = fma((double)p[u].w, (double)p[u].w, s);
+      }
+    }
+    if (q < (span & 3)) {                          // the span's last one to three samples
+      const double t = (double)cx[4 * n4 + q];
+      s = fma(t, t, s);
+    }
+    {
+      const double wsum = ira::wave_sum(s);
+      if ((q & 63) == 0) chunk_energy[q >> 6] = wsum;
+    }
+    __syncthreads();
+    const double scaled = ira::uniform((chunk_energy[0] + chunk_energy[1]) + (chunk_energy[2] + chunk_energy[3])) * (4.0 * (2 * M4));
+    if (scaled <= 16.0 * floor_pow) {
+      unsigned long long wb = 0;
+#pragma unroll
+      for (int j = 0; j < 2 * M4 / (2 * TL5); ++j) {
+        const dpair5 w = *reinterpret_cast<const dpair5*>(window + 2 * (j * TL5 + q));
+        const unsigned long long ba = (unsigned long long)__double_as_longlong(w.a * w.a) & 0x7fffffffffffffffull;
+        const unsigned long long bb = (unsigned long long)__double_as_longlong(w.b * w.b) & 0x7fffffffffffffffull;
+        wb = ba > wb ? ba : wb;
+        wb = bb > wb ? bb : wb;
+      }
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) {
+        const unsigned long long other = __shfl_xor(wb, o, 64);
+        wb = other > wb ? other : wb;
+      }
+      if ((q & 63) == 0) chunk_wmax[q >> 6] = wb;
+      __syncthreads();
+      unsigned long long wm = chunk_wmax[0];
+#pragma unroll
+      for (int i = 1; i < TL5 / 64; ++i) wm = chunk_wmax[i] > wm ? chunk_wmax[i] : wm;
+      const double wmax2 = ira::uniform(__longlong_as_double((long long)wm));
+      if (scaled * wmax2 <= floor_pow) {
+        if (lb_nbins <= 0) {
+          // dB mode: the chunk's frames are one run of nfr * 4097 floats of the frame-major matrix
+          float* fo = os + (int64_t)col0 * F4;
+          for (int i = q; i < nfr * F4; i += TL5) fo[i] = floor_db;
+        } else {
+          // log-bin mode: lane bb writes its bin's run of nfr consecutive frames
+          for (int bb = q; bb < lb_nbins; bb += TL5) {
+            const float val = quiet_bin(bb, floor_lin32);
+            float* o = os + (int64_t)bb * T_out + col0;
+            for (int j = 0; j < nfr; ++j) o[j] = val;
+          }
+        }
+        return;
+      }
+    }
+  }
+  bool quiet_built = false;                        // workgroup-uniform: quiet_val holds this workgroup's table
 
   for (int col = col0; col < col1; ++col) {
     // The lane index passes through an empty asm statement in every frame, so that the compiler derives the lane's
@@ -200,7 +329,7 @@ __global__ __launch_bounds__(TL5) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     // the sum non-finite and the comparison false: such a frame takes the full path and its bad_frame handling.
     // The waves' sums meet in wave_energy[frame parity]; every lane reads back the same four doubles and adds them in the
     // same order, so the decision is the same in all four waves and they meet the same barriers.  Two slots because the
-    // dB-mode quiet path has no barrier behind it: a fast wave writes the NEXT frame's slot while a slow one still reads
+    // quiet path (either mode) has no barrier behind it: a fast wave writes the NEXT frame's slot while a slow one still reads
     // this one's.  The barrier below orders a slot's writes before its reads in this frame, and its reads in this frame
     // before its next writes two frames on (the next frame's barrier lies between them).
     double* we = wave_energy[col & 1];
@@ -226,12 +355,26 @@ __global__ __launch_bounds__(TL5) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
         if (q == 0) fo[M4 / 2] = floor_db;
         continue;
       }
-      // log-bin mode: the slots the post step fills, with the value lin_of4 gives a floored row; then the aggregation
-      // below, the code that sums a loud frame's rows.  (The previous frame's sums have read exd before its tail barrier.)
+      // log-bin mode.  Every row of the frame holds the value lin_of4 gives a floored row, so log bin bb is a function of
+      // lb_count[bb] alone: the workgroup's first quiet frame works it out (quiet_bin: the additions of the sums at the
+      // loop's tail, over the constant) and lane q keeps bin q in quiet_val[q]; every later quiet frame stores from there.
+      // No barrier: a slot of quiet_val is written and read by the same lane, in program order, and no other.  No LDS
+      // access to the exchange buffer, so no barrier at the tail either, as in dB mode: what the previous loud frame's
+      // sums read of it is fenced by that frame's own tail barrier, and wave_energy by its two slots (above).  Bins from
+      // TL5 on (no caller has more than 240) are worked out frame by frame.
       // The value passes through an empty asm statement as a scalar: taken as a vector register pair it is held across
-      // the frame loop for these stores alone, and the loud frame has no pair to spare (the pair was spilled to scratch).
+      // the frame loop for this path alone, and the loud frame has no pair to spare (the pair was spilled to scratch).
       double fl = floor_lin32;
       asm volatile("" : "+s"(fl));
+      if (!IRA_ABL(ablate & 1024)) {
+        if (!quiet_built) {
+          if (q < lb_nbins) quiet_val[q] = quiet_bin(q, fl);
+          quiet_built = true;
+        }
+        for (int bb = q; bb < lb_nbins; bb += TL5) os[(int64_t)bb * T_out + col] = bb < TL5 ? quiet_val[bb] : quiet_bin(bb, fl);
+        continue;
+      }
+      // tuning build, bit 1024: the slots the post step fills, with the floored value; then the sums at the loop's tail
 #pragma unroll
       for (int i = 0; i < 8; ++i) {
         const int k = q + TL5 * i;
@@ -366,21 +509,7 @@ __global__ __launch_bounds__(TL5) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     for (int bb = q; bb < lb_nbins; bb += TL5) {
       const int c = lb_count[bb];
       float val = qnan32;
-      if (c > 0) {
-        const double* r = exd + lb_kbase + lb_first[bb];
-        double acc = r[0];
-        for (int k0 = 1; k0 < c; k0 += 8) {
-          double v8[8];
-#pragma unroll
-          for (int u = 0; u < 8; ++u) v8[u] = (k0 + u < c) ? r[k0 + u] : 0.0;
-#pragma unroll
-          for (int u = 0; u < 8; ++u)
-            if (k0 + u < c) acc += v8[u];
-        }
-        // 20 log10 m through the table log2 (series to r^6: a few 1e-16 relative, invisible after the float32 rounding) --
-        // the library log10 was ~130 of the ~1800 instructions of every wave although only 240 lanes of a frame use it
-        val = (float)(6.0205999132796239 * ira::log2_table<6>(fmax(acc / (double)c, 1e-30), ltab));
-      }
+      if (c > 0) val = logbin_mean_db<false>(exd + lb_kbase + lb_first[bb], 0.0, c, ltab);
       os[(int64_t)bb * T_out + col] = (bad_frame && c > 0) ? qnan32 : val;
     }
     __syncthreads();                               // the sums have read the buffer the next frame's E1 (or quiet path) writes
