@@ -97,6 +97,8 @@ PROTOTYPES = {
     "ira_echo_scratch_doubles": (C.c_int64, [i32, C.c_int64]),
     "ira_echo_criterion": (i32, [vp, vp, vp, vp, vp, vp, i32, C.c_int64, C.POINTER(f64), i32, C.c_int64, vp, vp, vp, vp, vp]),
     "ira_echo_density": (i32, [vp, vp, vp, vp, i32, vp, i32, i32, C.c_int64, C.POINTER(f64), i32, vp, vp, vp, vp]),
+    "ira_reflections": (i32, [vp, vp, vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, C.c_int64, f64, f64, i32, C.c_int64, vp, vp,
+                              vp, C.c_int64, vp, vp, vp]),
     "ira_xspec_accumulate": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp]),
     "ira_xspec_finish": (i32, [vp, vp, i32, i32, i32, i32, vp, vp]),
 }

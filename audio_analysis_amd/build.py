@@ -58,6 +58,8 @@ SOURCES = {
     "ira_echo.hip": ["-ffp-contract=off"],
     # float64 window sums w h2 and the comparison h2 A > B round one operation at a time, like the restatement's
     "ira_echodensity.hip": ["-ffp-contract=off"],
+    # float64 envelope and background sums round one operation at a time: compared bit for bit with the NumPy restatement
+    "ira_reflections.hip": ["-ffp-contract=off"],
     # cross-spectral sums are compared to a derived bound only (FMAs wanted in the transform); the finish kernel, whose
     # quotients are held to a few ulp, turns contraction off for itself
     "ira_xspec.hip": [],

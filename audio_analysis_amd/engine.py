@@ -59,6 +59,15 @@ NED_MAX_THRESHOLDS = 3        # IRA_NED_MAX_THRESHOLDS
 NED_NAN_SILENT = 0x7fc00000   # IRA_NED_NAN_SILENT: the profile's NaN where the window holds digital silence (B == 0)
 NED_NAN_NONFINITE = 0x7fc00001  # IRA_NED_NAN_NONFINITE: the profile's NaN where B is not finite
 NED_SLOTS = 5120              # float64 squares a workgroup stages (NED_SLOTS of ira_echodensity.hip)
+REFL_DOUBLES = 8              # IRA_REFL_DOUBLES
+REFL_FIELDS = 6               # IRA_REFL_FIELDS
+REFL_TILE = 1024              # IRA_REFL_TILE: row entries a workgroup of ira_reflections takes
+REFL_MAX_HALF = 512           # IRA_REFL_MAX_HALF: the largest half smoothing window (W = 2 d + 1 <= 1025)
+REFL_MAX_DIRECT = 1024        # IRA_REFL_MAX_DIRECT
+REFL_MAX_BG = 2048            # IRA_REFL_MAX_BG
+REFL_MAX_KEEP = 64            # IRA_REFL_MAX_KEEP
+REFL_MAX_SEP = 1024           # the largest separation S
+REFL_UNBOUNDED = 1 << 40      # a Tn from here on is no bound (REFL_UNBOUNDED of ira_reflections.hip)
 XSPEC_FRAMES = 16             # IRA_XSPEC_FRAMES: frames a workgroup of ira_xspec_accumulate sums before it writes
 XSPEC_ROWS = 11               # IRA_XSPEC_ROWS
 XSPEC_MIN_FFT, XSPEC_MAX_FFT = 256, 8192
@@ -89,6 +98,27 @@ def ned_tile_positions(delta: int, step: int) -> int:
         if t >= 1:
             return t
     return min(NED_TILE, (NED_SLOTS - w) // s + 1)
+
+
+def refl_row_room(length, direct: int, tn: int, background: int) -> np.ndarray:
+    """Entries of a channel's energy-time row as the host sizes it, for onset 0: min(L, Rmax), Rmax = D + Tn + B, L for
+    an unbounded Tn (int64, elementwise)."""
+    length = np.clip(np.asarray(length, dtype=np.int64), 0, None)
+    if int(tn) >= REFL_UNBOUNDED:
+        return length.copy()
+    return np.minimum(length, int(direct) + int(tn) + int(background)).astype(np.int64)
+
+
+def refl_tile_candidates(separation: int) -> int:
+    """Candidates a tile of REFL_TILE row entries can hold: two candidates lie more than S entries apart, so
+    ceil(REFL_TILE / (S + 1)) (ira_reflections.hip restated)."""
+    return (REFL_TILE + int(separation)) // (int(separation) + 1)
+
+
+def refl_scratch_doubles(nch: int, max_room: int, separation: int) -> int:
+    """Doubles of scratch ira_reflections needs: per channel and tile of the longest row a count and 4 doubles per
+    candidate the tile can hold (the geometry of ira_reflections.hip restated; the call checks it)."""
+    return int(nch) * (-(-int(max_room) // REFL_TILE)) * (1 + 4 * refl_tile_candidates(separation))
 
 
 def lundeby_layout(base_off, base_len, chan_of_seg, blk_size, nblk, first_m) -> Dict[str, object]:
@@ -789,6 +819,66 @@ class Engine:
                                         kmax, _lib.dbl_array(thresholds), len(thresholds), _ptr(prof), _ptr(d_poff),
                                         _ptr(rec), self.stream), "ira_echo_density")
         return prof[:total], prof_off, rec[: nch * NED_DOUBLES].view(nch, NED_DOUBLES)
+
+    # ------------------------------------------------------------------ early reflections
+    def reflections(self, x_dev, off: np.ndarray, length: np.ndarray, onset_dev, weights: np.ndarray, half: int,
+                    direct: int, direct_window: int, guard: int, separation: int, background: int, tn: int, rel: float,
+                    prom: float, keep: int):
+        """Energy-time rows, kept reflections and records (ira_reflections, one call).  Channel c: length[c] samples at
+        off[c] of x_dev, the row starts at onset_dev[c] (int64 device, read on the device); weights: the 2 half + 1 float64
+        smoothing weights; direct, direct_window, guard, separation, background: D, Dw, G, S, B in samples; tn: Tn in
+        samples (REFL_UNBOUNDED and more: no bound); rel, prom: the level and prominence factors; keep: reflections kept.
+        Returns (erow float64 device, flat; erow_off int64 host (nch,): row c starts at erow_off[c] and holds
+        refl_row_room(length[c], ..) values -- the onset is not known on the host -- of which the first R are e[o + j]
+        and the rest NaN; list (nch, keep, REFL_FIELDS) float64 device: n, e[n], Bsum, cnt, peak index, peak sample of
+        the kept reflections in time order (-1 / NaN rows behind them); rec (nch, REFL_DOUBLES) float64 device: n0, Ed,
+        M, kept, first candidate (-1), the direct and the remaining energy, non-finite row entries)."""
+        t = self.torch
+        off = np.ascontiguousarray(off, dtype=np.int64).reshape(-1)
+        length = np.ascontiguousarray(length, dtype=np.int64).reshape(-1)
+        weights = np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
+        half, direct, direct_window, guard = int(half), int(direct), int(direct_window), int(guard)
+        separation, background, tn, keep = int(separation), int(background), int(tn), int(keep)
+        nch = int(off.size)
+        if length.size != nch:
+            raise ValueError("off and length must be (nch,)")
+        if not 1 <= half <= REFL_MAX_HALF:
+            raise ValueError(f"half must be 1..{REFL_MAX_HALF} samples, got {half}")
+        if weights.size != 2 * half + 1 or not (np.all(np.isfinite(weights)) and np.all(weights > 0.0)):
+            raise ValueError("weights must be 2 * half + 1 finite values > 0")
+        if not 1 <= direct <= REFL_MAX_DIRECT:
+            raise ValueError(f"direct must be 1..{REFL_MAX_DIRECT} samples, got {direct}")
+        if not 1 <= direct_window < 1 << 31:
+            raise ValueError(f"direct_window must be >= 1 sample, got {direct_window}")
+        if not 1 <= separation <= REFL_MAX_SEP:
+            raise ValueError(f"separation must be 1..{REFL_MAX_SEP} samples, got {separation}")
+        if not separation <= guard < 1 << 31:
+            raise ValueError(f"guard must be at least the separation ({separation} samples), got {guard}")
+        if not separation < background <= REFL_MAX_BG:
+            raise ValueError(f"background must be more than the separation and at most {REFL_MAX_BG} samples, got {background}")
+        if tn < 0:
+            raise ValueError("tn must be >= 0")
+        if not (math.isfinite(rel) and rel >= 0.0 and math.isfinite(prom) and prom >= 1.0):
+            raise ValueError("rel must be finite and >= 0, prom finite and >= 1")
+        if not 1 <= keep <= REFL_MAX_KEEP:
+            raise ValueError(f"keep must be 1..{REFL_MAX_KEEP}, got {keep}")
+        tn = min(tn, REFL_UNBOUNDED)
+        room = refl_row_room(length, direct, tn, background)
+        erow_off = exclusive_cumsum(room)
+        total, max_room = int(room.sum()), int(room.max()) if nch else 0
+        scratch_doubles = refl_scratch_doubles(nch, max_room, separation)
+        erow = self.empty(total, t.float64)
+        scratch = self.empty(scratch_doubles, t.float64)
+        lst = self.empty(nch * keep * REFL_FIELDS, t.float64)
+        rec = self.empty(nch * REFL_DOUBLES, t.float64)
+        d_off, d_len, d_eoff = self.job_tables(off, length, erow_off)
+        d_w = self.to_dev(weights)
+        check(self.lib.ira_reflections(_ptr(x_dev), _ptr(d_off), _ptr(d_len), _ptr(onset_dev), nch, _ptr(d_w), half, direct,
+                                       direct_window, guard, separation, background, tn, float(rel), float(prom), keep,
+                                       max_room, _ptr(erow), _ptr(d_eoff), _ptr(scratch), scratch_doubles, _ptr(lst),
+                                       _ptr(rec), self.stream), "ira_reflections")
+        return (erow[:total], erow_off, lst[: nch * keep * REFL_FIELDS].view(nch, keep, REFL_FIELDS),
+                rec[: nch * REFL_DOUBLES].view(nch, REFL_DOUBLES))
 
     # ------------------------------------------------------------------ dual-channel spectral sums (Welch H1 / H2)
     def cross_spectra(self, x_dev, x_off: np.ndarray, y_off: np.ndarray, n: np.ndarray, n_fft: int, hop: int,

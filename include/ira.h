@@ -852,6 +852,46 @@ int32_t ira_echo_density(const float* x_dev, const int64_t* off_dev, const int64
                          const double* thresholds, int32_t nthr, float* prof_dev, const int64_t* prof_off_dev,
                          double* rec_dev, void* stream);
 
+/* ---- Early reflections: the energy-time curve from the onset, its outstanding local maxima, ITDG and DRR sums ----------
+ * Nothing in the reference computes it; the entry point replaces no reference function.  Host side, with the definition
+ * pinned: audio_analysis_amd/analyse/reflections.py (`python -m analyse.reflections`).
+ * ira_reflections: channel c is len_dev[c] float32 samples at x_dev + off_dev[c]; o = max(onset_dev[c], 0) is read on the
+ *   device.  w_dev: W = 2 d + 1 float64 weights (> 0), built on the host.  h2[i] = float64(x[i])^2, 0 outside the channel;
+ *   e[n] = sum_k w[k] h2[n - d + k] from 0.0 with k ascending, one rounding per multiply and per add.
+ *   erow_dev[erow_off_dev[c] + j] = e[o + j], j < R = min(len - o, Rmax), Rmax = D + Tn + B (Tn >= 2^40: no bound).  Row c
+ *     must hold the R of onset 0 (min(len, Rmax)) doubles: the onset never returns to the host to size it; entries from R
+ *     on are NaN.  max_room is the longest row of the batch; it sizes the grids and the scratch, no value depends on it.
+ *   n0 = the first index of the maximum of e over [o, min(len, o + D)) (a NaN never wins), Ed = e[n0].  A candidate is an
+ *     n in [n0 + G, min(len, n0 + Tn + 1)) with  e[n] > e[m] for m in [n - S, n);  e[n] >= e[m] for m in (n, min(n + S,
+ *     len - 1)];  e[n] >= Ed rel;  e[n] cnt >= prom Bsum, Bsum the sum of e[m] over [max(n - B, n0 + G), n - S) and then
+ *     (n + S, min(n + B, len - 1)], added one at a time with m ascending from 0.0, cnt its number of terms (cnt = 0 or
+ *     Bsum = 0 passes).  Of the M candidates the min(M, keep) of largest e are kept (the earlier on equal e).
+ *   list_dev[(c * keep + i) * IRA_REFL_FIELDS + ..], the kept in ascending time: [0] n  [1] e[n]  [2] Bsum  [3] cnt
+ *     [4] m = the first index of max |x| over [max(n - d, 0), min(n + d, len - 1)]  [5] x[m]; unused rows hold -1 in [0],
+ *     [3], [4] and NaN in the others.
+ *   rec_dev[c * IRA_REFL_DOUBLES + ..]: [0] n0  [1] Ed  [2] M  [3] the number kept  [4] the first candidate in time (-1:
+ *     none)  [5] sum of h2 over [max(n0 - Dw, 0), min(n0 + Dw, len - 1)]  [6] sum of h2 over (n0 + Dw, len)  [7] the
+ *     non-finite values among the R row entries.  len <= o: n0 = o, Ed = NaN, zeros and -1.
+ *   scratch_dev: nch * ceil(max_room / IRA_REFL_TILE) * (1 + 4 * ceil(IRA_REFL_TILE / (S + 1))) doubles (a count and the
+ *     candidates of every tile), checked against scratch_doubles.
+ *   Checked before anything is launched (IRA_E_NULL / IRA_E_SIZE): d 1..IRA_REFL_MAX_HALF, D 1..IRA_REFL_MAX_DIRECT,
+ *   Dw >= 1, 1 <= S <= 1024, G >= S, S < B <= IRA_REFL_MAX_BG, Tn >= 0, rel >= 0 and prom >= 1 finite, keep
+ *   1..IRA_REFL_MAX_KEEP, nch 0..65535, max_room 0..Rmax.  nch = 0: IRA_OK, no launch.
+ *   Four launches (envelope, direct sound, candidates, selection), no atomics; every sum runs in one fixed order that
+ *   depends on the channel alone: a channel's outputs are bit-identical whatever the batch or the channel's place in it. */
+#define IRA_REFL_DOUBLES 8
+#define IRA_REFL_FIELDS 6
+#define IRA_REFL_TILE 1024         /* row entries a workgroup of the envelope and candidate launches takes */
+#define IRA_REFL_MAX_HALF 512      /* W <= 1025 */
+#define IRA_REFL_MAX_DIRECT 1024
+#define IRA_REFL_MAX_BG 2048
+#define IRA_REFL_MAX_KEEP 64
+int32_t ira_reflections(const float* x_dev, const int64_t* off_dev, const int64_t* len_dev, const int64_t* onset_dev,
+                        int32_t nch, const double* w_dev, int32_t d, int32_t D, int32_t Dw, int32_t G, int32_t S,
+                        int32_t B, int64_t Tn, double rel, double prom, int32_t keep, int64_t max_room,
+                        double* erow_dev, const int64_t* erow_off_dev, double* scratch_dev, int64_t scratch_doubles,
+                        double* list_dev, double* rec_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
