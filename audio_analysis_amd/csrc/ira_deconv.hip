@@ -82,29 +82,32 @@ __global__ __launch_bounds__(FIN_THREADS) void deconv_mean_kernel(const float* _
   }
 }
 
-// h -= mean (optional), and the file's peak |h| (max is order independent)
+// h -= mean (optional), and the file's peak |h| (max is order independent).  The peak is numpy.max(numpy.abs(.)): a NaN
+// sample makes it NaN.  It is taken over the bit patterns of |h|, which order like the values and put every NaN above
+// infinity; a NaN goes out as the canonical quiet one, which still wins the unsigned atomicMax against every other file peak.
 __global__ __launch_bounds__(DV_THREADS) void deconv_center_kernel(float* __restrict__ h, const int64_t* __restrict__ hoff,
                                                                    const int32_t* __restrict__ n_out,
                                                                    const int32_t* __restrict__ group,
                                                                    const float* __restrict__ mean,
                                                                    unsigned* __restrict__ peak_bits) {
-  __shared__ float part[DV_THREADS / IRA_WAVE];
+  __shared__ unsigned part[DV_THREADS / IRA_WAVE];
   const int e = blockIdx.y;
   const int n = n_out[e];
   float* p = h + hoff[e];
   const float mu = mean ? mean[e] : 0.0f;
-  float m = 0.0f;
+  unsigned m = 0u;
   for (long long i = (long long)blockIdx.x * DV_THREADS + threadIdx.x; i < n; i += (long long)gridDim.x * DV_THREADS) {
     float v = p[i];
     if (mean) { v = v - mu; p[i] = v; }
-    m = fmaxf(m, fabsf(v));
+    const unsigned a = __float_as_uint(v) & 0x7fffffffu;
+    m = a > m ? a : m;
   }
-  m = ira::wave_max(m);
+  m = ira::wave_max_int(m);
   if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = m;
   __syncthreads();
   if (threadIdx.x == 0) {
-    for (int w = 1; w < DV_THREADS / IRA_WAVE; ++w) m = fmaxf(m, part[w]);
-    atomicMax(peak_bits + group[e], __float_as_uint(m));
+    for (int w = 1; w < DV_THREADS / IRA_WAVE; ++w) m = part[w] > m ? part[w] : m;
+    atomicMax(peak_bits + group[e], m > 0x7f800000u ? 0x7fc00000u : m);
   }
 }
 
@@ -115,7 +118,7 @@ __global__ __launch_bounds__(DV_THREADS) void deconv_scale_kernel(float* __restr
   const int e = blockIdx.y;
   const int n = n_out[e];
   const double peak = (double)__uint_as_float(peak_bits[group[e]]);
-  if (!(peak > 0.0)) return;                                   // all-zero response: left as it is (deconvolve.py:103-104)
+  if (peak <= 0.0) return;               // all-zero response: left as it is; a NaN peak scales by NaN (deconvolve.py:103-106)
   const float scale = (float)(target / peak);                  // Python float scalar * float32 array -> float32 multiply
   float* p = h + hoff[e];
   for (long long i = (long long)blockIdx.x * DV_THREADS + threadIdx.x; i < n; i += (long long)gridDim.x * DV_THREADS)

@@ -3,6 +3,7 @@
 #include <cmath>
 
 #include "ira_common.h"
+#include "ira_reduce.h"
 
 namespace {
 
@@ -81,7 +82,8 @@ __global__ __launch_bounds__(WF_THREADS) void waterfall_kernel(const float* __re
 
 // ---- a15: modal cloud log-bin aggregation.  in: STFT dB matrix (F, T); for log bin b the rows
 //      k_base + first[b] .. + count[b] - 1 are averaged in LINEAR magnitude (10^(dB/20), float64, rows added in
-//      order like numpy's axis-0 mean), then 20 log10(max(., 1e-30)) -> float32; empty bin -> NaN.
+//      order like numpy's axis-0 mean), then 20 log10(max(., 1e-30)) -> float32; empty bin -> NaN.  The max is
+//      numpy.maximum: a NaN mean (a NaN row in the frame) stays NaN, it is not clamped to -600 dB.
 //      Reference analyse/modalcloud.py:176-207.
 __global__ void logbin_kernel(const float* __restrict__ mag, const int64_t* __restrict__ mag_off,
                               const int32_t* __restrict__ nfr, int k_base, const int32_t* __restrict__ first,
@@ -106,8 +108,7 @@ __global__ void logbin_kernel(const float* __restrict__ mag, const int64_t* __re
     const double lin = exp10(db * 0.05);           // 10^(dB/20); pow() costs 4.5x the instructions for the same f32 result
     acc = (k == 0) ? lin : acc + lin;
   }
-  double mean = acc / (double)c;
-  mean = fmax(mean, 1e-30);
+  const double mean = ira::np_max(acc / (double)c, 1e-30);
   o[t] = (float)(20.0 * log10(mean));
 }
 
@@ -146,7 +147,7 @@ __global__ __launch_bounds__(LBT_THREADS) void logbin_tf_kernel(
         for (int u = 0; u < 8; ++u)
           if (k0 + u < c) acc += v8[u];
       }
-      const double mean = fmax(acc / (double)c, 1e-30);
+      const double mean = ira::np_max(acc / (double)c, 1e-30);
       v = (float)(20.0 * log10(mean));
     }
     o[(int64_t)b * T + t] = v;

@@ -60,6 +60,15 @@ __device__ __forceinline__ T wave_min(T v) {                  // integers
   }
   return v;
 }
+template <typename T>
+__device__ __forceinline__ T wave_max_int(T v) {              // integers (and bit patterns ordered as such)
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const T other = __shfl_xor(v, o, 64);
+    v = other > v ? other : v;
+  }
+  return v;
+}
 __device__ __forceinline__ double wave_max(double v) {        // fmax: a NaN is dropped
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));

@@ -297,7 +297,8 @@ int32_t ira_waterfall_rel(const float* mag_dev, const int64_t* mag_off_dev, cons
 /* ---- a15: modal-cloud log-frequency aggregation -----------------------------------------------------------
  * mag[e] is the (F, T_e) STFT dB matrix; for log bin b rows k_base+first[b] .. +count[b]-1 are averaged as
  * linear magnitude 10^(dB/20) in float64 (rows added in order), then 20 log10(max(mean, 1e-30)) -> float32;
- * count[b] == 0 gives a NaN row.  out[e] is (nbins, T_e).  frame_major_rows > 0: mag[e] is the FRAME-MAJOR (T_e, F)
+ * count[b] == 0 gives a NaN row; a NaN among a frame's rows of a bin stays NaN (numpy.maximum), it is not clamped.
+ * out[e] is (nbins, T_e).  frame_major_rows > 0: mag[e] is the FRAME-MAJOR (T_e, F)
  * matrix of ira_stft_mag_db_tf with F = frame_major_rows <= 8193 (same results, same row order).
  * Replaces _aggregate_to_log_bins, reference analyse/modalcloud.py:176-207. */
 int32_t ira_logbin_aggregate(const float* mag_dev, const int64_t* mag_off_dev, const int32_t* nframes_dev,
@@ -548,7 +549,8 @@ int32_t ira_host_pull(const void* host_src, int64_t count, int32_t format, float
  *   (deconvolve.py:150-166).  pmax_dev: nb doubles of scratch (receives max |X|^2 per element).
  * ira_deconv_finish: element e is one channel of length n_out[e] at h_dev + h_off[e], group[e] < ngroups its FILE:
  *   remove_dc: h -= float32(mean(h)) per channel; normalise_peak: every channel of a file is multiplied by
- *   float32(target_peak / max |h| over the file) unless that peak is 0 (deconvolve.py:176-189, :100-106).  mean_dev: nb
+ *   float32(target_peak / max |h| over the file) unless that peak is 0; the peak is numpy.max(numpy.abs(.)), so a NaN
+ *   sample in any channel of a file makes every sample of the file NaN (deconvolve.py:176-189, :100-106).  mean_dev: nb
  *   floats, peak_bits_dev: ngroups uint32 of scratch. */
 int32_t ira_deconv_divide(double* yspec_dev, const int64_t* yspec_off_dev, const double* xspec_dev,
                           const int64_t* xspec_off_dev, const int32_t* nfft_dev, int32_t nb, int32_t max_nfft,

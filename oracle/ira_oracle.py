@@ -1121,6 +1121,6 @@ def deconvolve(recorded: np.ndarray, sweep: np.ndarray, regularization_relative:
     ir = np.stack(chans, axis=1).astype(np.float32)
     if normalise_peak:
         peak = float(np.max(np.abs(ir))) if ir.size else 0.0
-        if peak > 0.0:
+        if not peak <= 0.0:                     # deconvolve.py:104: only a peak <= 0 is left unscaled, a NaN peak scales by NaN
             ir = (ir * (float(target_peak) / peak)).astype(np.float32)
     return ir

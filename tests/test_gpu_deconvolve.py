@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 from scipy.io import wavfile
 
+import deconv_ref
 from oracle import ira_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -118,6 +119,30 @@ def test_batched_device_path_recovers_known_responses_at_full_size():
         # a few samples may differ between batch compositions, nothing more
         _close(one["h"].cpu().numpy()[:600000], got, "alone vs in a batch")
     _close(host[:600000].reshape(-1, 1), O.deconvolve(recs[0], sweeps[0]), "oracle spot check")
+
+
+@pytest.mark.parametrize("mode,reg", deconv_ref.E2E_SETTINGS)
+def test_one_batch_whose_channels_need_different_transform_sizes(mode, reg):
+    """One deconvolve_device call over two stereo and three mono files of 8 to 5000 samples with sweeps of 8 to 4096
+    (deconv_ref.e2e_files: transforms of 8, 64, 1024, 1024 and 8192 points side by side, sweeps longer and shorter than
+    their recordings), per file against the oracle.  tests/test_deconv_ref_cpu.py shows by direct long-double DFTs that the
+    float64 computation sits within 1e-3 of this tolerance at the two smallest sizes."""
+    from audio_analysis_amd.analyse import deconvolve as D
+    from audio_analysis_amd.engine import get_engine
+    eng = get_engine()
+    files = deconv_ref.e2e_files()
+    chans = [np.ascontiguousarray(rec[:, c]) for rec, _ in files for c in range(rec.shape[1])]
+    file_of = [i for i, (rec, _) in enumerate(files) for _c in range(rec.shape[1])]
+    dev = D.deconvolve_device(eng, eng.upload(chans), file_of, eng.upload([sw for _, sw in files]), file_of, SR,
+                              D.DeconvolveSettings(regularization_relative=reg, output_length_mode=mode))
+    assert list(dev["n_fft"]) == [8, 8, 64, 1024, 1024, 1024, 8192]
+    host = dev["h"].cpu().numpy()
+    for i, (rec, sw) in enumerate(files):
+        mine = [e for e, f in enumerate(file_of) if f == i]
+        ref = O.deconvolve(rec, sw, regularization_relative=reg, output_length_mode=mode)
+        assert [int(dev["n_out"][e]) for e in mine] == [ref.shape[0]] * len(mine)
+        got = np.stack([host[int(dev["off"][e]): int(dev["off"][e]) + ref.shape[0]] for e in mine], axis=1)
+        _close(got, ref, f"file {i} ({rec.shape[0]} samples, sweep {sw.size}) {mode} reg {reg}")
 
 
 def test_input_forms_the_reference_accepts(z):
