@@ -1,7 +1,7 @@
 """
 ISO 3382-1 energy parameters on the device (ira_onset_index + ira_energy_windows, audio_analysis_amd.analyse.energy)
-against a NumPy restatement of the definitions in the module's docstring, written out here; band signals against the
-oracle's float64 filter bank.
+against the long-double restatement of the definitions in the module's docstring (tests/energy_ref.py); band signals
+against the oracle's float64 filter bank.  tests/test_gpu_energy_edges.py holds the same kernels to their chunk edges.
 """
 import json
 import math
@@ -13,6 +13,7 @@ from pathlib import Path
 import numpy as np
 import pytest
 
+from energy_ref import onset as onset_at, params as ref_params, sums as ref_sums
 from oracle import ira_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -22,30 +23,9 @@ SR = 48000
 
 
 # ------------------------------------------------------------------------------------------------ the restatement
+# tests/energy_ref.py (long double; tests/test_energy_ref_cpu.py holds it to a per-sample loop and to closed forms)
 def ref_onset(x, onset_db=-20.0):
-    x = np.asarray(x, dtype=np.float32)
-    e = x.astype(np.float64) ** 2
-    p = int(np.argmax(np.abs(x)))
-    return int(np.flatnonzero(e[: p + 1] >= e[p] * 10.0 ** (onset_db / 10.0))[0])
-
-
-def ref_sums(y, onset, limits):
-    """P_0 .. P_K, S1 of e = float64(y)^2 over y[onset:] (float64, NumPy's own sums)."""
-    s = np.asarray(y, dtype=np.float32)[onset:].astype(np.float64) ** 2
-    edges = [0] + [int(v) for v in limits] + [s.size]
-    parts = [float(np.sum(s[a:b])) if b > a else 0.0 for a, b in zip(edges[:-1], edges[1:])]
-    return np.array(parts + [float(np.sum(np.arange(s.size, dtype=np.float64) * s))])
-
-
-def ref_params(sums, fs, d_index=0):
-    p, s1 = sums[:-1], sums[-1]
-    total = float(np.sum(p))
-    k = p.size - 1
-    c = []
-    for i in range(1, k + 1):
-        early, late = float(np.sum(p[:i])), float(np.sum(p[i:]))
-        c.append(math.inf if late == 0.0 and early > 0.0 else 10.0 * math.log10(early / late))
-    return c, float(np.sum(p[: d_index + 1])) / total, s1 / (fs * total)
+    return onset_at(x, 10.0 ** (onset_db / 10.0))
 
 
 def limits_at(fs, ms=(50.0, 80.0)):

@@ -68,10 +68,12 @@ def sums_errors(dev, ref):
     return out
 
 
-@pytest.mark.parametrize("n_fft", [256, 1024, 8192])
+@pytest.mark.parametrize("n_fft", [256, 512, 1024, 2048, 4096, 8192])
 def test_sums_within_the_derived_bound_and_identical_alone(n_fft):
     """K = 1, C, C + 1, 2C + 1 frames (C frames per chunk) x delays 0, +5, -7 as ONE ragged batch per (hop, window), hop =
-    n_fft, n_fft / 2 and 37, Hann and rectangular; then every pair alone, in a buffer of its own: the same bytes."""
+    n_fft, n_fft / 2 and 37, Hann and rectangular; then every pair alone, in a buffer of its own: the same bytes.  Every
+    transform length from 256 to 8192: the three instantiations of the accumulate kernel (up to 2048, 4096 -- the length the
+    settings and the command line default to -- and 8192) and every remainder of the transform's radix schedule."""
     eng = _eng()
     rng = np.random.default_rng(n_fft)
     worst = 0.0
@@ -96,6 +98,71 @@ def test_sums_within_the_derived_bound_and_identical_alone(n_fft):
                 assert alone[0].tobytes() == dev[p].tobytes(), (n_fft, hop, window, ks[p], d)
             print(f"n_fft {n_fft} hop {hop} {window}: {len(pairs)} pairs, largest error / bound so far {worst:.3e} (bound 1)")
     assert worst > 0.0                                                  # the device did not merely echo the reference
+
+
+@pytest.mark.parametrize("n_fft", [512, 4096])
+def test_reads_stay_inside_the_rows(n_fft):
+    """Rows of EXACTLY n_fft + (K - 1) hop samples, K = 1 and 17, no spare sample, in a hand-built buffer with 1 to 7 NaN
+    samples in front of and behind every row (Engine.upload packs rows back to back, where a read past a row would land in
+    finite neighbour data): one sample read outside a row makes a sum NaN.  Between the others a pair of n_fft - 1 samples:
+    no frame, zero sums and the NaN pattern of a pair without frames."""
+    eng = _eng()
+    rng = np.random.default_rng(100 + n_fft)
+    worst = 0.0
+    for hop in (1, n_fft // 2, n_fft):
+        lens = [n_fft, n_fft - 1, n_fft + 16 * hop]
+        rows = [r for n in lens for r in noise_pair(rng, n)]
+        off, pos = [], 0
+        for i, r in enumerate(rows):
+            pos += 1 + (3 * i + hop) % 7                                # the gap in front of row i
+            off.append(pos)
+            pos += r.size
+        flat = np.full(pos + 7, np.nan, np.float32)
+        for o, r in zip(off, rows):
+            flat[o : o + r.size] = r
+        assert np.count_nonzero(np.isnan(flat)) == flat.size - sum(r.size for r in rows)
+        x_dev = eng.to_dev(flat)
+        for window in ("hann", "rect"):
+            dev = eng.cross_spectra(x_dev, np.array(off[0::2], np.int64), np.array(off[1::2], np.int64),
+                                    np.array(lens, np.int64), n_fft, hop, window == "hann").cpu().numpy()
+            for p, k in ((0, 1), (2, 17)):
+                ref = R.pair_reference(rows[2 * p], rows[2 * p + 1], 0, n_fft, hop, window)
+                assert ref["K"] == k
+                assert np.all(np.isfinite(dev[p, :4])), (n_fft, hop, window, k)
+                errs = sums_errors(dev[p], ref)
+                worst = max(worst, *errs)
+                assert max(errs) <= 1.0, (n_fft, hop, window, k, errs)
+            assert R.pair_reference(rows[2], rows[3], 0, n_fft, hop, window)["K"] == 0
+            assert np.all(dev[1, :4] == 0.0) and np.all(np.isnan(dev[1, 4:10])) and np.all(dev[1, 10] == 0.0)
+            assert np.array_equal(np.isnan(R.derived(dev[1, 0], dev[1, 1], dev[1, 2], dev[1, 3])), np.isnan(dev[1]))
+    print(f"n_fft {n_fft}: rows between NaN, largest error / bound {worst:.3e} (bound 1)")
+    assert worst > 0.0
+
+
+@pytest.mark.parametrize("window", ["rect", "hann"])
+def test_a_channel_silent_in_some_frames_only(window):
+    """The measurement is zero for its first 3 hops, then noise: its first two frames are all zeros (their spectrum is taken
+    as 0 exactly), the later frames of the SAME chunk are not.  The sums stay within the bound, and Syy is the Syy of the
+    pair with the two silent frames cut off the front -- against the reference's, within its bound, not bit for bit: the
+    frames fall into the chunks differently."""
+    eng = _eng()
+    n_fft, hop = 4096, 2048
+    rng = np.random.default_rng(12)
+    x, y = noise_pair(rng, n_fft + 19 * hop)
+    y[: 3 * hop] = 0.0
+    assert not np.any(y[: hop + n_fft]) and np.any(y[2 * hop : 2 * hop + n_fft])
+    cut_x, cut_y = x[2 * hop :], y[2 * hop :]
+    dev = run(eng, [x, y, cut_x, cut_y], [(0, 1, 0), (2, 3, 0)], n_fft, hop, window)
+    ref = R.pair_reference(x, y, 0, n_fft, hop, window)
+    ref_cut = R.pair_reference(cut_x, cut_y, 0, n_fft, hop, window)
+    assert ref["K"] == 20 and ref_cut["K"] == 18 and C == 16
+    errs, errs_cut = sums_errors(dev[0], ref), sums_errors(dev[1], ref_cut)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        r_syy = np.abs(dev[0, 1] - ref_cut["syy"]) / ref_cut["bounds"][1]
+    print(f"{window}: error / bound {max(errs):.3e} (whole), {max(errs_cut):.3e} (cut); Syy of the whole against the cut "
+          f"pair's reference {float(np.max(r_syy)):.3e} (bound 1)")
+    assert max(errs) <= 1.0 and max(errs_cut) <= 1.0
+    assert np.all(ref_cut["bounds"][1] > 0.0) and np.all(r_syy <= 1.0)
 
 
 def test_finish_stage_alone_to_a_few_ulp():
