@@ -38,6 +38,10 @@ PROTOTYPES = {
     "ira_stft_mag_db": (i32, [vp, vp, vp, i32, i32, i32, i32, vp, vp, i32, f64, vp, vp, vp, vp, vp]),
     "ira_stft_logbin": (i32, [vp, vp, vp, i32, i32, i32, i32, vp, vp, i32, f64, i32, vp, vp, i32, vp, vp, vp]),
     "ira_stft_mag_db_tf": (i32, [vp, vp, vp, i32, i32, i32, i32, vp, vp, i32, f64, vp, vp, vp, vp, vp]),
+    "ira_tail_energy": (i32, [vp, vp, vp, vp, i32, i32, vp, vp]),
+    "ira_stft_logbin_tail": (i32, [vp, vp, vp, i32, i32, i32, i32, vp, vp, i32, f64, i32, vp, vp, i32, vp, vp, vp, vp, vp,
+                                   vp]),
+    "ira_stft_mag_db_tf_tail": (i32, [vp, vp, vp, i32, i32, i32, i32, vp, vp, i32, f64, vp, vp, vp, vp, vp, vp, vp, vp]),
     "ira_fft_split": (i32, [i32, vp, vp]),
     "ira_bluestein_filter": (i32, [vp, i32, i32, vp, vp, vp, vp, vp]),
     "ira_rfft_any": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp,

@@ -152,14 +152,17 @@ def modal_cloud_device(eng, batch, sample_rate_hz: int, settings: ModalCloudAnal
     rows_ok = nbins == 0 or int(k_base + (first + count).max()) <= n_fft // 2 + 1
     if eng.stft_logbin_ok(n_fft) and nbins > 0 and rows_ok and fused:
         cols = nframes.astype(np.int32)
+        # the decaying tails are floored frames: certified from the batch's suffix energies instead of transformed
         curves, cur_off = eng.stft_logbin(batch.x, batch.off + starts, nframes, n_fft, hop,
-                                          bool(settings.use_hann_window), float(settings.floor_db), k_base, first, count)
+                                          bool(settings.use_hann_window), float(settings.floor_db), k_base, first, count,
+                                          tail=eng.tail_table(batch, starts))
     else:
         # frame-major only up to n_fft 16384: ira_logbin_aggregate's frame-major kernel holds at most 8193 rows in LDS
         tf = eng.stft_frame_major_ok(n_fft, 64) and n_fft // 2 + 1 <= 8193
+        tail = eng.tail_table(batch, starts) if tf and eng.stft_tail_ok(n_fft, 64) else None
         mag, mag_off, cols = eng.stft_mag_db(batch.x, batch.off + starts, nframes, n_fft, hop,
                                              bool(settings.use_hann_window), float(settings.floor_db), 64,
-                                             frame_major=tf)
+                                             frame_major=tf, tail=tail)
         curves, cur_off = eng.logbin_aggregate(mag, mag_off, cols, k_base, first, count,
                                                frame_major_rows=(n_fft // 2 + 1) if tf else 0)
     cols64 = np.asarray(cols, dtype=np.int64)

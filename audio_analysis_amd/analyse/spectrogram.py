@@ -76,9 +76,11 @@ def spectrogram_device(eng, batch, sample_rate_hz: int, settings: "SpectrogramAn
     a configuration ira_stft_mag_db_tf implements, of their (T_i, F) transposes (dict key "frame_major" says which)."""
     starts, lens, nframes = select_stft_segments(eng, batch, sample_rate_hz, settings, "spectrogram")
     tf = bool(frame_major) and eng.stft_frame_major_ok(int(settings.n_fft), stft_precision())
+    # the batch's suffix energies, shared with the modal cloud where both trim alike
+    tail = eng.tail_table(batch, starts) if tf and eng.stft_tail_ok(int(settings.n_fft), stft_precision()) else None
     mag, mag_off, cols = eng.stft_mag_db(batch.x, batch.off + starts, nframes, int(settings.n_fft),
                                          int(settings.hop_length), bool(settings.use_hann_window),
-                                         float(settings.floor_db), stft_precision(), frame_major=tf)
+                                         float(settings.floor_db), stft_precision(), frame_major=tf, tail=tail)
     return dict(mag=mag, mag_off=mag_off, cols=cols, starts=starts, lens=lens, frame_major=tf)
 
 

@@ -134,6 +134,8 @@ int32_t launch_stft(const float* x, const int64_t* off, const int32_t* nframes, 
 //   ira_stft_mag_db_tf  (T, F)  f32 / 4096                         stft6_kernel  (ira_stft3.hip)
 //                               f64 / 8192                         stft5_kernel  (ira_stft4.hip)
 //   ira_stft_logbin             f64 / 8192                         stft5_kernel  (ira_stft4.hip)
+// ira_stft_mag_db_tf_tail and ira_stft_logbin_tail are the same calls with ira_tail_energy's table: the same kernels,
+// stft5_kernel behind stft5_consts_kernel.
 // Every other configuration of the last two is IRA_E_UNSUPPORTED.  stft5_kernel takes eight consecutive frames of a segment
 // per workgroup in both of its modes; its results do not depend on that number.
 extern "C" int32_t ira_stft_mag_db(const float* x_dev, const int64_t* off_dev, const int32_t* nframes_dev,
@@ -164,11 +166,13 @@ extern "C" int32_t ira_stft_mag_db(const float* x_dev, const int64_t* off_dev, c
                              floor_db, out_dev, out_off_dev, frame_sel_dev, sel_off_dev, st);
 }
 
-extern "C" int32_t ira_stft_mag_db_tf(const float* x_dev, const int64_t* off_dev, const int32_t* nframes_dev,
-                                      int32_t nseg, int32_t max_frames, int32_t n_fft, int32_t hop,
-                                      const void* window_dev, const void* twiddle_dev, int32_t precision,
-                                      double floor_db, float* out_dev, const int64_t* out_off_dev,
-                                      const int32_t* frame_sel_dev, const int64_t* sel_off_dev, void* stream) {
+namespace {
+
+int32_t stft_mag_db_tf(const float* x_dev, const int64_t* off_dev, const int32_t* nframes_dev, int32_t nseg,
+                       int32_t max_frames, int32_t n_fft, int32_t hop, const void* window_dev, const void* twiddle_dev,
+                       int32_t precision, double floor_db, float* out_dev, const int64_t* out_off_dev,
+                       const int32_t* frame_sel_dev, const int64_t* sel_off_dev, const double* tail_dev,
+                       const int64_t* tail_off_dev, void* consts_dev, void* stream) {
   IRA_CHECK_PTR(x_dev); IRA_CHECK_PTR(off_dev); IRA_CHECK_PTR(nframes_dev); IRA_CHECK_PTR(window_dev);
   IRA_CHECK_PTR(twiddle_dev); IRA_CHECK_PTR(out_dev); IRA_CHECK_PTR(out_off_dev);
   if (frame_sel_dev != nullptr && sel_off_dev == nullptr) return IRA_E_NULL;
@@ -178,18 +182,19 @@ extern "C" int32_t ira_stft_mag_db_tf(const float* x_dev, const int64_t* off_dev
   hipStream_t st = (hipStream_t)stream;
   if (precision == 32 && n_fft == 4096)
     return ira_stft6_launch(x_dev, off_dev, nframes_dev, nseg, max_frames, hop, window_dev, twiddle_dev, floor_db,
-                            out_dev, out_off_dev, frame_sel_dev, sel_off_dev, st);
+                            out_dev, out_off_dev, frame_sel_dev, sel_off_dev, tail_dev, tail_off_dev, st);
   if (precision == 64 && n_fft == 8192)
     return ira_stft5_launch(x_dev, off_dev, nframes_dev, nseg, max_frames, hop, window_dev, twiddle_dev, floor_db,
-                            out_dev, out_off_dev, frame_sel_dev, sel_off_dev, 0, 0, nullptr, nullptr, st);
+                            out_dev, out_off_dev, frame_sel_dev, sel_off_dev, 0, 0, nullptr, nullptr, tail_dev,
+                            tail_off_dev, consts_dev, st);
   return IRA_E_UNSUPPORTED;
 }
 
-extern "C" int32_t ira_stft_logbin(const float* x_dev, const int64_t* off_dev, const int32_t* nframes_dev,
-                                   int32_t nseg, int32_t max_frames, int32_t n_fft, int32_t hop,
-                                   const void* window_dev, const void* twiddle_dev, int32_t precision, double floor_db,
-                                   int32_t k_base, const int32_t* first_dev, const int32_t* count_dev, int32_t nbins,
-                                   float* curves_dev, const int64_t* curves_off_dev, void* stream) {
+int32_t stft_logbin(const float* x_dev, const int64_t* off_dev, const int32_t* nframes_dev, int32_t nseg,
+                    int32_t max_frames, int32_t n_fft, int32_t hop, const void* window_dev, const void* twiddle_dev,
+                    int32_t precision, double floor_db, int32_t k_base, const int32_t* first_dev,
+                    const int32_t* count_dev, int32_t nbins, float* curves_dev, const int64_t* curves_off_dev,
+                    const double* tail_dev, const int64_t* tail_off_dev, void* consts_dev, void* stream) {
   IRA_CHECK_PTR(x_dev); IRA_CHECK_PTR(off_dev); IRA_CHECK_PTR(nframes_dev); IRA_CHECK_PTR(window_dev);
   IRA_CHECK_PTR(twiddle_dev); IRA_CHECK_PTR(first_dev); IRA_CHECK_PTR(count_dev); IRA_CHECK_PTR(curves_dev);
   IRA_CHECK_PTR(curves_off_dev);
@@ -198,6 +203,52 @@ extern "C" int32_t ira_stft_logbin(const float* x_dev, const int64_t* off_dev, c
   if (nseg > 65535) return IRA_E_SIZE;
   if (precision != 64 || n_fft != 8192) return IRA_E_UNSUPPORTED;
   return ira_stft5_launch(x_dev, off_dev, nframes_dev, nseg, max_frames, hop, window_dev, twiddle_dev, floor_db,
-                          curves_dev, curves_off_dev, nullptr, nullptr, nbins, k_base, first_dev, count_dev,
-                          (hipStream_t)stream);
+                          curves_dev, curves_off_dev, nullptr, nullptr, nbins, k_base, first_dev, count_dev, tail_dev,
+                          tail_off_dev, consts_dev, (hipStream_t)stream);
+}
+
+}  // namespace
+
+extern "C" int32_t ira_stft_mag_db_tf(const float* x_dev, const int64_t* off_dev, const int32_t* nframes_dev,
+                                      int32_t nseg, int32_t max_frames, int32_t n_fft, int32_t hop,
+                                      const void* window_dev, const void* twiddle_dev, int32_t precision,
+                                      double floor_db, float* out_dev, const int64_t* out_off_dev,
+                                      const int32_t* frame_sel_dev, const int64_t* sel_off_dev, void* stream) {
+  return stft_mag_db_tf(x_dev, off_dev, nframes_dev, nseg, max_frames, n_fft, hop, window_dev, twiddle_dev, precision,
+                        floor_db, out_dev, out_off_dev, frame_sel_dev, sel_off_dev, nullptr, nullptr, nullptr, stream);
+}
+
+// The same call with the suffix-energy table of ira_tail_energy.
+extern "C" int32_t ira_stft_mag_db_tf_tail(const float* x_dev, const int64_t* off_dev, const int32_t* nframes_dev,
+                                           int32_t nseg, int32_t max_frames, int32_t n_fft, int32_t hop,
+                                           const void* window_dev, const void* twiddle_dev, int32_t precision,
+                                           double floor_db, float* out_dev, const int64_t* out_off_dev,
+                                           const int32_t* frame_sel_dev, const int64_t* sel_off_dev,
+                                           const double* tail_dev, const int64_t* tail_off_dev, void* consts_dev,
+                                           void* stream) {
+  return stft_mag_db_tf(x_dev, off_dev, nframes_dev, nseg, max_frames, n_fft, hop, window_dev, twiddle_dev, precision,
+                        floor_db, out_dev, out_off_dev, frame_sel_dev, sel_off_dev, tail_dev, tail_off_dev, consts_dev,
+                        stream);
+}
+
+extern "C" int32_t ira_stft_logbin(const float* x_dev, const int64_t* off_dev, const int32_t* nframes_dev,
+                                   int32_t nseg, int32_t max_frames, int32_t n_fft, int32_t hop,
+                                   const void* window_dev, const void* twiddle_dev, int32_t precision, double floor_db,
+                                   int32_t k_base, const int32_t* first_dev, const int32_t* count_dev, int32_t nbins,
+                                   float* curves_dev, const int64_t* curves_off_dev, void* stream) {
+  return stft_logbin(x_dev, off_dev, nframes_dev, nseg, max_frames, n_fft, hop, window_dev, twiddle_dev, precision,
+                     floor_db, k_base, first_dev, count_dev, nbins, curves_dev, curves_off_dev, nullptr, nullptr, nullptr,
+                     stream);
+}
+
+extern "C" int32_t ira_stft_logbin_tail(const float* x_dev, const int64_t* off_dev, const int32_t* nframes_dev,
+                                        int32_t nseg, int32_t max_frames, int32_t n_fft, int32_t hop,
+                                        const void* window_dev, const void* twiddle_dev, int32_t precision,
+                                        double floor_db, int32_t k_base, const int32_t* first_dev,
+                                        const int32_t* count_dev, int32_t nbins, float* curves_dev,
+                                        const int64_t* curves_off_dev, const double* tail_dev,
+                                        const int64_t* tail_off_dev, void* consts_dev, void* stream) {
+  return stft_logbin(x_dev, off_dev, nframes_dev, nseg, max_frames, n_fft, hop, window_dev, twiddle_dev, precision,
+                     floor_db, k_base, first_dev, count_dev, nbins, curves_dev, curves_off_dev, tail_dev, tail_off_dev,
+                     consts_dev, stream);
 }

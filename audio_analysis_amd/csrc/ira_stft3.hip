@@ -26,6 +26,7 @@
 #include <type_traits>
 
 #include "ira_fft_reg.h"
+#include "ira_reduce.h"
 #include "ira_stft.h"
 
 namespace {
@@ -415,15 +416,49 @@ __global__ __launch_bounds__(64 * NT) void stft6_kernel(
     const float* __restrict__ x, const int64_t* __restrict__ off, const int32_t* __restrict__ nframes, int hop,
     const float* __restrict__ window, const cf* __restrict__ tw, float floor_lin, float floor_db,
     float* __restrict__ out, const int64_t* __restrict__ out_off, const int32_t* __restrict__ frame_sel,
-    const int64_t* __restrict__ sel_off, unsigned gx, unsigned ntiles, unsigned win_lds_off, int stagger, int resync) {
+    const int64_t* __restrict__ sel_off, unsigned gx, unsigned ntiles, unsigned win_lds_off, int stagger, int resync,
+    const double* __restrict__ tail, const int64_t* __restrict__ tail_off, double tail_lim) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   const int tid = threadIdx.x;
   const int team = __builtin_amdgcn_readfirstlane(tid >> 6), q0 = tid & 63;
   cf* ex = reinterpret_cast<cf*>(smem_raw) + (size_t)team * EXC;
   float* exf = reinterpret_cast<float*>(ex);
   float* winl = reinterpret_cast<float*>(smem_raw + win_lds_off);
-  for (int i = tid; i < 2 * M3; i += 64 * NT) winl[i] = window[i];
+  // While the window is staged every lane keeps the greatest |w| it has seen, as a bit pattern (ordered like the values, every
+  // NaN above infinity); the waves' maxima meet in LDS behind the window copy, across the barrier that is there anyway.
+#ifdef IRA_TUNING_BUILD
+  unsigned* wmaxl = reinterpret_cast<unsigned*>(winl + 2 * M3 + 1024);    // behind the scratch tail of the AB & 64 emulation
+#else
+  unsigned* wmaxl = reinterpret_cast<unsigned*>(winl + 2 * M3);
+#endif
+  unsigned wbits = 0;
+  for (int i = tid; i < 2 * M3; i += 64 * NT) {
+    const float w = window[i];
+    winl[i] = w;
+    const unsigned b = __float_as_uint(w) & 0x7fffffffu;
+    wbits = b > wbits ? b : wbits;
+  }
+  wbits = ira::wave_max_int(wbits);
+  if (q0 == 0) wmaxl[team] = wbits;
   __syncthreads();                                        // the only workgroup barrier of the kernel
+  // QUIET FRAMES (a launch with the suffix energies of ira_tail_energy and no frame selection).  S[j] of
+  // the table is the sum of x^2 from block j (512 samples) of the frame's segment to the end of its channel; frame t starts
+  // in block j = t hop / 512 and reads nothing past that end, so every bin obeys
+  //   |X[k]|^2 <= N sum (x w)^2 <= N wmax2 S[j]          (N = 4096, wmax2 = the greatest w^2 of THIS call's window).
+  // Where 4 N wmax2 S[j] <= floor^2 the exact |X[k]| is at most half the floor; the float32 transform adds an error of a
+  // few 1e-6 of sqrt(N sum (x w)^2), and the float64 table sum is off by 1e-13: db_quarter's maximum returns floor_db for
+  // every bin.  Such a frame stores floor_db through the loud path's lane mapping and loads, multiplies and transforms
+  // nothing.  The host passes tail_lim = floor^2 / (4 N); the test is S * wmax2 <= tail_lim.
+  // A NaN or an infinity from the frame on makes S[j] non-finite, a NaN in the window makes wmax2 one: the test is false
+  // and the frame takes the loud path with its NaN flag.  The test is wave-uniform (a wave owns its frame).
+  double wmax2 = 0.0;
+  if (tail != nullptr) {
+    unsigned wm = wmaxl[0];
+#pragma unroll
+    for (int i = 1; i < NT; ++i) wm = wmaxl[i] > wm ? wmaxl[i] : wm;
+    const double wm64 = (double)__uint_as_float(wm);
+    wmax2 = ira::uniform(wm64 * wm64);
+  }
 
   // Tiles of NT frames in (segment, frame group) order.  Workgroups are dealt round-robin over the 8 XCDs (each with its
   // own L2): XCD c takes the contiguous range [c * per, (c + 1) * per) and its workgroups walk it interleaved, so that the
@@ -434,11 +469,16 @@ __global__ __launch_bounds__(64 * NT) void stft6_kernel(
   const unsigned t_end = (xcd + 1u) * per < ntiles ? (xcd + 1u) * per : ntiles;
   const float qn = __uint_as_float(0x7fc00000u);
 
-  auto locate = [&](unsigned t, const float*& fxp, float*& fop) -> bool {       // wave-uniform
+  auto locate = [&](unsigned t, const float*& fxp, float*& fop, bool& quietp) -> bool {       // wave-uniform
     const int seg = (int)(t / gx);
     const int col = (int)(t - (unsigned)seg * gx) * NT + team;
     if (col >= nframes[seg]) return false;
     const int64_t frame = frame_sel ? (int64_t)frame_sel[sel_off[seg] + col] : (int64_t)col;
+    quietp = false;
+    if (tail != nullptr) {                                  // (the launcher passes no table with a frame selection)
+      const double S = ira::uniform(tail[ira::uniform((long long)(tail_off[seg] + (frame * hop) / IRA_TAIL_BLOCK))]);
+      quietp = S * wmax2 <= tail_lim;
+    }
     // wave-uniform bases in scalar registers: every access below is base + 32-bit lane offset
     fxp = x + ira::uniform((long long)(off[seg] + frame * hop));
     fop = out + ira::uniform((long long)(out_off[seg] + (int64_t)col * F3));
@@ -476,8 +516,8 @@ __global__ __launch_bounds__(64 * NT) void stft6_kernel(
   };
   const float* fx = x;
   float* fo = out;
-  bool have = false;
-  while (t < t_end && !(have = locate(t, fx, fo))) t += t_step;
+  bool have = false, quiet = false;
+  while (t < t_end && !(have = locate(t, fx, fo, quiet))) t += t_step;
 
   // The sixteen wave-uniform factors W_N^(64 i) of the post step live in scalar registers for the whole walk: inside the loop
   // they were sixteen scalar loads per frame in four to eight serial round trips (s_waitcnt lgkmcnt(0)).
@@ -493,94 +533,105 @@ __global__ __launch_bounds__(64 * NT) void stft6_kernel(
     unsigned tn = t + t_step;
     const float* fxn = fx;
     float* fon = fo;
-    bool have_n = false;
-    while (tn < t_end && !(have_n = locate(tn, fxn, fon))) tn += t_step;
-    // The lane's twiddle factors and their powers are the same for every frame; left to itself the optimiser hoists all of
-    // them out of this loop (~190 registers) and spills them.  An opaque copy of the lane index keeps them per-frame work,
-    // as in the one-frame kernels: three 8-byte L1 hits and ~220 multiply-adds per frame instead of scratch traffic.
-    int q = q0;
-    asm volatile("" : "+v"(q));
-    if (AB & 64) {
-      // the emulated share of the cooperative staging: 3 x 16 bytes per lane from the frame's own samples into the free tail of LDS
-      typedef float f4 __attribute__((ext_vector_type(4), aligned(4)));
-      float* tail = reinterpret_cast<float*>(smem_raw + win_lds_off) + 2 * M3;       // behind the window copy (4 KB are free)
-#pragma unroll
-      for (int u = 0; u < 3; ++u) {
-        const f4 v4 = *reinterpret_cast<const f4*>(fx + 4u * (unsigned)(q + 64 * u));
-        *reinterpret_cast<f4*>(tail + 4 * (q + 64 * (u & 3))) = v4;
-      }
-    }
-    const cf wlane = tw[(unsigned)q];
-
-    // ---- steps 1 to 3 ------------------------------------------------------------------------------------------------
-    cf z3[4][8];
-    frame_steps<AB>([&](int h, float (&xa)[16], float (&xb)[16]) { load_half(fx, q, h, xa, xb); }, (AB & 2) != 0, winl, tw,
-                    ex, q, z3);
-
-    // ---- E3: the mirror partner Z[M - k] of every bin the lane holds.  After step 3 the lane already holds Z[q + 64 i'],
-    // i' = hh + 4 k3 < 32, in natural order; the partner of k = q + 64 i (i < 16) is register 31 - i of lane (64 - q) & 63 --
-    // and for lane 0 its OWN register 32 - i (register 0 for i = 0).  Round 5: a lane permutation through the LDS crossbar
-    // (ds_bpermute_b32: no LDS memory, no wave_sync) instead of writing real parts, then imaginary parts, through a
-    // 2048-float buffer and reading both orders back: 32 permutes + 32 selects for 130 LDS accesses and four round trips
-    // (tools/micro/stft_epilogue_rate.hip: -540 SIMD-cycles per frame; profiles/r05_stft_epilogue.txt).  Pure data movement:
-    // the same float32 values as before.  AB & 32 (tuning build) keeps the LDS form as the A/B.
-    float zkr[16], zpr[16], zki[16], zpi[16], midr, midi;
-    if (AB & 32) {
-      mirror_exchange_lds(z3, exf, q, zkr, zpr, zki, zpi, midr, midi);
-      wave_sync();                                          // the next frame's step 1 writes this buffer again
-    } else {
-      // (the permutes are issued inside the post loop below, bin pair by bin pair: holding all 64 partner values beside the
-      // lane's own 64 spills)
-      zkr[0] = z3[0][0].re; zki[0] = z3[0][0].im;           // the NaN flag below reads Z[0]
-      midr = z3[0][brev_bits(4, 3)].re;                     // Z[1024] = lane 0's register 16 (only lane 0 stores the bin)
-      midi = z3[0][brev_bits(4, 3)].im;
-      wave_sync();                                          // the next frame's step 1 writes the exchange buffer again
-    }
-    const int perm_src = ((64 - q) & 63) << 2;              // byte address of the partner lane for ds_bpermute
-
-    // ---- post: X[k] = E + P, X[M-k] = conj(E - P) with E = (Zk + conj Zp)/2, P = W_N^k (-i)(Zk - conj Zp)/2 -> dB -> store.
-    // A NaN (or infinite) sample anywhere in the frame makes every bin of numpy's rfft NaN (spectrogram.py:150): it shows
-    // in Z[0] = sum of the packed inputs, which lane 0 holds as its first pair -- one flag per frame.  Every result is
-    // stored as soon as it exists (nothing of it stays live).
-    const float z0 = (zkr[0] - zkr[0]) + (zki[0] - zki[0]);                // 0 if finite, NaN otherwise
-    const bool bad = __shfl(z0, 0, 64) != 0.0f;                            // wave-uniform: a branch, not a select per bin
-    // per-lane pointers once per frame: every store below is base + immediate offset (as 32-bit lane offsets added to a
-    // scalar base each store took an integer add of its own: an unsigned offset cannot be folded into the immediate)
-    float* const flo = fo + q;
-    float* const fhi = fo + (M3 - q);
-    if (__builtin_expect(bad, 0)) {
+    bool have_n = false, quiet_n = false;
+    while (tn < t_end && !(have_n = locate(tn, fxn, fon, quiet_n))) tn += t_step;
+    if (quiet) {
+      // floor_db on all 2049 rows, lane mapping of the loud path's stores; no LDS access, so nothing to fence
       if (!(AB & 4)) {
+        float* const flo = fo + q0;
+        float* const fhi = fo + (M3 - q0);
 #pragma unroll
-        for (int i = 0; i < 16; ++i) { flo[64 * i] = qn; fhi[-64 * i] = qn; }
-        if (q == 0) fo[M3 / 2] = qn;
+        for (int i = 0; i < 16; ++i) { flo[64 * i] = floor_db; fhi[-64 * i] = floor_db; }
+        if (q0 == 0) fo[M3 / 2] = floor_db;
       }
     } else {
-      float sacc = 0.0f;
+      // The lane's twiddle factors and their powers are the same for every frame; left to itself the optimiser hoists all of
+      // them out of this loop (~190 registers) and spills them.  An opaque copy of the lane index keeps them per-frame work,
+      // as in the one-frame kernels: three 8-byte L1 hits and ~220 multiply-adds per frame instead of scratch traffic.
+      int q = q0;
+      asm volatile("" : "+v"(q));
+      if (AB & 64) {
+        // the emulated share of the cooperative staging: 3 x 16 bytes per lane from the frame's own samples into the free tail of LDS
+        typedef float f4 __attribute__((ext_vector_type(4), aligned(4)));
+        float* stail = reinterpret_cast<float*>(smem_raw + win_lds_off) + 2 * M3;       // behind the window copy (4 KB are free)
 #pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        const cf wk = (AB & 128) ? tw[(unsigned)(q + 64 * i)]
-                                 : ira::cmul(wlane, (AB & 8) ? cf{wlane.im * (float)(i + 1), wlane.re} : wuni[i]);
-        float lo, hi;
-        if (AB & 32) {
-          untangle_db<(AB & 16) != 0>(zkr[i], zpr[i], zki[i], zpi[i], wk, floor_db, lo, hi);
-        } else {
-          const int ip = 31 - i, il = (32 - i) & 31;        // partner register of lanes q > 0 / of lane 0
-          const cf own = z3[i & 3][brev_bits(i >> 2, 3)];
-          const cf pv = z3[ip & 3][brev_bits(ip >> 2, 3)], lv = z3[il & 3][brev_bits(il >> 2, 3)];
-          const float pr = __int_as_float(__builtin_amdgcn_ds_bpermute(perm_src, __float_as_int(pv.re)));
-          const float pi = __int_as_float(__builtin_amdgcn_ds_bpermute(perm_src, __float_as_int(pv.im)));
-          untangle_db<(AB & 16) != 0>(own.re, q == 0 ? lv.re : pr, own.im, q == 0 ? lv.im : pi, wk, floor_db, lo, hi);
+        for (int u = 0; u < 3; ++u) {
+          const f4 v4 = *reinterpret_cast<const f4*>(fx + 4u * (unsigned)(q + 64 * u));
+          *reinterpret_cast<f4*>(stail + 4 * (q + 64 * (u & 3))) = v4;
         }
-        if (AB & 4) { sacc += lo + hi; continue; }
-        flo[64 * i] = lo;
-        fhi[-64 * i] = hi;                                    // k = 0 -> bin M (Nyquist)
       }
-      const float mid = db_quarter<(AB & 16) != 0>(2.0f * midr, 2.0f * midi, floor_db);
-      if (AB & 4) { if (sacc + mid == 12345.678f) fo[q] = sacc; }
-      else if (q == 0) fo[M3 / 2] = mid;
-    }
+      const cf wlane = tw[(unsigned)q];
+
+      // ---- steps 1 to 3 ------------------------------------------------------------------------------------------------
+      cf z3[4][8];
+      frame_steps<AB>([&](int h, float (&xa)[16], float (&xb)[16]) { load_half(fx, q, h, xa, xb); }, (AB & 2) != 0, winl, tw,
+                      ex, q, z3);
+
+      // ---- E3: the mirror partner Z[M - k] of every bin the lane holds.  After step 3 the lane already holds Z[q + 64 i'],
+      // i' = hh + 4 k3 < 32, in natural order; the partner of k = q + 64 i (i < 16) is register 31 - i of lane (64 - q) & 63 --
+      // and for lane 0 its OWN register 32 - i (register 0 for i = 0).  Round 5: a lane permutation through the LDS crossbar
+      // (ds_bpermute_b32: no LDS memory, no wave_sync) instead of writing real parts, then imaginary parts, through a
+      // 2048-float buffer and reading both orders back: 32 permutes + 32 selects for 130 LDS accesses and four round trips
+      // (tools/micro/stft_epilogue_rate.hip: -540 SIMD-cycles per frame; profiles/r05_stft_epilogue.txt).  Pure data movement:
+      // the same float32 values as before.  AB & 32 (tuning build) keeps the LDS form as the A/B.
+      float zkr[16], zpr[16], zki[16], zpi[16], midr, midi;
+      if (AB & 32) {
+        mirror_exchange_lds(z3, exf, q, zkr, zpr, zki, zpi, midr, midi);
+        wave_sync();                                          // the next frame's step 1 writes this buffer again
+      } else {
+        // (the permutes are issued inside the post loop below, bin pair by bin pair: holding all 64 partner values beside the
+        // lane's own 64 spills)
+        zkr[0] = z3[0][0].re; zki[0] = z3[0][0].im;           // the NaN flag below reads Z[0]
+        midr = z3[0][brev_bits(4, 3)].re;                     // Z[1024] = lane 0's register 16 (only lane 0 stores the bin)
+        midi = z3[0][brev_bits(4, 3)].im;
+        wave_sync();                                          // the next frame's step 1 writes the exchange buffer again
+      }
+      const int perm_src = ((64 - q) & 63) << 2;              // byte address of the partner lane for ds_bpermute
+
+      // ---- post: X[k] = E + P, X[M-k] = conj(E - P) with E = (Zk + conj Zp)/2, P = W_N^k (-i)(Zk - conj Zp)/2 -> dB -> store.
+      // A NaN (or infinite) sample anywhere in the frame makes every bin of numpy's rfft NaN (spectrogram.py:150): it shows
+      // in Z[0] = sum of the packed inputs, which lane 0 holds as its first pair -- one flag per frame.  Every result is
+      // stored as soon as it exists (nothing of it stays live).
+      const float z0 = (zkr[0] - zkr[0]) + (zki[0] - zki[0]);                // 0 if finite, NaN otherwise
+      const bool bad = __shfl(z0, 0, 64) != 0.0f;                            // wave-uniform: a branch, not a select per bin
+      // per-lane pointers once per frame: every store below is base + immediate offset (as 32-bit lane offsets added to a
+      // scalar base each store took an integer add of its own: an unsigned offset cannot be folded into the immediate)
+      float* const flo = fo + q;
+      float* const fhi = fo + (M3 - q);
+      if (__builtin_expect(bad, 0)) {
+        if (!(AB & 4)) {
+#pragma unroll
+          for (int i = 0; i < 16; ++i) { flo[64 * i] = qn; fhi[-64 * i] = qn; }
+          if (q == 0) fo[M3 / 2] = qn;
+        }
+      } else {
+        float sacc = 0.0f;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+          const cf wk = (AB & 128) ? tw[(unsigned)(q + 64 * i)]
+                                   : ira::cmul(wlane, (AB & 8) ? cf{wlane.im * (float)(i + 1), wlane.re} : wuni[i]);
+          float lo, hi;
+          if (AB & 32) {
+            untangle_db<(AB & 16) != 0>(zkr[i], zpr[i], zki[i], zpi[i], wk, floor_db, lo, hi);
+          } else {
+            const int ip = 31 - i, il = (32 - i) & 31;        // partner register of lanes q > 0 / of lane 0
+            const cf own = z3[i & 3][brev_bits(i >> 2, 3)];
+            const cf pv = z3[ip & 3][brev_bits(ip >> 2, 3)], lv = z3[il & 3][brev_bits(il >> 2, 3)];
+            const float pr = __int_as_float(__builtin_amdgcn_ds_bpermute(perm_src, __float_as_int(pv.re)));
+            const float pi = __int_as_float(__builtin_amdgcn_ds_bpermute(perm_src, __float_as_int(pv.im)));
+            untangle_db<(AB & 16) != 0>(own.re, q == 0 ? lv.re : pr, own.im, q == 0 ? lv.im : pi, wk, floor_db, lo, hi);
+          }
+          if (AB & 4) { sacc += lo + hi; continue; }
+          flo[64 * i] = lo;
+          fhi[-64 * i] = hi;                                    // k = 0 -> bin M (Nyquist)
+        }
+        const float mid = db_quarter<(AB & 16) != 0>(2.0f * midr, 2.0f * midi, floor_db);
+        if (AB & 4) { if (sacc + mid == 12345.678f) fo[q] = sacc; }
+        else if (q == 0) fo[M3 / 2] = mid;
+      }
+    }                                                       // loud frame
     sync_up_to(have_n ? (tn - t_first) / t_step : n_pos);
-    t = tn; fx = fxn; fo = fon; have = have_n;
+    t = tn; fx = fxn; fo = fon; have = have_n; quiet = quiet_n;
   }
   sync_up_to(n_pos);
 }
@@ -592,12 +643,14 @@ constexpr int IRA_STFT6_RESYNC_DEFAULT = 2;
 
 int32_t ira_stft6_launch(const float* x, const int64_t* off, const int32_t* nframes, int32_t nseg, int32_t max_frames,
                          int32_t hop, const void* window, const void* tw, double floor_db, float* out,
-                         const int64_t* out_off, const int32_t* frame_sel, const int64_t* sel_off, hipStream_t st) {
+                         const int64_t* out_off, const int32_t* frame_sel, const int64_t* sel_off, const double* tail,
+                         const int64_t* tail_off, hipStream_t st) {
   constexpr size_t lds_main = ((size_t)NT * EXC * sizeof(cf) + 15) & ~(size_t)15;
 #ifdef IRA_TUNING_BUILD
-  constexpr size_t lds = lds_main + (size_t)2 * M3 * sizeof(float) + 4096;   // + the scratch tail of the AB & 64 emulation
+  constexpr size_t lds = lds_main + (size_t)2 * M3 * sizeof(float) + 4096 + NT * sizeof(unsigned);   // + the scratch tail of the
+                                                                                  // AB & 64 emulation + the window maxima
 #else
-  constexpr size_t lds = lds_main + (size_t)2 * M3 * sizeof(float);
+  constexpr size_t lds = lds_main + (size_t)2 * M3 * sizeof(float) + NT * sizeof(unsigned);   // + the waves' window maxima
 #endif
   static_assert(lds <= 160 * 1024, "one workgroup must fit the CU's LDS");
   int dev = 0, cus = 0;
@@ -611,6 +664,9 @@ int32_t ira_stft6_launch(const float* x, const int64_t* off, const int32_t* nfra
   if (tiles < grid) grid = (unsigned)tiles;
   if (grid == 0) return IRA_OK;
   const double floor_lin = std::pow(10.0, floor_db / 20.0);
+  if (frame_sel != nullptr) tail = nullptr;        // selected frames say nothing about where a frame's samples end
+  if (tail != nullptr && tail_off == nullptr) return IRA_E_NULL;
+  const double tail_lim = floor_lin * floor_lin / (4.0 * (2 * M3));
   const int stagger = ira_tune_int("IRA_STFT6_STAGGER", 0);
 #define IRA_LAUNCH6(AB)                                                                                                   \
   do {                                                                                                                    \
@@ -618,7 +674,8 @@ int32_t ira_stft6_launch(const float* x, const int64_t* off, const int32_t* nfra
     stft6_kernel<AB><<<grid, 64 * NT, lds, st>>>(x, off, nframes, hop, static_cast<const float*>(window),                 \
                                                  static_cast<const cf*>(tw), (float)floor_lin, (float)floor_db, out,      \
                                                  out_off, frame_sel, sel_off, gx, (unsigned)tiles, (unsigned)lds_main,    \
-                                                 stagger, ira_tune_int("IRA_STFT6_RESYNC", IRA_STFT6_RESYNC_DEFAULT));    \
+                                                 stagger, ira_tune_int("IRA_STFT6_RESYNC", IRA_STFT6_RESYNC_DEFAULT),     \
+                                                 tail, tail_off, tail_lim);                                               \
   } while (0)
 #ifdef IRA_TUNING_BUILD
   switch (ira_tune_int("IRA_STFT6_ABLATE", 0)) {

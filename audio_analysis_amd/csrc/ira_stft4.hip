@@ -22,6 +22,11 @@
 // workgroup stores its floored values without a frame loop.  In log-bin mode the value a floored frame leaves in a log bin
 // depends on the bin alone: a quiet frame of an uncertified chunk takes it from a table the workgroup's first quiet frame
 // builds (quiet_val) instead of summing the same constant again.
+// QUIET SUFFIXES skip the pass as well.  What is quiet in an impulse response is a suffix of it: a launch that is given the
+// suffix energies of ira_tail_energy (ira_tailenergy.hip) tests a chunk with ONE load -- 4 N max(w^2) S[j] <= floor^2, j the
+// 512-sample block its first frame starts in -- before it builds anything, and copies a floored row that
+// stft5_consts_kernel formed once for the launch; a chunk the table does not certify goes to the frame loop without a span
+// pass.  Without the table the kernel is what it was.
 // 16-byte LDS accesses are served a quarter wave at a time: in every exchange the 16 lanes of a quarter differ in k1
 // (or in consecutive m), which the strides 129 and 1 map to distinct 16-byte bank groups: conflict free.
 // Why four waves per frame (profiles/r02_stft4_counters.txt): with two waves per frame (32 values per lane, 228 VGPRs, two
@@ -117,6 +122,57 @@ typedef float fquad5 __attribute__((ext_vector_type(4), aligned(4)));   // four 
 // loud chunk more and certifies fewer quiet ones (from hop = n_fft on it reads the gaps between the frames as well).
 constexpr int64_t SPAN5_MAX = 2 * (2 * M4);
 
+// What a launch with a suffix-energy table needs of its window table and its log bins, worked out ONCE per launch by
+// stft5_consts_kernel instead of by every certified workgroup: the greatest w^2 and the log-bin row of a floored frame.
+// Layout of the caller's scratch (IRA_STFT_CONSTS_DOUBLES): the double, then lb_nbins floats.
+struct Stft5Consts {
+  double wmax2;
+  float row[1];                                    // lb_nbins values (none in dB mode)
+};
+
+// The greatest w^2 of the window table, taken over the bit patterns of |w^2|, which order like the values and put every
+// NaN above infinity: a NaN in the table comes out as a NaN (and certifies nothing).  A maximum: whatever order the lanes
+// visit the table in, the bits are the same.  wmax (one slot per wave) is LDS; ends behind a barrier.
+__device__ __forceinline__ double window_max_sq5(const double* __restrict__ window, int q, unsigned long long* wmax) {
+  unsigned long long wb = 0;
+#pragma unroll
+  for (int j = 0; j < 2 * M4 / (2 * TL5); ++j) {
+    const dpair5 w = *reinterpret_cast<const dpair5*>(window + 2 * (j * TL5 + q));
+    const unsigned long long ba = (unsigned long long)__double_as_longlong(w.a * w.a) & 0x7fffffffffffffffull;
+    const unsigned long long bb = (unsigned long long)__double_as_longlong(w.b * w.b) & 0x7fffffffffffffffull;
+    wb = ba > wb ? ba : wb;
+    wb = bb > wb ? bb : wb;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const unsigned long long other = __shfl_xor(wb, o, 64);
+    wb = other > wb ? other : wb;
+  }
+  if ((q & 63) == 0) wmax[q >> 6] = wb;
+  __syncthreads();
+  unsigned long long wm = wmax[0];
+#pragma unroll
+  for (int i = 1; i < TL5 / 64; ++i) wm = wmax[i] > wm ? wmax[i] : wm;
+  return ira::uniform(__longlong_as_double((long long)wm));
+}
+
+// One workgroup per launch.  row[bb] is what stft5_kernel's quiet_bin gives log bin bb of a floored frame: the same
+// function of the same float floor_db on the same table, so the same bytes.
+__global__ __launch_bounds__(TL5) void stft5_consts_kernel(const double* __restrict__ window, float floor_db, int lb_nbins,
+                                                           const int32_t* __restrict__ lb_count, Stft5Consts* __restrict__ cst) {
+  __shared__ unsigned long long wmax[TL5 / 64];
+  __shared__ ira::LogTabEntry ltab[ira::LOGTAB_N];
+  const int q = threadIdx.x;
+  ira::build_log_table(ltab, q);
+  const double wmax2 = window_max_sq5(window, q, wmax);          // its barrier also publishes ltab
+  if (q == 0) cst->wmax2 = wmax2;
+  const double floor_lin32 = ira::uniform(exp10((double)floor_db * 0.05));
+  for (int bb = q; bb < lb_nbins; bb += TL5) {
+    const int c = lb_count[bb];
+    cst->row[bb] = c > 0 ? logbin_mean_db<true>(nullptr, floor_lin32, c, ltab) : __uint_as_float(0x7fc00000u);
+  }
+}
+
 // One workgroup transforms kfr CONSECUTIVE frames of one segment, one after the other.  Everything that does not depend on
 // the frame is done once, before the frame loop: the XCD remap and (segment, chunk) decode, the segment's job values (as
 // scalars), the log2 table in LDS, the hull of the log bins and 10^(floor/20).  Only scalar state lives across the loop:
@@ -131,11 +187,12 @@ __global__ __launch_bounds__(TL5) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     const double* __restrict__ window, const cdd* __restrict__ tw, double floor_lin, float floor_db,
     float* __restrict__ out, const int64_t* __restrict__ out_off, const int32_t* __restrict__ frame_sel,
     const int64_t* __restrict__ sel_off, int lb_nbins, int lb_kbase, const int32_t* __restrict__ lb_first,
-    const int32_t* __restrict__ lb_count, int kfr, int ablate) {
+    const int32_t* __restrict__ lb_count, int kfr, int ablate, const double* __restrict__ tail,
+    const int64_t* __restrict__ tail_off, const Stft5Consts* __restrict__ cst) {
   // ablate (IRA_STFT5_ABLATE, tuning build, timing only): 1 no window loads, 2 no sample loads, 4 no dB -> linear conversion;
-  // results unchanged (tests and A/B): 256 every frame takes the full path -- the quiet-frame rule, the chunk test and the
-  // quiet table are all off; 512 the chunk test alone is off; 1024 the quiet table alone is off (a quiet frame fills the
-  // exchange buffer with the floored value and sums it like a loud one)
+  // results unchanged (tests and A/B): 256 every frame takes the full path -- the quiet-frame rule, the chunk test (table
+  // test included) and the quiet table are all off; 512 the chunk test (table test included) alone is off; 1024 the quiet
+  // table alone is off (a quiet frame fills the exchange buffer with the floored value and sums it like a loud one)
   __shared__ __attribute__((aligned(16))) cdd ex[EXC4];
   __shared__ double wave_energy[2][TL5 / 64];      // per-wave sums of (xw)^2, one slot per frame parity
   __shared__ double chunk_energy[TL5 / 64];        // per-wave sums of x^2 over the chunk's span (written once, before the loop)
@@ -154,14 +211,52 @@ __global__ __launch_bounds__(TL5) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
   if (col0 >= T_out) return;                       // the whole workgroup, before its first barrier
   const int col1 = T_out - col0 < kfr ? T_out : col0 + kfr;
   int q = threadIdx.x;
+  float* os = out + ira::uniform(out_off[seg]);
+  const double floor_pow = floor_lin * floor_lin;
+
+  // ---- quiet suffix? (a launch with a suffix-energy table and no frame selection) -------------------------------------
+  // The table's S[j] is the sum of x^2 from block j (512 samples) of THIS segment to the end of its channel (ira_tail_energy;
+  // the caller's contract: the table's segments start where these do, and no frame reads past the channel's end).  The
+  // chunk's first frame starts at sample col0 hop, inside block j = col0 hop / 512, and frames are consecutive: every
+  // sample the chunk reads is one of those S[j] sums, so for each of its frames
+  //   sum (x w)^2 <= wmax2 sum x^2 <= wmax2 S_exact[j].
+  // S[j] is a float64 sum of at most a few million non-negative terms (480 000 for ten seconds) in trees no deeper than a
+  // few dozen additions: S_exact <= S[j] (1 + 1e-13), far inside the factor 4 the per-frame rule below keeps over the
+  // transform's own rounding.  So 4 N wmax2 S[j] <= floor^2 puts every frame of the chunk under that rule, as the span
+  // pass further down does -- for ONE load, before the log table, the hull and any barrier; the frames get the floor (dB
+  // mode) or the floored log-bin row stft5_consts_kernel formed with quiet_bin's arithmetic, the bytes the frame loop
+  // gives a floored frame.  A suffix holds more than the chunk's span, so the test certifies a little later in a decay
+  // than the span pass; what it misses the per-frame rule still finds.  A NaN or an infinity from the chunk on makes
+  // S[j] non-finite, a NaN in the window makes wmax2 one: the comparison is false.  Workgroup-uniform (launch arguments
+  // and values read through ira::uniform): either every wave leaves here or none.
+  // A chunk the table does not certify goes straight to the frame loop: it does not pay the span pass as well.
+  const bool use_tail = tail != nullptr && frame_sel == nullptr && !IRA_ABL(ablate & (256 | 512));
+  if (use_tail) {
+    const int64_t j = ((int64_t)col0 * hop) / IRA_TAIL_BLOCK;
+    const double S = ira::uniform(tail[ira::uniform(tail_off[seg]) + j]);
+    const double wmax2 = ira::uniform(cst->wmax2);
+    if (S * (4.0 * (2 * M4)) * wmax2 <= floor_pow) {
+      const int nfr = col1 - col0;
+      if (lb_nbins <= 0) {
+        float* fo = os + (int64_t)col0 * F4;
+        for (int i = q; i < nfr * F4; i += TL5) fo[i] = floor_db;
+      } else {
+        for (int bb = q; bb < lb_nbins; bb += TL5) {
+          const float val = cst->row[bb];
+          float* o = os + (int64_t)bb * T_out + col0;
+          for (int jf = 0; jf < nfr; ++jf) o[jf] = val;
+        }
+      }
+      return;
+    }
+  }
+
   double* exd = reinterpret_cast<double*>(ex);
   ira::build_log_table(ltab, q);
   if (q < 2) lb_range[q] = q == 0 ? F4 : 0;
 
   const float* xs = x + ira::uniform(off[seg]);
-  float* os = out + ira::uniform(out_off[seg]);
   const int32_t* fsel = frame_sel ? frame_sel + ira::uniform(sel_off[seg]) : nullptr;
-  const double floor_pow = floor_lin * floor_lin;
   const float qnan32 = __uint_as_float(0x7fc00000u);
   // Log-bin mode: the hull [k_lo, k_hi) of the rows some log bin reads, and the linear value of a floored row.  Only the
   // hull's rows are converted: 20 Hz .. 20 kHz is rows 4 .. 3413 of 4097, a sixth of the conversions (the costliest part
@@ -208,7 +303,8 @@ __global__ __launch_bounds__(TL5) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
   // Every branch here is workgroup-uniform (launch arguments, values read back through ira::uniform from LDS that all lanes
   // read alike), so all four waves meet the same barriers; a certified chunk leaves behind its last one.
   // The decision may differ from K to K, the bytes do not: a certified frame gets what the loop would have given it.
-  if (!IRA_ABL(ablate & (256 | 512)) && fsel == nullptr && (int64_t)(col1 - col0 - 1) * hop + 2 * M4 <= SPAN5_MAX) {
+  // A launch with a suffix-energy table has made its test above and does not pass over the span.
+  if (!use_tail && !IRA_ABL(ablate & (256 | 512)) && fsel == nullptr && (int64_t)(col1 - col0 - 1) * hop + 2 * M4 <= SPAN5_MAX) {
     const int nfr = col1 - col0;
     const int span = (nfr - 1) * hop + 2 * M4;
     const float* cx = xs + (int64_t)col0 * hop;
@@ -240,26 +336,7 @@ __global__ __launch_bounds__(TL5) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     __syncthreads();
     const double scaled = ira::uniform((chunk_energy[0] + chunk_energy[1]) + (chunk_energy[2] + chunk_energy[3])) * (4.0 * (2 * M4));
     if (scaled <= 16.0 * floor_pow) {
-      unsigned long long wb = 0;
-#pragma unroll
-      for (int j = 0; j < 2 * M4 / (2 * TL5); ++j) {
-        const dpair5 w = *reinterpret_cast<const dpair5*>(window + 2 * (j * TL5 + q));
-        const unsigned long long ba = (unsigned long long)__double_as_longlong(w.a * w.a) & 0x7fffffffffffffffull;
-        const unsigned long long bb = (unsigned long long)__double_as_longlong(w.b * w.b) & 0x7fffffffffffffffull;
-        wb = ba > wb ? ba : wb;
-        wb = bb > wb ? bb : wb;
-      }
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) {
-        const unsigned long long other = __shfl_xor(wb, o, 64);
-        wb = other > wb ? other : wb;
-      }
-      if ((q & 63) == 0) chunk_wmax[q >> 6] = wb;
-      __syncthreads();
-      unsigned long long wm = chunk_wmax[0];
-#pragma unroll
-      for (int i = 1; i < TL5 / 64; ++i) wm = chunk_wmax[i] > wm ? chunk_wmax[i] : wm;
-      const double wmax2 = ira::uniform(__longlong_as_double((long long)wm));
+      const double wmax2 = window_max_sq5(window, q, chunk_wmax);
       if (scaled * wmax2 <= floor_pow) {
         if (lb_nbins <= 0) {
           // dB mode: the chunk's frames are one run of nfr * 4097 floats of the frame-major matrix
@@ -521,13 +598,22 @@ __global__ __launch_bounds__(TL5) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
 int32_t ira_stft5_launch(const float* x, const int64_t* off, const int32_t* nframes, int32_t nseg, int32_t max_frames,
                          int32_t hop, const void* window, const void* tw, double floor_db, float* out,
                          const int64_t* out_off, const int32_t* frame_sel, const int64_t* sel_off, int32_t lb_nbins,
-                         int32_t lb_kbase, const int32_t* lb_first, const int32_t* lb_count, hipStream_t st) {
+                         int32_t lb_kbase, const int32_t* lb_first, const int32_t* lb_count, const double* tail,
+                         const int64_t* tail_off, void* consts, hipStream_t st) {
   const double floor_lin = std::pow(10.0, floor_db / 20.0);
   int kfr = ira_tune_int("IRA_STFT5_K", KF5);
   if (kfr < 1) kfr = 1;
+  if (frame_sel != nullptr) tail = nullptr;        // selected frames are not consecutive: the table says nothing about them
+  if (tail != nullptr) {
+    if (tail_off == nullptr || consts == nullptr) return IRA_E_NULL;
+    stft5_consts_kernel<<<1, TL5, 0, st>>>(static_cast<const double*>(window), (float)floor_db, lb_nbins > 0 ? lb_nbins : 0,
+                                           lb_count, static_cast<Stft5Consts*>(consts));
+    IRA_TRY_HIP(hipGetLastError());
+  }
   dim3 grid((max_frames + kfr - 1) / kfr, nseg);
   stft5_kernel<<<grid, TL5, (size_t)ira_tune_int("IRA_STFT5_LDS_PAD", 0), st>>>(x, off, nframes, hop, static_cast<const double*>(window),
                                      static_cast<const cdd*>(tw), floor_lin, (float)floor_db, out, out_off, frame_sel,
-                                     sel_off, lb_nbins, lb_kbase, lb_first, lb_count, kfr, ira_tune_int("IRA_STFT5_ABLATE", 0));
+                                     sel_off, lb_nbins, lb_kbase, lb_first, lb_count, kfr, ira_tune_int("IRA_STFT5_ABLATE", 0),
+                                     tail, tail_off, static_cast<const Stft5Consts*>(consts));
   IRA_RETURN_LAUNCH();
 }

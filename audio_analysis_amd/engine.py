@@ -37,6 +37,7 @@ def _unit_roots(count: int, period: int) -> np.ndarray:
     return np.stack([np.cos(ang), np.sin(ang)], axis=1)
 
 
+TAIL_BLOCK = 512              # IRA_TAIL_BLOCK: samples per block of ira_tail_energy's suffix energies
 LUNDEBY_DOUBLES = 16          # IRA_LUNDEBY_DOUBLES
 LUNDEBY_MAX_BLOCKS = 4096     # IRA_LUNDEBY_MAX_BLOCKS
 LUNDEBY_STAGE = 4096          # samples a workgroup of the two sample passes stages; the largest block size
@@ -191,6 +192,7 @@ class ChannelBatch:
     peak_abs: Optional[np.ndarray] = None   # float32 (B,)
     ready: Optional[object] = None          # event recorded after the batch's arrays were enqueued for upload
     _peak_pending: Optional[tuple] = None   # Engine.peaks_begin(): pinned results + event, picked up by Engine.peaks()
+    _tail: Optional[tuple] = None           # Engine.tail_table(): (key of the starts, table, event, stream it was made on)
 
     @property
     def count(self) -> int:
@@ -1191,15 +1193,83 @@ class Engine:
               "ira_curve_fits")
         return views
 
+    # ------------------------------------------------------------------ suffix energies (quiet tails of the STFT calls)
+    def tail_energy(self, x_dev, start: np.ndarray, end: np.ndarray) -> Dict[str, object]:
+        """Float64 suffix energies (ira_tail_energy) of the segments [start[s], end[s]) of x_dev in blocks of TAIL_BLOCK
+        samples: S[j] = sum of x^2 over [start[s] + j TAIL_BLOCK, end[s]), j <= nblk[s] = ceil((end - start) / TAIL_BLOCK), at
+        off[s] of the returned table.  Returns dict(tab float64 device, off host, off_dev, nblk, start, end)."""
+        t = self.torch
+        start = np.ascontiguousarray(start, dtype=np.int64)
+        end = np.ascontiguousarray(end, dtype=np.int64)
+        n = int(start.size)
+        if end.shape != start.shape or start.ndim != 1 or n > 65535:
+            raise ValueError("start and end must be (nseg,) with nseg <= 65535")
+        if n and (start.min() < 0 or np.any(end < start) or int(end.max()) > int(x_dev.numel())):
+            raise ValueError("every segment must satisfy 0 <= start <= end <= the size of the sample buffer")
+        nblk = -(-(end - start) // TAIL_BLOCK)
+        if n and int(nblk.max()) >= 1 << 31:
+            raise ValueError("segment too long")
+        off = exclusive_cumsum(nblk + 1)
+        tab = self.empty(int((nblk + 1).sum()), t.float64)
+        d_off = None
+        if n:
+            d_start, d_end, d_off = self.job_tables(start, end, off)
+            check(self.lib.ira_tail_energy(_ptr(x_dev), _ptr(d_start), _ptr(d_end), _ptr(d_off), n, int(nblk.max()),
+                                           _ptr(tab), self.stream), "ira_tail_energy")
+        return dict(tab=tab, off=off, off_dev=d_off, nblk=nblk, start=start, end=end)
+
+    def tail_table(self, b: ChannelBatch, starts: np.ndarray) -> Dict[str, object]:
+        """tail_energy of every channel of the batch from sample starts[i] of the channel to its end, computed once per
+        batch and start vector: the blocks of a report step that trim alike (spectrogram, modal cloud) share one pass over
+        the samples.  A block on another stream than the one the table was made on waits for it there."""
+        t = self.torch
+        starts = np.ascontiguousarray(starts, dtype=np.int64)
+        key = starts.tobytes()
+        cur = t.cuda.current_stream(self.device) if self.device.type == "cuda" else None      # (None: a host-side engine)
+        if b._tail is None or b._tail[0] != key:
+            tab = self.tail_energy(b.x, b.off + starts, b.off + b.length)
+            ev = None
+            if cur is not None:
+                ev = t.cuda.Event()
+                ev.record(cur)
+            b._tail = (key, tab, ev, cur)
+            return tab
+        _, tab, ev, made_on = b._tail
+        if cur is not None and cur != made_on:
+            cur.wait_event(ev)
+            for buf in (tab["tab"], tab["off_dev"]):
+                if buf is not None:
+                    buf.record_stream(cur)
+        return tab
+
+    @staticmethod
+    def stft_tail_ok(n_fft: int, precision: int) -> bool:
+        """Configurations whose frame-major / log-bin STFT takes the table of tail_energy (stft6_kernel, stft5_kernel)."""
+        return (int(n_fft), int(precision)) in ((4096, 32), (8192, 64))
+
+    @staticmethod
+    def _tail_args(tail, seg_off: np.ndarray, cols: np.ndarray, n_fft: int, hop: int):
+        """The table's device pointers for an STFT call over the segments at seg_off, after the contract of
+        ira_stft_logbin_tail has been checked on the host: same starts, no frame past the table's end."""
+        if not np.array_equal(np.asarray(tail["start"]), np.asarray(seg_off, dtype=np.int64)):
+            raise ValueError("the suffix-energy table was made for other segment starts")
+        last = np.asarray(seg_off, dtype=np.int64) + (cols.astype(np.int64) - 1) * int(hop) + int(n_fft)
+        if np.any((cols > 0) & (last > np.asarray(tail["end"]))):
+            raise ValueError("a frame reads past the end the suffix-energy table was made for")
+        return tail["tab"], tail["off_dev"]
+
     # ------------------------------------------------------------------ a11
     def stft_mag_db(self, x_dev, seg_off: np.ndarray, nframes: np.ndarray, n_fft: int, hop: int, use_hann: bool,
                     floor_db: float, precision: int = 32, frame_sel: Optional[List[np.ndarray]] = None,
-                    frame_major: bool = False):
+                    frame_major: bool = False, tail=None):
         """
         STFT magnitude (dB) of segments starting at seg_off with nframes[s] valid frames each.
         Returns (out flat f32 device, out_off host int64); out[s] is a C-contiguous (n_fft/2+1, T_s) matrix.
         frame_sel: optional per-segment arrays of frame indices (then T_s = len(frame_sel[s])).
         frame_major=True asks for the transposed (T_s, n_fft/2+1) layout (ira_stft_mag_db_tf; see stft_frame_major_ok).
+        tail: the table of tail_energy for these segments (same starts); the same bytes come back, sooner where the
+        segments end in quiet tails.  Used by the frame-major calls ira_stft_mag_db_tf implements, without a frame
+        selection (stft_tail_ok), ignored by every other.
         """
         t = self.torch
         n = int(seg_off.size)
@@ -1222,17 +1292,25 @@ class Engine:
         out_off = exclusive_cumsum(sizes)
         out = self.empty(int(sizes.sum()), t.float32)
         d_off, d_cols, d_ooff = self.job_tables(seg_off, cols, out_off)
-        fn = self.lib.ira_stft_mag_db_tf if frame_major else self.lib.ira_stft_mag_db
+        use_tail = tail is not None and frame_major and frame_sel is None and self.stft_tail_ok(n_fft, precision) and n > 0
+        name = "ira_stft_mag_db_tf_tail" if use_tail else "ira_stft_mag_db_tf" if frame_major else "ira_stft_mag_db"
+        extra = ()
+        if use_tail:
+            d_tab, d_toff = self._tail_args(tail, seg_off, cols, n_fft, hop)
+            consts = self.empty(1, t.float64)           # IRA_STFT_CONSTS_DOUBLES(0); alive until the call is enqueued
+            extra = (_ptr(d_tab), _ptr(d_toff), _ptr(consts))
         with self.tagged(f"[f{precision},n{n_fft}{',sel' if frame_sel is not None else ''}]"):
-            check(fn(_ptr(x_dev), _ptr(d_off), _ptr(d_cols), n, int(cols.max()) if n else 0, int(n_fft), int(hop),
-                     _ptr(self.window(n_fft, use_hann, precision)), _ptr(self.twiddle(n_fft, precision)), int(precision),
-                     float(floor_db), _ptr(out), _ptr(d_ooff), _ptr(sel), _ptr(sel_off_dev), self.stream),
-                  "ira_stft_mag_db_tf" if frame_major else "ira_stft_mag_db")
+            check(getattr(self.lib, name)(
+                _ptr(x_dev), _ptr(d_off), _ptr(d_cols), n, int(cols.max()) if n else 0, int(n_fft), int(hop),
+                _ptr(self.window(n_fft, use_hann, precision)), _ptr(self.twiddle(n_fft, precision)), int(precision),
+                float(floor_db), _ptr(out), _ptr(d_ooff), _ptr(sel), _ptr(sel_off_dev), *extra, self.stream), name)
         return out, out_off, cols
 
     def stft_logbin(self, x_dev, seg_off: np.ndarray, nframes: np.ndarray, n_fft: int, hop: int, use_hann: bool,
-                    floor_db: float, k_base: int, first: np.ndarray, count: np.ndarray):
-        """Fused float64 STFT + log-bin aggregation (ira_stft_logbin; n_fft 8192): (curves device, curves_off host)."""
+                    floor_db: float, k_base: int, first: np.ndarray, count: np.ndarray, tail=None):
+        """Fused float64 STFT + log-bin aggregation (ira_stft_logbin; n_fft 8192): (curves device, curves_off host).
+        tail: the table of tail_energy for these segments (same starts): the same bytes (ira_stft_logbin_tail), sooner where
+        the segments end in quiet tails."""
         t = self.torch
         n = int(seg_off.size)
         nbins = int(first.size)
@@ -1242,11 +1320,17 @@ class Engine:
         out = self.empty(int(sizes.sum()), t.float32)
         d_off, d_cols, d_ooff, d_f, d_c = self.job_tables(seg_off, cols, out_off, first.astype(np.int32),
                                                            count.astype(np.int32))
+        name, extra = "ira_stft_logbin", ()
+        if tail is not None and n > 0:
+            d_tab, d_toff = self._tail_args(tail, seg_off, cols, n_fft, hop)
+            name = "ira_stft_logbin_tail"
+            consts = self.empty(1 + (nbins + 1) // 2, t.float64)   # IRA_STFT_CONSTS_DOUBLES; alive until the call is enqueued
+            extra = (_ptr(d_tab), _ptr(d_toff), _ptr(consts))
         with self.tagged(f"[f64,n{n_fft}]"):
-            check(self.lib.ira_stft_logbin(_ptr(x_dev), _ptr(d_off), _ptr(d_cols), n, int(cols.max()) if n else 0,
-                                           int(n_fft), int(hop), _ptr(self.window(n_fft, use_hann, 64)),
-                                           _ptr(self.twiddle(n_fft, 64)), 64, float(floor_db), int(k_base), _ptr(d_f),
-                                           _ptr(d_c), nbins, _ptr(out), _ptr(d_ooff), self.stream), "ira_stft_logbin")
+            check(getattr(self.lib, name)(_ptr(x_dev), _ptr(d_off), _ptr(d_cols), n, int(cols.max()) if n else 0,
+                                          int(n_fft), int(hop), _ptr(self.window(n_fft, use_hann, 64)),
+                                          _ptr(self.twiddle(n_fft, 64)), 64, float(floor_db), int(k_base), _ptr(d_f),
+                                          _ptr(d_c), nbins, _ptr(out), _ptr(d_ooff), *extra, self.stream), name)
         return out, out_off
 
     @staticmethod

@@ -165,6 +165,41 @@ int32_t ira_stft_logbin(const float* x_dev, const int64_t* off_dev, const int32_
                         const int32_t* first_dev, const int32_t* count_dev, int32_t nbins, float* curves_dev,
                         const int64_t* curves_off_dev, void* stream);
 
+/* ---- suffix energies, and the two STFT calls above certified from them ---------------------------------------------
+ * ira_tail_energy: per segment s the float64 table S at tab_dev + tab_off[s], nblk[s] + 1 doubles with
+ * nblk[s] = ceil((end[s] - start[s]) / IRA_TAIL_BLOCK):
+ *   S[j] = sum of x[n]^2 over n in [start[s] + j IRA_TAIL_BLOCK, end[s]),  S[nblk[s]] = 0
+ * (start / end: sample indices into x_dev; end is where the segment's channel ends, nothing is read at or past it).
+ * Exact squares added in a fixed order: the same inputs give the same bits in every run.  A NaN or an infinity makes every
+ * entry at or before its block non-finite and leaves the entries behind it alone.  max_nblk = the largest nblk[s] (sizes
+ * the grid); nseg <= 65535.  Nothing in the reference computes this table: it exists for the two calls below. */
+#define IRA_TAIL_BLOCK 512
+int32_t ira_tail_energy(const float* x_dev, const int64_t* start_dev, const int64_t* end_dev,
+                        const int64_t* tab_off_dev, int32_t nseg, int32_t max_nblk, double* tab_dev, void* stream);
+
+/* ira_stft_logbin / ira_stft_mag_db_tf (their configurations) with the table of ira_tail_energy: THE SAME BYTES as the
+ * call without it.  A frame (precision 32) or a workgroup's run of frames (precision 64) that starts in block j of its
+ * segment reads only samples S[j] covers, so 4 n_fft max(window^2) S[j] <= floor^2 certifies that it is floored on every
+ * row, with one load and no sample traffic; nothing is certified from a non-finite entry.
+ * CONTRACT: tail_dev / tail_off_dev are the table and offsets of an ira_tail_energy call whose start[s] == off[s] for
+ * every segment, and no frame of segment s reads at or past that call's end[s].  tail_dev == NULL: exactly the call
+ * without the table.  With a frame selection the table is ignored.
+ * consts_dev: scratch the precision-64 call fills for itself (the window's greatest square and the floored log-bin row),
+ * IRA_STFT_CONSTS_DOUBLES(nbins) doubles (nbins = 0 for ira_stft_mag_db_tf_tail); required with a table there. */
+#define IRA_STFT_CONSTS_DOUBLES(nbins) (1 + ((nbins) + 1) / 2)
+int32_t ira_stft_logbin_tail(const float* x_dev, const int64_t* off_dev, const int32_t* nframes_dev, int32_t nseg,
+                             int32_t max_frames, int32_t n_fft, int32_t hop, const void* window_dev,
+                             const void* twiddle_dev, int32_t precision, double floor_db, int32_t k_base,
+                             const int32_t* first_dev, const int32_t* count_dev, int32_t nbins, float* curves_dev,
+                             const int64_t* curves_off_dev, const double* tail_dev, const int64_t* tail_off_dev,
+                             void* consts_dev, void* stream);
+int32_t ira_stft_mag_db_tf_tail(const float* x_dev, const int64_t* off_dev, const int32_t* nframes_dev,
+                                int32_t nseg, int32_t max_frames, int32_t n_fft, int32_t hop,
+                                const void* window_dev, const void* twiddle_dev, int32_t precision,
+                                double floor_db, float* out_dev, const int64_t* out_off_dev,
+                                const int32_t* frame_sel_dev, const int64_t* sel_off_dev, const double* tail_dev,
+                                const int64_t* tail_off_dev, void* consts_dev, void* stream);
+
 /* ---- a9/a17: arbitrary-length float64 DFTs (Bluestein over a four-step FFT of size M) -------------------
  * Common arguments: the convolution size m = M, a power of two (16 <= M <= 2^22) or three times one
  * (96 <= M <= 3*2^20), with M >= 2*max(L) - 1 -- or only M >= L + L/2 for ira_rfft_any elements that carry ONE real
