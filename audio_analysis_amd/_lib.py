@@ -105,6 +105,8 @@ PROTOTYPES = {
                               vp, C.c_int64, vp, vp, vp]),
     "ira_xspec_accumulate": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp]),
     "ira_xspec_finish": (i32, [vp, vp, i32, i32, i32, i32, vp, vp]),
+    "ira_fdw_scratch_doubles": (C.c_int64, [i32, C.POINTER(i32), i32]),
+    "ira_fdw_response": (i32, [vp, vp, vp, vp, i32, C.POINTER(f64), C.POINTER(i32), vp, vp, i32, i32, vp, C.c_int64, vp, vp]),
 }
 
 

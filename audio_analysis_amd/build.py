@@ -65,6 +65,9 @@ SOURCES = {
     # cross-spectral sums are compared to a derived bound only (FMAs wanted in the transform); the finish kernel, whose
     # quotients are held to a few ulp, turns contraction off for itself
     "ira_xspec.hip": [],
+    # the turn count k rho is reduced from its rounded product and that product's error, which a contraction would merge;
+    # the sums call fma themselves and are held to a derived bound, not to bits
+    "ira_fdw.hip": ["-ffp-contract=off"],
 }
 COMMON = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function"]
 

@@ -72,6 +72,13 @@ REFL_UNBOUNDED = 1 << 40      # a Tn from here on is no bound (REFL_UNBOUNDED of
 XSPEC_FRAMES = 16             # IRA_XSPEC_FRAMES: frames a workgroup of ira_xspec_accumulate sums before it writes
 XSPEC_ROWS = 11               # IRA_XSPEC_ROWS
 XSPEC_MIN_FFT, XSPEC_MAX_FFT = 256, 8192
+FDW_FIELDS = 6                # IRA_FDW_FIELDS
+FDW_SUMS = 5                  # IRA_FDW_SUMS
+FDW_MAX_POINTS = 4096         # IRA_FDW_MAX_POINTS
+FDW_MAX_HALF = 1 << 20        # IRA_FDW_MAX_HALF
+FDW_CHUNK = 4096              # IRA_FDW_CHUNK: terms of a wide point a workgroup of ira_fdw_response sums
+FDW_NARROW_HALF = 127         # IRA_FDW_NARROW_HALF: up to here one wavefront takes the point
+FDW_WINDOWS = ("hann", "rect")
 
 
 def xspec_frames(n, n_fft: int, hop: int) -> np.ndarray:
@@ -120,6 +127,22 @@ def refl_scratch_doubles(nch: int, max_room: int, separation: int) -> int:
     """Doubles of scratch ira_reflections needs: per channel and tile of the longest row a count and 4 doubles per
     candidate the tile can hold (the geometry of ira_reflections.hip restated; the call checks it)."""
     return int(nch) * (-(-int(max_room) // REFL_TILE)) * (1 + 4 * refl_tile_candidates(separation))
+
+
+def fdw_chunks(half) -> np.ndarray:
+    """Chunks of FDW_CHUNK terms of each point: ceil((2 H + 1) / FDW_CHUNK) for a wide point, 0 for a narrow one (H <=
+    FDW_NARROW_HALF), which one wavefront sums without a partial (int64, elementwise)."""
+    half = np.asarray(half, dtype=np.int64)
+    return np.where(half > FDW_NARROW_HALF, -(-(2 * half + 1) // FDW_CHUNK), 0).astype(np.int64)
+
+
+def fdw_scratch_doubles(nch: int, half) -> int:
+    """Doubles of scratch ira_fdw_response needs (ira_fdw_scratch_doubles restated; the call checks it): FDW_SUMS per
+    channel and chunk, then the int32 tables the plan launch builds (first chunk of each point and the total, the point
+    of each chunk, the narrow points)."""
+    chunks = fdw_chunks(half)
+    total, narrow, npts = int(chunks.sum()), int(np.count_nonzero(chunks == 0)), int(chunks.size)
+    return int(nch) * total * FDW_SUMS + (npts + 1 + total + narrow + 1) // 2
 
 
 def lundeby_layout(base_off, base_len, chan_of_seg, blk_size, nblk, first_m) -> Dict[str, object]:
@@ -881,6 +904,49 @@ class Engine:
                                        _ptr(rec), self.stream), "ira_reflections")
         return (erow[:total], erow_off, lst[: nch * keep * REFL_FIELDS].view(nch, keep, REFL_FIELDS),
                 rec[: nch * REFL_DOUBLES].view(nch, REFL_DOUBLES))
+
+    # ------------------------------------------------------------------ frequency-dependent-window response
+    def fdw_response(self, x_dev, off: np.ndarray, length: np.ndarray, centre_dev, rho: np.ndarray, half: np.ndarray,
+                     window: str):
+        """Windowed Fourier sums around a centre sample, one window length per frequency point (ira_fdw_response, one
+        call).  Channel c: length[c] samples at off[c] of x_dev, centred at centre_dev[c] (int64 device, read on the
+        device; it may lie outside the channel); point j: rho[j] = f_j / fs in (0, 0.5] and the half width half[j] >= 1
+        samples (terms k = -half .. half); window "hann" or "rect".  Returns (nch, J, FDW_FIELDS) float64 device: Re S0,
+        Im S0, Re S1, Im S1, A = sum |v|, N = the terms inside the channel."""
+        t = self.torch
+        off = np.ascontiguousarray(off, dtype=np.int64).reshape(-1)
+        length = np.ascontiguousarray(length, dtype=np.int64).reshape(-1)
+        rho = np.ascontiguousarray(rho, dtype=np.float64).reshape(-1)
+        half_in = np.asarray(half).reshape(-1)
+        nch, npts = int(off.size), int(rho.size)
+        if length.size != nch:
+            raise ValueError("off and length must be (nch,)")
+        if nch > 65535:
+            raise ValueError("at most 65535 channels per launch")
+        if half_in.size != npts:
+            raise ValueError("rho and half must be (J,)")
+        if npts > FDW_MAX_POINTS:
+            raise ValueError(f"at most {FDW_MAX_POINTS} frequency points, got {npts}")
+        if window not in FDW_WINDOWS:
+            raise ValueError(f"window must be one of {FDW_WINDOWS}, got {window!r}")
+        if npts and not (np.all(np.isfinite(rho)) and np.all(rho > 0.0) and np.all(rho <= 0.5)):
+            raise ValueError("rho must be finite and in (0, 0.5]")
+        if npts and not (np.all(half_in == np.rint(half_in)) and np.all(half_in >= 1) and np.all(half_in <= FDW_MAX_HALF)):
+            raise ValueError(f"half must be whole numbers 1..{FDW_MAX_HALF}")
+        half = np.ascontiguousarray(half_in, dtype=np.int32)
+        if nch == 0 or npts == 0:                                   # nothing to launch (zero-size tables have no address)
+            return self.empty(0, t.float64)[:0].view(nch, npts, FDW_FIELDS)
+        scratch_doubles = fdw_scratch_doubles(nch, half)
+        scratch = self.empty(scratch_doubles, t.float64)
+        out = self.empty(nch * npts * FDW_FIELDS, t.float64)
+        d_off, d_len, d_rho, d_half = self.job_tables(off, length, rho, half)
+        c_rho = (_lib.f64 * npts)(*rho.tolist())
+        c_half = (_lib.i32 * npts)(*half.tolist())
+        with self.tagged(f"[{window}]"):
+            check(self.lib.ira_fdw_response(_ptr(x_dev), _ptr(d_off), _ptr(d_len), _ptr(centre_dev), nch, c_rho, c_half,
+                                            _ptr(d_rho), _ptr(d_half), npts, FDW_WINDOWS.index(window), _ptr(scratch),
+                                            scratch_doubles, _ptr(out), self.stream), "ira_fdw_response")
+        return out[: nch * npts * FDW_FIELDS].view(nch, npts, FDW_FIELDS)
 
     # ------------------------------------------------------------------ dual-channel spectral sums (Welch H1 / H2)
     def cross_spectra(self, x_dev, x_off: np.ndarray, y_off: np.ndarray, n: np.ndarray, n_fft: int, hop: int,

@@ -929,6 +929,51 @@ int32_t ira_reflections(const float* x_dev, const int64_t* off_dev, const int64_
                         double* erow_dev, const int64_t* erow_off_dev, double* scratch_dev, int64_t scratch_doubles,
                         double* list_dev, double* rec_dev, void* stream);
 
+/* ---- Frequency-dependent-window (FDW) response: one windowed Fourier sum per frequency point, window of N cycles ----------
+ * Nothing in the reference computes it; the entry points replace no reference function.  Host side, with the definition
+ * pinned: audio_analysis_amd/analyse/fdw.py (`python -m analyse.fdw`).
+ * ira_fdw_response: channel c is len_dev[c] float32 samples at x_dev + off_dev[c]; its centre p = centre_dev[c] (int64) is
+ *   read on the device and may lie outside the channel.  Point j < npts has rho[j] = f_j / fs (float64, 0 < rho <= 0.5) and
+ *   a half width half[j] = H >= 1 samples, the same for every channel.  Terms k = -H .. H, i = p + k; a term with i outside
+ *   [0, len) contributes nothing and is not read.
+ *     weight   window 0 (hann): w(k) = 0.5 + 0.5 cospi(k / (H + 1)), formed as sinpi((H + 1 - |k|) / (2 H + 2))^2, the
+ *              same function without the cancellation at the window's ends (> 0 on every term, 1 at the centre);
+ *              window 1 (rect): w = 1
+ *     phasor   t_hi = k * rho, t_lo = fma(k, rho, -t_hi), r = (t_hi - rint(t_hi)) + t_lo (the turn count reduced exactly),
+ *              e^{-2 pi i r} from sincospi(2 r)
+ *     v = w(k) * float64(x[i]);  S0 = sum v e^{-2 pi i r};  S1 = sum k v e^{-2 pi i r};  A = sum |v|;  N = the number of
+ *     terms inside the channel.
+ *   out_dev[(c * npts + j) * IRA_FDW_FIELDS + ..], float64: [0] Re S0  [1] Im S0  [2] Re S1  [3] Im S1  [4] A  [5] N.
+ *   N = 0 gives zeros.  Non-finite samples propagate by arithmetic alone: a NaN or an infinity inside a point's window
+ *   makes that point's sums non-finite and no other point's.
+ *   rho and half are HOST arrays, checked before anything is launched; rho_dev and half_dev are the same values on the
+ *   device (the kernels read them there: this is the one argument pair more than a host-only table would need, the
+ *   library copies nothing itself).  Checked (IRA_E_NULL / IRA_E_SIZE): nch 0..65535, npts 0..IRA_FDW_MAX_POINTS, every
+ *   half 1..IRA_FDW_MAX_HALF, every rho finite and in (0, 0.5], window 0 or 1, scratch_doubles >=
+ *   ira_fdw_scratch_doubles(nch, half, npts).  nch = 0 or npts = 0: IRA_OK, no launch.
+ *   A point with H <= IRA_FDW_NARROW_HALF (at most 255 terms) is NARROW: one wavefront takes it, four points per
+ *   workgroup, lane l adds the terms l, l + 64, .. in ascending order and the lanes are added by a butterfly.  Any other
+ *   point is WIDE: it is cut into ceil((2 H + 1) / IRA_FDW_CHUNK) chunks of IRA_FDW_CHUNK consecutive terms, a workgroup
+ *   of 256 threads takes one (chunk, channel), thread t adds the terms t, t + 256, .. of the chunk in ascending order,
+ *   lanes by a butterfly, the four waves in ascending order; the chunk's five sums go to scratch with plain stores and a
+ *   finishing launch adds a point's chunks in ascending order.  The job tables (chunk -> point, first chunk of a point,
+ *   the narrow points) are built on the device from half_dev by a one-workgroup launch into the tail of scratch.
+ *   Four launches, no atomics; the sums of a (channel, point) are a function of that channel's samples, p, rho, H and
+ *   the window alone and run in one fixed order: bit-identical whatever the batch or the channel's place in it.
+ * ira_fdw_scratch_doubles: nch * T * IRA_FDW_SUMS + (npts + 1 + T + M + 1) / 2 doubles, T the chunks of the wide points and M
+ *   the number of narrow points (the second term holds the int32 tables); IRA_E_NULL / IRA_E_SIZE (negative) as above. */
+#define IRA_FDW_FIELDS 6
+#define IRA_FDW_SUMS 5             /* Re S0, Im S0, Re S1, Im S1, A of a chunk; N needs no sum */
+#define IRA_FDW_MAX_POINTS 4096
+#define IRA_FDW_MAX_HALF (1 << 20)
+#define IRA_FDW_CHUNK 4096         /* terms per partial sum: a constant, never sized from the batch or the device */
+#define IRA_FDW_NARROW_HALF 127    /* 2 H + 1 <= 255 terms: one wavefront per point */
+int64_t ira_fdw_scratch_doubles(int32_t nch, const int32_t* half, int32_t npts);
+int32_t ira_fdw_response(const float* x_dev, const int64_t* off_dev, const int64_t* len_dev, const int64_t* centre_dev,
+                         int32_t nch, const double* rho, const int32_t* half, const double* rho_dev,
+                         const int32_t* half_dev, int32_t npts, int32_t window, double* scratch_dev,
+                         int64_t scratch_doubles, double* out_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
