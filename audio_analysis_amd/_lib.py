@@ -107,6 +107,9 @@ PROTOTYPES = {
     "ira_xspec_finish": (i32, [vp, vp, i32, i32, i32, i32, vp, vp]),
     "ira_fdw_scratch_doubles": (C.c_int64, [i32, C.POINTER(i32), i32]),
     "ira_fdw_response": (i32, [vp, vp, vp, vp, i32, C.POINTER(f64), C.POINTER(i32), vp, vp, i32, i32, vp, C.c_int64, vp, vp]),
+    "ira_burst_table_doubles": (C.c_int64, [C.POINTER(i32), i32]),
+    "ira_burst_table": (i32, [C.POINTER(f64), C.POINTER(i32), vp, vp, vp, i32, i32, vp, C.c_int64, vp]),
+    "ira_burst_decay": (i32, [vp, vp, vp, vp, i32, C.POINTER(i32), vp, vp, vp, C.c_int64, C.POINTER(i32), vp, i32, i32, vp, vp]),
 }
 
 

@@ -68,6 +68,9 @@ SOURCES = {
     # the turn count k rho is reduced from its rounded product and that product's error, which a contraction would merge;
     # the sums call fma themselves and are held to a derived bound, not to bits
     "ira_fdw.hip": ["-ffp-contract=off"],
+    # the wavelet table repeats ira_fdw.hip's weight and phasor term for term (the same split of k rho); the map's sums
+    # call fma themselves
+    "ira_burstdecay.hip": ["-ffp-contract=off"],
 }
 COMMON = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function"]
 

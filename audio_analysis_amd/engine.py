@@ -79,6 +79,12 @@ FDW_MAX_HALF = 1 << 20        # IRA_FDW_MAX_HALF
 FDW_CHUNK = 4096              # IRA_FDW_CHUNK: terms of a wide point a workgroup of ira_fdw_response sums
 FDW_NARROW_HALF = 127         # IRA_FDW_NARROW_HALF: up to here one wavefront takes the point
 FDW_WINDOWS = ("hann", "rect")
+BURST_STEPS = 8               # IRA_BURST_STEPS: steps of a point a wavefront of ira_burst_decay serves from one walk
+BURST_LANES = 64              # IRA_BURST_LANES: terms per round of that walk, one a lane
+BURST_CHANNELS = 4            # IRA_BURST_CHANNELS: channels (waves) per workgroup
+BURST_MAX_STEPS = 4096        # IRA_BURST_MAX_STEPS
+BURST_MAX_DELTA = 1 << 24     # IRA_BURST_MAX_DELTA: the largest |delta| in samples
+BURST_MAX_OUT_BYTES = 256 << 20  # Engine.burst_decay: one ira_burst_decay call writes at most this (the default map of 256 channels is 60 MB)
 
 
 def xspec_frames(n, n_fft: int, hop: int) -> np.ndarray:
@@ -145,6 +151,26 @@ def fdw_scratch_doubles(nch: int, half) -> int:
     return int(nch) * total * FDW_SUMS + (npts + 1 + total + narrow + 1) // 2
 
 
+def burst_table_offsets(half) -> np.ndarray:
+    """tab_off[j], the first entry of point j in the wavelet table of ira_burst_table: the points' 2 H + 1 entries lie one
+    after the other (int64, exclusive running sum)."""
+    half = np.asarray(half, dtype=np.int64).reshape(-1)
+    return exclusive_cumsum(2 * half + 1).astype(np.int64)
+
+
+def burst_table_doubles(half) -> int:
+    """Doubles of the wavelet table (ira_burst_table_doubles restated; both calls check it): (re, im) per entry, 2 H + 1
+    entries per point."""
+    half = np.asarray(half, dtype=np.int64).reshape(-1)
+    return 2 * int(np.sum(2 * half + 1))
+
+
+def burst_channels_per_call(npts: int, nsteps: int) -> int:
+    """Channels one ira_burst_decay call of Engine.burst_decay takes: as many as keep its output of 16 bytes per (channel,
+    point, step) within BURST_MAX_OUT_BYTES, at least one, at most the 65535 of a launch."""
+    return int(max(1, min(65535, BURST_MAX_OUT_BYTES // max(1, 16 * int(npts) * int(nsteps)))))
+
+
 def lundeby_layout(base_off, base_len, chan_of_seg, blk_size, nblk, first_m) -> Dict[str, object]:
     """Host side of the Lundeby row tables (pure NumPy): the tables in the kernels' types, every row's table offset
     blk_off = j * (max nb + 1), table_doubles = nseg * (max nb + 1) (what ira_lundeby_scratch_doubles answers) and
@@ -201,6 +227,20 @@ def multislope_jobs(jobs, width: int, nseg: int, ngrids: int, nslots: int, max_g
             if jobs[:, col].min() < lo or jobs[:, col].max() >= hi:
                 raise ValueError(f"column {col} of the job table must lie in [{lo}, {hi})")
     return jobs
+
+
+@dataclass
+class BurstTable:
+    """What Engine.burst_table leaves on the device for Engine.burst_decay: the wavelets of every point, one after the
+    other, and the tables the map kernel reads beside them."""
+    rho: np.ndarray              # float64 (J,) host
+    half: np.ndarray             # int32 (J,) host
+    window: str
+    offsets: np.ndarray          # int64 (J,) host: burst_table_offsets(half)
+    doubles: int                 # burst_table_doubles(half)
+    table: "object"              # torch.float64 (doubles,) on device: (re, im) per entry
+    half_dev: "object"
+    offsets_dev: "object"
 
 
 @dataclass
@@ -947,6 +987,79 @@ class Engine:
                                             _ptr(d_rho), _ptr(d_half), npts, FDW_WINDOWS.index(window), _ptr(scratch),
                                             scratch_doubles, _ptr(out), self.stream), "ira_fdw_response")
         return out[: nch * npts * FDW_FIELDS].view(nch, npts, FDW_FIELDS)
+
+    # ------------------------------------------------------------------ burst decay (constant-Q level-over-periods map)
+    def burst_table(self, rho: np.ndarray, half: np.ndarray, window: str) -> BurstTable:
+        """The wavelets g_j(k) = w(k) e^{-2 pi i k rho_j}, k = -half[j] .. half[j], of every point as (re, im) doubles, one
+        point after the other (ira_burst_table, one call): weight and phasor exactly as ira_fdw_response forms them.  rho[j]
+        in (0, 0.5], half[j] >= 1 samples, window "hann" or "rect"."""
+        t = self.torch
+        rho = np.ascontiguousarray(rho, dtype=np.float64).reshape(-1)
+        half_in = np.asarray(half).reshape(-1)
+        npts = int(rho.size)
+        if half_in.size != npts:
+            raise ValueError("rho and half must be (J,)")
+        if npts > FDW_MAX_POINTS:
+            raise ValueError(f"at most {FDW_MAX_POINTS} frequency points, got {npts}")
+        if window not in FDW_WINDOWS:
+            raise ValueError(f"window must be one of {FDW_WINDOWS}, got {window!r}")
+        if npts and not (np.all(np.isfinite(rho)) and np.all(rho > 0.0) and np.all(rho <= 0.5)):
+            raise ValueError("rho must be finite and in (0, 0.5]")
+        if npts and not (np.all(half_in == np.rint(half_in)) and np.all(half_in >= 1) and np.all(half_in <= FDW_MAX_HALF)):
+            raise ValueError(f"half must be whole numbers 1..{FDW_MAX_HALF}")
+        half = np.ascontiguousarray(half_in, dtype=np.int32)
+        offsets, doubles = burst_table_offsets(half), burst_table_doubles(half)
+        if npts == 0:                                               # nothing to launch (zero-size tables have no address)
+            return BurstTable(rho, half, window, offsets, 0, None, None, None)
+        table = self.empty(doubles, t.float64)
+        d_rho, d_half, d_off = self.job_tables(rho, half, offsets)
+        c_rho = (_lib.f64 * npts)(*rho.tolist())
+        c_half = (_lib.i32 * npts)(*half.tolist())
+        with self.tagged(f"[{window}]"):
+            check(self.lib.ira_burst_table(c_rho, c_half, _ptr(d_rho), _ptr(d_half), _ptr(d_off), npts,
+                                           FDW_WINDOWS.index(window), _ptr(table), doubles, self.stream), "ira_burst_table")
+        return BurstTable(rho, half, window, offsets, doubles, table, d_half, d_off)
+
+    def burst_decay(self, x_dev, off: np.ndarray, length: np.ndarray, centre_dev, table: BurstTable, delta: np.ndarray) -> List:
+        """The map S[c, j, m] = sum over k of g_j(k) * x_c[centre_c + delta[j, m] + k] (ira_burst_decay).  Channel c:
+        length[c] samples at off[c] of x_dev, centred at centre_dev[c] (int64 device, read on the device); table from
+        burst_table; delta (J, M) whole samples, non-decreasing along m, |delta| <= BURST_MAX_DELTA.  The batch is cut into
+        calls of burst_channels_per_call(J, M) channels, so that one call writes at most BURST_MAX_OUT_BYTES.  Returns the
+        list of the calls' outputs in channel order: (channels of the call, J, M, 2) float64 device, (Re S, Im S)."""
+        t = self.torch
+        off = np.ascontiguousarray(off, dtype=np.int64).reshape(-1)
+        length = np.ascontiguousarray(length, dtype=np.int64).reshape(-1)
+        nch, npts = int(off.size), int(table.half.size)
+        if length.size != nch:
+            raise ValueError("off and length must be (nch,)")
+        delta_in = np.asarray(delta)
+        if delta_in.ndim != 2 or delta_in.shape[0] != npts:
+            raise ValueError("delta must be (J, M)")
+        nsteps = int(delta_in.shape[1])
+        if nsteps > BURST_MAX_STEPS:
+            raise ValueError(f"at most {BURST_MAX_STEPS} steps, got {nsteps}")
+        if delta_in.size and not (np.all(delta_in == np.rint(delta_in)) and np.all(np.abs(delta_in) <= BURST_MAX_DELTA)):
+            raise ValueError(f"delta must be whole numbers of at most {BURST_MAX_DELTA} samples either way")
+        if delta_in.size and np.any(np.diff(delta_in, axis=1) < 0):
+            raise ValueError("delta must not decrease along the steps")
+        delta = np.ascontiguousarray(delta_in, dtype=np.int32)
+        if nch == 0 or npts == 0 or nsteps == 0:                    # nothing to launch
+            return [self.empty(0, t.float64)[:0].view(nch, npts, nsteps, 2)]
+        per_call = burst_channels_per_call(npts, nsteps)
+        d_off, d_len, d_delta = self.job_tables(off, length, delta.reshape(-1))
+        c_half = (_lib.i32 * npts)(*table.half.tolist())
+        c_delta = (_lib.i32 * delta.size)(*delta.reshape(-1).tolist())
+        outs = []
+        with self.tagged(f"[{table.window}]"):
+            for a in range(0, nch, per_call):
+                n = min(per_call, nch - a)
+                out = self.empty(n * npts * nsteps * 2, t.float64)
+                check(self.lib.ira_burst_decay(_ptr(x_dev), _ptr(d_off[a:]), _ptr(d_len[a:]), _ptr(centre_dev[a:]), n, c_half,
+                                               _ptr(table.half_dev), _ptr(table.offsets_dev), _ptr(table.table), table.doubles,
+                                               c_delta, _ptr(d_delta), npts, nsteps, _ptr(out), self.stream),
+                      "ira_burst_decay")
+                outs.append(out[: n * npts * nsteps * 2].view(n, npts, nsteps, 2))
+        return outs
 
     # ------------------------------------------------------------------ dual-channel spectral sums (Welch H1 / H2)
     def cross_spectra(self, x_dev, x_off: np.ndarray, y_off: np.ndarray, n: np.ndarray, n_fft: int, hop: int,

@@ -974,6 +974,65 @@ int32_t ira_fdw_response(const float* x_dev, const int64_t* off_dev, const int64
                          const int32_t* half_dev, int32_t npts, int32_t window, double* scratch_dev,
                          int64_t scratch_doubles, double* out_dev, void* stream);
 
+/* ---- Burst decay: a constant-Q level-over-periods map, one windowed Fourier sum per (channel, point, step) -----------------
+ * Nothing in the reference computes it; the entry points replace no reference function.  Host side, with the definition
+ * pinned: audio_analysis_amd/analyse/burstdecay.py (`python -m analyse.burstdecay`).
+ * Point j < npts has rho[j] = f_j / fs (float64, 0 < rho <= 0.5) and a half width half[j] = H >= 1 samples, as for
+ * ira_fdw_response.  Its WAVELET is g_j(k) = w(k) e^{-2 pi i r(k)}, k = -H .. H, with w and r formed exactly as stated there:
+ *     weight   window 0 (hann): w(k) = sinpi((H + 1 - |k|) / (2 H + 2))^2;  window 1 (rect): w = 1
+ *     phasor   t_hi = k * rho, t_lo = fma(k, rho, -t_hi), r = (t_hi - rint(t_hi)) + t_lo, (sn, cs) from sincospi(2 r)
+ *     g_j(k) = (w * cs, -(w * sn))
+ * ira_burst_table: writes g_j(k) as (re, im) doubles at table_dev[2 * (tab_off[j] + k + H)], tab_off[j] (int64, read from
+ *   tab_off_dev) the first entry of point j.  Every entry is a function of (rho_j, H_j, window, k) alone; one thread per
+ *   entry, one launch.  rho and half are HOST arrays, checked before anything is launched, rho_dev and half_dev the same
+ *   values on the device (the library copies nothing itself).  Checked (IRA_E_NULL / IRA_E_SIZE): npts
+ *   0..IRA_FDW_MAX_POINTS, every half 1..IRA_FDW_MAX_HALF, every rho finite and in (0, 0.5], window 0 or 1, table_doubles
+ *   >= ira_burst_table_doubles(half, npts).  A point whose entries tab_off[j] .. tab_off[j] + 2 H would leave the
+ *   table_doubles / 2 entries is not written.  npts = 0: IRA_OK, no launch.
+ * ira_burst_decay: channel c is len_dev[c] float32 samples at x_dev + off_dev[c]; its centre p = centre_dev[c] (int64) is
+ *   read on the device and may lie outside the channel.  Step m < nsteps of point j is centred on c = p + delta[j * nsteps
+ *   + m] (int32):
+ *     S[j, m] = sum over k = -H .. H of g_j(k) * float64(x[c + k]);  a term with c + k outside [0, len) contributes nothing
+ *     and is not read.  The phase is relative to the cell's own centre.
+ *   out_dev[((c * npts + j) * nsteps + m) * 2 + {0, 1}] = Re S, Im S, float64.  A cell with nothing inside is (0, 0).
+ *   Non-finite samples propagate by arithmetic alone: a NaN or an infinity inside a cell's window makes that cell
+ *   non-finite and no other.
+ *   ONE ORDER, of a cell's terms u = k + H = 0 .. 2 H: lane l < IRA_BURST_LANES adds the terms u = l, l + 64, l + 128, ..
+ *   in ascending order from (0, 0) by re = fma(Re g, x, re), im = fma(Im g, x, im); the 64 lane sums are then added in
+ *   ascending lane order, starting from lane 0's.  A term outside the channel is skipped or enters as x = +0.0, which are
+ *   the same bits (no sum here can be -0.0).  The order depends on H and k alone: a cell's bits are a function of the
+ *   channel's samples, p, delta[j, m], H, rho and the window only -- identical whatever the batch, the channel's place
+ *   or alignment in it, and whichever other points and steps the call carries.
+ *   Tiling (no value depends on it): one wavefront takes IRA_BURST_STEPS consecutive steps of one (channel, point) and
+ *   walks the window once, a ROUND of IRA_BURST_LANES consecutive terms at a time: g_j of the round is loaded once (16
+ *   bytes a lane) and serves every step of the tile, whose samples are IRA_BURST_STEPS loads of 64 consecutive floats.
+ *   Rounds in which every step of the tile lies inside its channel run without a test; the others compare u with each
+ *   step's first and last term inside.  The lane sums meet in LDS (pitch IRA_BURST_LANES + 1 doubles).  A workgroup is
+ *   IRA_BURST_CHANNELS waves: consecutive channels of the same (point, step tile), which walk the same wavelet at the
+ *   same time; the workgroups are numbered so that one XCD takes consecutive tiles and points of the same channels,
+ *   whose samples overlap, and finds them in its L2.  One launch, no atomics, no scratch.
+ *   half and delta are HOST arrays, checked before anything is launched; half_dev, delta_dev the same values on the
+ *   device.  Checked (IRA_E_NULL / IRA_E_SIZE): nch 0..65535, npts 0..IRA_FDW_MAX_POINTS, nsteps 0..IRA_BURST_MAX_STEPS,
+ *   every half 1..IRA_FDW_MAX_HALF, |delta| <= IRA_BURST_MAX_DELTA and delta non-decreasing in m for every j,
+ *   table_doubles >= ira_burst_table_doubles(half, npts).  The device's own copies are clamped to the same ranges and a
+ *   point whose tab_off would leave the table gives NaN cells, so no access leaves x's channels, table_dev or out_dev
+ *   even if the device arrays do not hold the host's values.  nch, npts or nsteps = 0: IRA_OK, no launch.
+ * ira_burst_table_doubles (host only): 2 * sum over j of (2 half[j] + 1), the doubles of the wavelet table -- the only
+ *   workspace the two calls share; IRA_E_NULL / IRA_E_SIZE (negative) as above. */
+#define IRA_BURST_STEPS 8          /* steps of a point a wavefront serves from one walk over the wavelet */
+#define IRA_BURST_LANES 64         /* terms per round, one a lane: constants, never sized from the batch or the device */
+#define IRA_BURST_CHANNELS 4       /* waves, i.e. channels, per workgroup */
+#define IRA_BURST_MAX_STEPS 4096
+#define IRA_BURST_MAX_DELTA (1 << 24)
+int64_t ira_burst_table_doubles(const int32_t* half, int32_t npts);
+int32_t ira_burst_table(const double* rho, const int32_t* half, const double* rho_dev, const int32_t* half_dev,
+                        const int64_t* tab_off_dev, int32_t npts, int32_t window, double* table_dev, int64_t table_doubles,
+                        void* stream);
+int32_t ira_burst_decay(const float* x_dev, const int64_t* off_dev, const int64_t* len_dev, const int64_t* centre_dev,
+                        int32_t nch, const int32_t* half, const int32_t* half_dev, const int64_t* tab_off_dev,
+                        const double* table_dev, int64_t table_doubles, const int32_t* delta, const int32_t* delta_dev,
+                        int32_t npts, int32_t nsteps, double* out_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
