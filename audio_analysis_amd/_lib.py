@@ -110,6 +110,10 @@ PROTOTYPES = {
     "ira_burst_table_doubles": (C.c_int64, [C.POINTER(i32), i32]),
     "ira_burst_table": (i32, [C.POINTER(f64), C.POINTER(i32), vp, vp, vp, i32, i32, vp, C.c_int64, vp]),
     "ira_burst_decay": (i32, [vp, vp, vp, vp, i32, C.POINTER(i32), vp, vp, vp, C.c_int64, C.POINTER(i32), vp, i32, i32, vp, vp]),
+    "ira_minphase_logmag": (i32, [vp, vp, vp, i32, i32, f64, vp, vp, vp, vp]),
+    "ira_minphase_excess": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, vp, vp]),
+    "ira_minphase_gather": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp]),
+    "ira_minphase_spectrum": (i32, [vp, vp, vp, vp, vp, i32, i32, vp]),
 }
 
 

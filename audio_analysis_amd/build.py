@@ -71,6 +71,8 @@ SOURCES = {
     # the wavelet table repeats ira_fdw.hip's weight and phasor term for term (the same split of k rho); the map's sums
     # call fma themselves
     "ira_burstdecay.hip": ["-ffp-contract=off"],
+    # |X|^2 = re * re + im * im and the phase wrap d - 2 pi rint(d / 2 pi) round one operation at a time, like NumPy's
+    "ira_minphase.hip": ["-ffp-contract=off"],
 }
 COMMON = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function"]
 

@@ -85,6 +85,11 @@ BURST_CHANNELS = 4            # IRA_BURST_CHANNELS: channels (waves) per workgro
 BURST_MAX_STEPS = 4096        # IRA_BURST_MAX_STEPS
 BURST_MAX_DELTA = 1 << 24     # IRA_BURST_MAX_DELTA: the largest |delta| in samples
 BURST_MAX_OUT_BYTES = 256 << 20  # Engine.burst_decay: one ira_burst_decay call writes at most this (the default map of 256 channels is 60 MB)
+MINPHASE_FIELDS = 8           # IRA_MINPHASE_FIELDS: Re X, Im X, Im T at k - 1, k, k + 1, the unwrapped excess phase at k - 1, k, k + 1
+MINPHASE_MAX_LOG2 = 21        # IRA_MINPHASE_MAX_LOG2
+MINPHASE_MIN_N = 32           # the smallest transform of the chain
+MINPHASE_MIN_FLOOR_DB = -300.0  # IRA_MINPHASE_MIN_FLOOR_DB
+MINPHASE_SCRATCH_BYTES = 4 << 30  # minphase_cut: the device scratch of one sub-batch of the minimum-phase chain stays under this
 
 
 def xspec_frames(n, n_fft: int, hop: int) -> np.ndarray:
@@ -169,6 +174,28 @@ def burst_channels_per_call(npts: int, nsteps: int) -> int:
     """Channels one ira_burst_decay call of Engine.burst_decay takes: as many as keep its output of 16 bytes per (channel,
     point, step) within BURST_MAX_OUT_BYTES, at least one, at most the 65535 of a launch."""
     return int(max(1, min(65535, BURST_MAX_OUT_BYTES // max(1, 16 * int(npts) * int(nsteps)))))
+
+
+def minphase_scratch_bytes(n_fft) -> np.ndarray:
+    """Device scratch of the minimum-phase chain per channel of transform size N, in bytes: X, G and T (16 (N/2 + 1) each),
+    the cepstrum (4 N), the wrapped and the unwrapped excess phase (8 (N/2 + 1) each) and a transform's work array (8 N):
+    44 N + 64, 92 MB at N = 2^21."""
+    return 44 * np.asarray(n_fft, dtype=np.int64) + 64
+
+
+def minphase_cut(n_fft) -> List[Tuple[int, int]]:
+    """[(first, end), ..]: consecutive channels cut into sub-batches whose scratch (minphase_scratch_bytes) stays under
+    MINPHASE_SCRATCH_BYTES; a channel that alone exceeds it is a sub-batch of its own."""
+    need = minphase_scratch_bytes(n_fft).reshape(-1)
+    cuts, first, total = [], 0, 0
+    for i, b in enumerate(need.tolist()):
+        if i > first and total + b > MINPHASE_SCRATCH_BYTES:
+            cuts.append((first, i))
+            first, total = i, 0
+        total += b
+    if need.size:
+        cuts.append((first, int(need.size)))
+    return cuts
 
 
 def lundeby_layout(base_off, base_len, chan_of_seg, blk_size, nblk, first_m) -> Dict[str, object]:
@@ -1060,6 +1087,91 @@ class Engine:
                       "ira_burst_decay")
                 outs.append(out[: n * npts * nsteps * 2].view(n, npts, nsteps, 2))
         return outs
+
+    # ------------------------------------------------------------------ minimum phase / excess phase (real cepstrum)
+    @staticmethod
+    def _minphase_sizes(spec_off: np.ndarray, n_fft: np.ndarray):
+        spec_off = np.ascontiguousarray(spec_off, dtype=np.int64).reshape(-1)
+        n_in = np.asarray(n_fft).reshape(-1)
+        if n_in.size != spec_off.size:
+            raise ValueError("spec_off and n_fft must be (n,)")
+        if spec_off.size > 65535:
+            raise ValueError("at most 65535 channels per launch")
+        n64 = n_in.astype(np.int64)
+        if n_in.size and not (np.all(n_in == n64) and np.all(n64 >= MINPHASE_MIN_N) and np.all(n64 <= 1 << MINPHASE_MAX_LOG2)
+                              and np.all(n64 & (n64 - 1) == 0)):
+            raise ValueError(f"n_fft must be powers of two {MINPHASE_MIN_N}..2^{MINPHASE_MAX_LOG2}")
+        return spec_off, n64.astype(np.int32)
+
+    def minphase_logmag(self, spec_dev, spec_off: np.ndarray, n_fft: np.ndarray, floor_db: float):
+        """G = 0.5 ln(max(|X|^2, P 10^(floor_db / 10))) as the complex (G, 0) at the spectra's own offsets, P = max |X|^2 per
+        element and the count of bins below the floor (ira_minphase_logmag).  Returns (g float64 device laid out like
+        spec_dev, pmax float64 device (n,), floored int64 device (n,))."""
+        t = self.torch
+        spec_off, n_fft = self._minphase_sizes(spec_off, n_fft)
+        if not (MINPHASE_MIN_FLOOR_DB <= float(floor_db) <= 0.0):
+            raise ValueError(f"floor_db must lie in {MINPHASE_MIN_FLOOR_DB:g} .. 0, got {floor_db}")
+        n = int(spec_off.size)
+        g = self.empty(int((n_fft.astype(np.int64) // 2 + 1).sum()) * 2, t.float64)
+        pmax, floored = self.empty(n, t.float64), self.empty(n, t.int64)
+        if n:
+            d_so, d_nf = self.job_tables(spec_off, n_fft)
+            check(self.lib.ira_minphase_logmag(_ptr(spec_dev), _ptr(d_so), _ptr(d_nf), n, int(n_fft.max()), float(floor_db),
+                                               _ptr(g), _ptr(pmax), _ptr(floored), self.stream), "ira_minphase_logmag")
+        return g, pmax[:n], floored[:n]
+
+    def minphase_excess(self, spec_dev, tspec_dev, spec_off: np.ndarray, n_fft: np.ndarray, centre: np.ndarray, pmax_dev):
+        """wrap(phi_rel - phi_min) per bin, float64 radians, one double per bin at spec_off (the offsets phase_unwrap
+        takes): phi_rel = angle(X_k) + 2 pi frac(k centre / N), phi_min = 2 Im T_k (ira_minphase_excess)."""
+        t = self.torch
+        spec_off, n_fft = self._minphase_sizes(spec_off, n_fft)
+        centre = np.ascontiguousarray(centre, dtype=np.int64).reshape(-1)
+        n = int(spec_off.size)
+        if centre.size != n or (n and (centre.min() < 0 or centre.max() >= 1 << 31)):
+            raise ValueError("centre must be (n,) sample indices 0 .. 2^31 - 1")
+        ex = self.empty(int((n_fft.astype(np.int64) // 2 + 1).sum()), t.float64)
+        if n:
+            d_so, d_nf, d_c = self.job_tables(spec_off, n_fft, centre)
+            check(self.lib.ira_minphase_excess(_ptr(spec_dev), _ptr(tspec_dev), _ptr(d_so), _ptr(d_nf), _ptr(d_c),
+                                               _ptr(pmax_dev), n, int(n_fft.max()), _ptr(ex), self.stream),
+                  "ira_minphase_excess")
+        return ex
+
+    def minphase_gather(self, spec_dev, tspec_dev, unwrapped_dev, spec_off: np.ndarray, n_fft: np.ndarray, bins: np.ndarray,
+                        pmax_dev):
+        """The records of the grid points: bins (n, J) whole numbers 1 .. N/2 - 1 per element -> (n, J, MINPHASE_FIELDS)
+        float64 device: Re X, Im X, Im T at k - 1, k, k + 1, the unwrapped excess phase at k - 1, k, k + 1; NaN for an
+        element without values (ira_minphase_gather)."""
+        t = self.torch
+        spec_off, n_fft = self._minphase_sizes(spec_off, n_fft)
+        n = int(spec_off.size)
+        bins_in = np.asarray(bins)
+        if bins_in.ndim != 2 or bins_in.shape[0] != n:
+            raise ValueError("bins must be (n, J)")
+        npts = int(bins_in.shape[1])
+        if npts > FDW_MAX_POINTS:
+            raise ValueError(f"at most {FDW_MAX_POINTS} frequency points, got {npts}")
+        if bins_in.size and not (np.all(bins_in == np.rint(bins_in)) and np.all(bins_in >= 1)
+                                 and np.all(bins_in <= (n_fft.astype(np.int64) // 2 - 1)[:, None])):
+            raise ValueError("bins must be whole numbers 1 .. n_fft / 2 - 1")
+        bins = np.ascontiguousarray(bins_in, dtype=np.int32)
+        if n == 0 or npts == 0:                                     # nothing to launch (zero-size tables have no address)
+            return self.empty(0, t.float64)[:0].view(n, npts, MINPHASE_FIELDS)
+        out = self.empty(n * npts * MINPHASE_FIELDS, t.float64)
+        d_so, d_nf, d_b = self.job_tables(spec_off, n_fft, bins.reshape(-1))
+        check(self.lib.ira_minphase_gather(_ptr(spec_dev), _ptr(tspec_dev), _ptr(unwrapped_dev), _ptr(d_so), _ptr(d_nf),
+                                           _ptr(d_b), _ptr(pmax_dev), n, npts, _ptr(out), self.stream), "ira_minphase_gather")
+        return out[: n * npts * MINPHASE_FIELDS].view(n, npts, MINPHASE_FIELDS)
+
+    def minphase_spectrum(self, g_dev, tspec_dev, spec_off: np.ndarray, n_fft: np.ndarray, pmax_dev) -> None:
+        """M = e^G (cos phi_min, sin phi_min), phi_min = 2 Im T, in place of G; Im M = 0 at k = 0 and N/2
+        (ira_minphase_spectrum)."""
+        spec_off, n_fft = self._minphase_sizes(spec_off, n_fft)
+        n = int(spec_off.size)
+        if n:
+            d_so, d_nf = self.job_tables(spec_off, n_fft)
+            check(self.lib.ira_minphase_spectrum(_ptr(g_dev), _ptr(tspec_dev), _ptr(d_so), _ptr(d_nf), _ptr(pmax_dev), n,
+                                                 int(n_fft.max()), self.stream), "ira_minphase_spectrum")
 
     # ------------------------------------------------------------------ dual-channel spectral sums (Welch H1 / H2)
     def cross_spectra(self, x_dev, x_off: np.ndarray, y_off: np.ndarray, n: np.ndarray, n_fft: int, hop: int,

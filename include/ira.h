@@ -1033,6 +1033,51 @@ int32_t ira_burst_decay(const float* x_dev, const int64_t* off_dev, const int64_
                         const double* table_dev, int64_t table_doubles, const int32_t* delta, const int32_t* delta_dev,
                         int32_t npts, int32_t nsteps, double* out_dev, void* stream);
 
+/* ---- Minimum phase, excess phase and the minimum-phase response by the real cepstrum ---------------------------------------
+ * Nothing in the reference computes it; the entry points replace no reference function.  Host side, with the definition
+ * pinned: audio_analysis_amd/analyse/minphase.py (`python -m analyse.minphase`).
+ * The chain of a channel x of D samples with the centre p, N a power of two (32 .. 2^IRA_MINPHASE_MAX_LOG2):
+ *     X         = rfft(x[:D], n = N)                                    (ira_rfft_smooth / ira_rfft_any, data_len D, win_len N)
+ *     P         = max_k |X_k|^2, |X|^2 = re * re + im * im in float64;  P_floor = P * 10^(floor_db / 10)
+ *     G_k       = 0.5 ln(max(|X_k|^2, P_floor)), k = 0 .. N/2, written as the complex (G, 0)          (ira_minphase_logmag)
+ *     c         = float32(irfft(G, N))                                  (ira_band_irfft*, all-pass record 2, -1, -1)
+ *     T         = rfft(c[0 : N/2], n = N)                               (data_len N/2)
+ *     phi_min_k = 2 Im T_k: the folded cepstrum c[0], 2 c[n], c[N/2], 0 .. has exactly this imaginary transform
+ *     phi_rel_k = atan2(Im X_k, Re X_k) + 2 pi ((k p mod N) / N), k p mod N in int64
+ *     d_k       = phi_rel_k - phi_min_k;  wrapped: d_k - 2 pi rint(d_k / (2 pi))                      (ira_minphase_excess)
+ *     excess    = numpy.unwrap of the wrapped d over k = 0 .. N/2                                     (ira_phase_unwrap)
+ *     M_k       = e^{G_k} (cos phi_min_k, sin phi_min_k), Im M = 0 at k = 0 and N/2, in place of G    (ira_minphase_spectrum)
+ * Element e < nb: nfft_dev[e] = N (int32) and its N/2 + 1 bins at spec_off_dev[e] (int64), counted in complex doubles for
+ * spec_dev, tspec_dev and g_dev and in doubles for excess_dev / unwrapped_dev -- the offsets ira_phase_unwrap takes.
+ * ira_minphase_logmag: pmax_dev[e] = P as the maximum over the bit patterns of |X_k|^2 (sign cleared), so a NaN among them
+ *   wins; floored_dev[e] (int64) = the bins with |X_k|^2 < P_floor.  Both are zeroed by the call and combined across
+ *   workgroups by INTEGER atomics (max, add): order free.  An element has values only if 0 < P < infinity; otherwise (digital
+ *   silence, a NaN or an infinity among the samples) its G is (0, 0) -- no logarithm of zero is taken -- its floored count 0,
+ *   and the other calls write 0 (excess, M) or NaN (the records) for it.  Elements never meet: no value of one element
+ *   depends on another.
+ * ira_minphase_gather: out_dev[(e * npts + j) * IRA_MINPHASE_FIELDS + ..], float64, for the bin k = bins_dev[e * npts + j]
+ *   (int32, clamped to 1 .. N/2 - 1):  [0] Re X_k  [1] Im X_k  [2] Im T_(k-1)  [3] Im T_k  [4] Im T_(k+1)
+ *   [5] excess_(k-1)  [6] excess_k  [7] excess_(k+1)  (radians, unwrapped).
+ * All four are streaming passes (16-byte loads of the interleaved complex doubles, one bin a lane); no value depends on the
+ * launch shape, and every index is formed from the element's own clamped N.
+ * Checked before anything touches a device (IRA_E_NULL / IRA_E_SIZE): nb 0..65535, max_nfft (the largest N; it sizes the
+ * grid) a power of two 32 .. 2^IRA_MINPHASE_MAX_LOG2, IRA_MINPHASE_MIN_FLOOR_DB <= floor_db <= 0, npts
+ * 0..IRA_FDW_MAX_POINTS.  nb = 0 (or npts = 0): IRA_OK, no launch. */
+#define IRA_MINPHASE_FIELDS 8
+#define IRA_MINPHASE_MAX_LOG2 21          /* the largest transform the long-FFT kernels take */
+#define IRA_MINPHASE_MIN_FLOOR_DB (-300.0)
+int32_t ira_minphase_logmag(const double* spec_dev, const int64_t* spec_off_dev, const int32_t* nfft_dev, int32_t nb,
+                            int32_t max_nfft, double floor_db, double* g_dev, double* pmax_dev, int64_t* floored_dev,
+                            void* stream);
+int32_t ira_minphase_excess(const double* spec_dev, const double* tspec_dev, const int64_t* spec_off_dev,
+                            const int32_t* nfft_dev, const int64_t* centre_dev, const double* pmax_dev, int32_t nb,
+                            int32_t max_nfft, double* excess_dev, void* stream);
+int32_t ira_minphase_gather(const double* spec_dev, const double* tspec_dev, const double* unwrapped_dev,
+                            const int64_t* spec_off_dev, const int32_t* nfft_dev, const int32_t* bins_dev,
+                            const double* pmax_dev, int32_t nb, int32_t npts, double* out_dev, void* stream);
+int32_t ira_minphase_spectrum(double* g_dev, const double* tspec_dev, const int64_t* spec_off_dev, const int32_t* nfft_dev,
+                              const double* pmax_dev, int32_t nb, int32_t max_nfft, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
