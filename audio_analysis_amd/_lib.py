@@ -174,6 +174,16 @@ def check(rc: int, what: str = "") -> None:
         raise IraError(f"libira {what} failed with code {rc}: {msg.decode() if msg else '?'}")
 
 
+def ptr(t) -> int:
+    """The device address of a tensor, 0 for None.  torch gives a zero-size view no address; one that Engine.out_view
+    made answers with its buffer's, as the buffer itself did when the launchers passed that."""
+    return 0 if t is None else int(t.data_ptr()) or getattr(t, "buffer_ptr", 0)
+
+
 def dbl_array(values):
     arr = (f64 * max(1, len(values)))(*[float(v) for v in values])
     return arr
+
+
+def i32_array(values):
+    return (i32 * max(1, len(values)))(*[int(v) for v in values])

@@ -3,11 +3,10 @@
 // audio_analysis_amd/analyse/burstdecay.py state the definition).  Nothing in the reference computes it.
 //
 // ira_fdw_response makes weight and phasor of every term where it uses them.  A map uses the wavelet g_j of a point for
-// every step and every channel, so it is made ONCE (burst_table_kernel, the arithmetic of ira_fdw.hip term for term) and
-// the map is a real-by-complex correlation against that table: two fmas and a conversion per term.
+// every step and every channel, so it is made ONCE (burst_table_kernel, from the same ira::wavelet_term of ira_wavelet.h)
+// and the map is a real-by-complex correlation against that table: two fmas and a conversion per term.
 //
-// Compiled with -ffp-contract=off: the reduction of the turn count needs the PRODUCT k rho rounded (t_hi) and its error
-// (t_lo) apart, and the sums call fma themselves.
+// Compiled with -ffp-contract=off for the reduction of the turn count (ira_wavelet.h); the sums call fma themselves.
 //
 //   burst_table_kernel  grid (ceil((2 max H + 1) / 256), points), 256 threads: one thread per table entry.
 //   burst_decay_kernel  grid (points * ceil(steps / IRA_BURST_STEPS), ceil(channels / IRA_BURST_CHANNELS)), a wave per
@@ -21,6 +20,7 @@
 #include <math.h>
 
 #include "ira_common.h"
+#include "ira_wavelet.h"
 
 namespace {
 
@@ -28,39 +28,23 @@ constexpr int BD_THREADS = IRA_BURST_CHANNELS * IRA_WAVE;
 constexpr int BD_TABLE_THREADS = 256;
 constexpr int BD_VALUES = 2 * IRA_BURST_STEPS;                           // Re, Im of every step of a tile
 constexpr int BD_PITCH = IRA_BURST_LANES + 1;                            // doubles: the 16 summing lanes on 16 banks
-constexpr int64_t BD_CENTRE_LIMIT = (int64_t)1 << 62;                    // |p| beyond this is as far outside as this
 static_assert(IRA_BURST_LANES == IRA_WAVE, "a round is one term a lane");
 static_assert(BD_VALUES <= IRA_WAVE, "a lane per value in the final sums");
 static_assert(IRA_BURST_MAX_STEPS >= 1024 && IRA_BURST_MAX_DELTA >= 72000, "the default axes fit");
-
-__device__ __forceinline__ int bd_half(const int32_t* half_dev, int j) {
-  const int h = half_dev[j];
-  return h < 1 ? 1 : (h > IRA_FDW_MAX_HALF ? IRA_FDW_MAX_HALF : h);
-}
 
 __global__ __launch_bounds__(BD_TABLE_THREADS) void burst_table_kernel(const double* __restrict__ rho_dev,
                                                                        const int32_t* __restrict__ half_dev,
                                                                        const int64_t* __restrict__ tab_off_dev, int window,
                                                                        int64_t entries, double* __restrict__ table) {
   const int j = blockIdx.y;
-  const int h = ira::uniform(bd_half(half_dev, j));
+  const int h = ira::uniform(ira::wavelet_half(half_dev, j));
   const int64_t n = 2 * (int64_t)h + 1;
   const int64_t u = (int64_t)blockIdx.x * BD_TABLE_THREADS + threadIdx.x;
   const int64_t first = ira::uniform(tab_off_dev[j]);
   if (u >= n || first < 0 || first > entries - n) return;                // a point that would leave the table: not written
   const double rho = ira::uniform(rho_dev[j]);
-  const int k = (int)(u - h);
-  const double kd = (double)k;
-  const double t_hi = kd * rho;
-  const double t_lo = fma(kd, rho, -t_hi);
-  const double turn = (t_hi - rint(t_hi)) + t_lo;
   double sn, cs;
-  sincospi(2.0 * turn, &sn, &cs);
-  double w = 1.0;
-  if (window == 0) {
-    const double sp = sinpi((double)(h + 1 - (k < 0 ? -k : k)) * (1.0 / (double)(2 * h + 2)));
-    w = sp * sp;
-  }
+  const double w = ira::wavelet_term((int)(u - h), h, rho, window, [h] { return 1.0 / (double)(2 * h + 2); }, &sn, &cs);
   double2 g;
   g.x = w * cs;
   g.y = -(w * sn);
@@ -124,15 +108,14 @@ __global__ __launch_bounds__(BD_THREADS) void burst_decay_kernel(const float* __
   const int c = (int)by * IRA_BURST_CHANNELS + wv;
   if (c >= nch) return;                                                  // the whole wave; the waves of a workgroup never meet
   const int j = (int)bx / tiles, m0 = ((int)bx % tiles) * IRA_BURST_STEPS;
-  const int h = ira::uniform(bd_half(half_dev, j));
+  const int h = ira::uniform(ira::wavelet_half(half_dev, j));
   const int n = 2 * h + 1;
   const int64_t first = ira::uniform(tab_off_dev[j]);
   const bool table_ok = first >= 0 && first <= entries - n;
   const float* xc = x + ira::uniform(off[c]);
   int64_t length = ira::uniform(len[c]);
   length = length > 0 ? length : 0;
-  int64_t p = ira::uniform(centre[c]);
-  p = p > BD_CENTRE_LIMIT ? BD_CENTRE_LIMIT : (p < -BD_CENTRE_LIMIT ? -BD_CENTRE_LIMIT : p);
+  const int64_t p = ira::wavelet_centre(ira::uniform(centre[c]));
 
   // per step: the terms inside the channel; over the tile: the rounds that hold any, and those that hold nothing else
   BdTile t;
@@ -190,22 +173,18 @@ __global__ __launch_bounds__(BD_THREADS) void burst_decay_kernel(const float* __
   }
 }
 
+// the entries of the table of a checked grid
 int64_t bd_entries(const int32_t* half, int32_t npts) {
   int64_t total = 0;
-  for (int32_t j = 0; j < npts; ++j) {
-    if (half[j] < 1 || half[j] > IRA_FDW_MAX_HALF) return IRA_E_SIZE;
-    total += 2 * (int64_t)half[j] + 1;
-  }
+  for (int32_t j = 0; j < npts; ++j) total += 2 * (int64_t)half[j] + 1;
   return total;
 }
 
 }  // namespace
 
 extern "C" int64_t ira_burst_table_doubles(const int32_t* half, int32_t npts) {
-  if (npts < 0 || npts > IRA_FDW_MAX_POINTS) return IRA_E_SIZE;
-  if (npts > 0) IRA_CHECK_PTR(half);
-  const int64_t entries = bd_entries(half, npts);
-  return entries < 0 ? entries : 2 * entries;
+  const int32_t rc = ira::wavelet_points_check(nullptr, half, npts, 0);
+  return rc != IRA_OK ? rc : 2 * bd_entries(half, npts);
 }
 
 extern "C" int32_t ira_burst_table(const double* rho, const int32_t* half, const double* rho_dev, const int32_t* half_dev,
@@ -213,13 +192,9 @@ extern "C" int32_t ira_burst_table(const double* rho, const int32_t* half, const
                                    int64_t table_doubles, void* stream) {
   IRA_CHECK_PTR(rho); IRA_CHECK_PTR(half); IRA_CHECK_PTR(rho_dev); IRA_CHECK_PTR(half_dev); IRA_CHECK_PTR(tab_off_dev);
   IRA_CHECK_PTR(table_dev);
-  if (npts < 0 || npts > IRA_FDW_MAX_POINTS) return IRA_E_SIZE;
-  if (window != 0 && window != 1) return IRA_E_SIZE;
-  for (int32_t j = 0; j < npts; ++j)
-    if (!(isfinite(rho[j]) && rho[j] > 0.0 && rho[j] <= 0.5)) return IRA_E_SIZE;
-  const int64_t entries = bd_entries(half, npts);
-  if (entries < 0) return (int32_t)entries;
-  if (table_doubles < 2 * entries) return IRA_E_SIZE;
+  const int32_t rc = ira::wavelet_points_check(rho, half, npts, window);
+  if (rc != IRA_OK) return rc;
+  if (table_doubles < 2 * bd_entries(half, npts)) return IRA_E_SIZE;
   if (npts == 0) return IRA_OK;
   int32_t widest = 1;
   for (int32_t j = 0; j < npts; ++j) widest = half[j] > widest ? half[j] : widest;
@@ -237,11 +212,10 @@ extern "C" int32_t ira_burst_decay(const float* x_dev, const int64_t* off_dev, c
   IRA_CHECK_PTR(x_dev); IRA_CHECK_PTR(off_dev); IRA_CHECK_PTR(len_dev); IRA_CHECK_PTR(centre_dev); IRA_CHECK_PTR(half);
   IRA_CHECK_PTR(half_dev); IRA_CHECK_PTR(tab_off_dev); IRA_CHECK_PTR(table_dev); IRA_CHECK_PTR(delta);
   IRA_CHECK_PTR(delta_dev); IRA_CHECK_PTR(out_dev);
-  if (nch < 0 || nch > 65535 || npts < 0 || npts > IRA_FDW_MAX_POINTS || nsteps < 0 || nsteps > IRA_BURST_MAX_STEPS)
-    return IRA_E_SIZE;
-  const int64_t entries = bd_entries(half, npts);
-  if (entries < 0) return (int32_t)entries;
-  if (table_doubles < 2 * entries) return IRA_E_SIZE;
+  if (nch < 0 || nch > 65535 || nsteps < 0 || nsteps > IRA_BURST_MAX_STEPS) return IRA_E_SIZE;
+  const int32_t rc = ira::wavelet_points_check(nullptr, half, npts, 0);
+  if (rc != IRA_OK) return rc;
+  if (table_doubles < 2 * bd_entries(half, npts)) return IRA_E_SIZE;
   for (int32_t j = 0; j < npts; ++j) {
     const int32_t* d = delta + (int64_t)j * nsteps;
     for (int32_t m = 0; m < nsteps; ++m) {

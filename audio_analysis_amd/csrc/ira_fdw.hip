@@ -2,9 +2,8 @@
 // sample, the window a fixed number of cycles long, so its length falls with frequency (include/ira.h and
 // audio_analysis_amd/analyse/fdw.py state the definition).  Nothing in the reference computes it.
 //
-// Compiled with -ffp-contract=off: the reduction of the turn count needs the PRODUCT k rho rounded (t_hi) and its error
-// (t_lo) apart -- a contraction of `k * rho - rint(t_hi)` into one fma would count t_lo twice -- and the sums call fma
-// themselves.
+// Compiled with -ffp-contract=off for the reduction of the turn count (ira_wavelet.h, which holds the term's weight and
+// phasor); the sums call fma themselves.
 //
 //   fdw_plan_kernel     one workgroup.  From half_dev: first[j] = the first chunk of point j (a narrow point has none),
 //                       first[npts] = T, job_point[b] = the point of chunk b, narrow_point[m] = the m-th narrow point.
@@ -24,6 +23,7 @@
 
 #include "ira_common.h"
 #include "ira_reduce.h"
+#include "ira_wavelet.h"
 
 namespace {
 
@@ -32,18 +32,12 @@ constexpr int FDW_WAVES = FDW_THREADS / IRA_WAVE;
 constexpr int FDW_ROUNDS = IRA_FDW_CHUNK / FDW_THREADS;                  // terms per thread of a wide chunk
 constexpr int FDW_NARROW_ROUNDS = (2 * IRA_FDW_NARROW_HALF + 1 + IRA_WAVE - 1) / IRA_WAVE;
 constexpr int FDW_PLAN_PER_THREAD = IRA_FDW_MAX_POINTS / FDW_THREADS;
-constexpr int64_t FDW_CENTRE_LIMIT = (int64_t)1 << 62;                   // |p| beyond this is as far outside as this
 static_assert(IRA_FDW_CHUNK % FDW_THREADS == 0, "whole rounds");
 static_assert(FDW_NARROW_ROUNDS == 4 && 2 * IRA_FDW_NARROW_HALF + 1 <= FDW_NARROW_ROUNDS * IRA_WAVE, "a narrow point fits a wave's rounds");
 static_assert(FDW_PLAN_PER_THREAD * FDW_THREADS == IRA_FDW_MAX_POINTS, "the plan's workgroup covers every point");
 
 __host__ __device__ inline int64_t fdw_chunks(int h) {
   return h <= IRA_FDW_NARROW_HALF ? 0 : (2 * (int64_t)h + 1 + IRA_FDW_CHUNK - 1) / IRA_FDW_CHUNK;
-}
-
-__device__ __forceinline__ int fdw_half(const int32_t* half_dev, int j) {
-  const int h = half_dev[j];
-  return h < 1 ? 1 : (h > IRA_FDW_MAX_HALF ? IRA_FDW_MAX_HALF : h);
 }
 
 struct FdwChannel {
@@ -57,8 +51,7 @@ __device__ __forceinline__ FdwChannel fdw_channel(const float* x, const int64_t*
   ch.x = x + ira::uniform(off[c]);
   ch.len = ira::uniform(len[c]);
   ch.len = ch.len > 0 ? ch.len : 0;
-  ch.p = ira::uniform(centre[c]);
-  ch.p = ch.p > FDW_CENTRE_LIMIT ? FDW_CENTRE_LIMIT : (ch.p < -FDW_CENTRE_LIMIT ? -FDW_CENTRE_LIMIT : ch.p);
+  ch.p = ira::wavelet_centre(ira::uniform(centre[c]));
   return ch;
 }
 
@@ -93,19 +86,9 @@ __device__ __forceinline__ FdwSums fdw_terms(const FdwChannel& ch, int h, double
   for (int r = 0; r < R; ++r) {
     if (!in[r]) continue;
     const int k = u0 + stride * r - h;
-    const double kd = (double)k;
-    const double t_hi = kd * rho;
-    const double t_lo = fma(kd, rho, -t_hi);
-    const double turn = (t_hi - rint(t_hi)) + t_lo;
     double sn, cs;
-    sincospi(2.0 * turn, &sn, &cs);
-    double w = 1.0;
-    if (window == 0) {
-      const double sp = sinpi((double)(h + 1 - (k < 0 ? -k : k)) * inv);
-      w = sp * sp;
-    }
-    const double v = w * (double)xv[r];
-    const double kv = kd * v;
+    const double v = ira::wavelet_term(k, h, rho, window, [inv] { return inv; }, &sn, &cs) * (double)xv[r];
+    const double kv = (double)k * v;
     s.v[0] = fma(v, cs, s.v[0]);
     s.v[1] = fma(-v, sn, s.v[1]);
     s.v[2] = fma(kv, cs, s.v[2]);
@@ -126,7 +109,7 @@ __global__ __launch_bounds__(FDW_THREADS) void fdw_plan_kernel(const int32_t* __
 #pragma unroll
   for (int q = 0; q < FDW_PLAN_PER_THREAD; ++q) {
     const int j = j0 + q;
-    cnt[q] = j < npts ? (int)fdw_chunks(fdw_half(half_dev, j)) : -1;     // -1: no such point
+    cnt[q] = j < npts ? (int)fdw_chunks(ira::wavelet_half(half_dev, j)) : -1;     // -1: no such point
     wide += cnt[q] > 0 ? cnt[q] : 0;
     narrow += cnt[q] == 0;
   }
@@ -165,7 +148,7 @@ __global__ __launch_bounds__(FDW_THREADS) void fdw_narrow_kernel(const float* __
   const int c = blockIdx.y;
   int j = ira::uniform(narrow_point[m]);
   j = j < 0 ? 0 : (j >= npts ? npts - 1 : j);
-  int h = ira::uniform(fdw_half(half_dev, j));
+  int h = ira::uniform(ira::wavelet_half(half_dev, j));
   h = h > IRA_FDW_NARROW_HALF ? IRA_FDW_NARROW_HALF : h;
   const double rho = ira::uniform(rho_dev[j]);
   const FdwChannel ch = fdw_channel(x, off, len, centre, c);
@@ -193,7 +176,7 @@ __global__ __launch_bounds__(FDW_THREADS) void fdw_wide_kernel(const float* __re
   const int b = blockIdx.x, c = blockIdx.y;
   int j = ira::uniform(job_point[b]);
   j = j < 0 ? 0 : (j >= npts ? npts - 1 : j);
-  const int h = ira::uniform(fdw_half(half_dev, j));
+  const int h = ira::uniform(ira::wavelet_half(half_dev, j));
   const double rho = ira::uniform(rho_dev[j]);
   int chunk = b - ira::uniform(first[j]);
   chunk = chunk < 0 || chunk >= fdw_chunks(h) ? -1 : chunk;              // a chunk the point does not have: no term
@@ -241,24 +224,21 @@ __global__ __launch_bounds__(FDW_THREADS) void fdw_finish_kernel(const int64_t* 
   FdwChannel ch;
   ch.x = nullptr;
   ch.len = len[c] > 0 ? len[c] : 0;
-  ch.p = centre[c];
-  ch.p = ch.p > FDW_CENTRE_LIMIT ? FDW_CENTRE_LIMIT : (ch.p < -FDW_CENTRE_LIMIT ? -FDW_CENTRE_LIMIT : ch.p);
+  ch.p = ira::wavelet_centre(centre[c]);
   double* o = out + ((int64_t)c * npts + j) * IRA_FDW_FIELDS;
 #pragma unroll
   for (int q = 0; q < IRA_FDW_SUMS; ++q) o[q] = v[q];
-  o[IRA_FDW_SUMS] = (double)fdw_inside(ch, fdw_half(half_dev, j));
+  o[IRA_FDW_SUMS] = (double)fdw_inside(ch, ira::wavelet_half(half_dev, j));
 }
 
-// T = the chunks of the wide points, M = the number of narrow points; IRA_E_SIZE for a half out of range
-int32_t fdw_counts(const int32_t* half, int32_t npts, int64_t* total, int64_t* narrow) {
+// T = the chunks of the wide points, M = the number of narrow points, of a checked grid
+void fdw_counts(const int32_t* half, int32_t npts, int64_t* total, int64_t* narrow) {
   *total = *narrow = 0;
   for (int32_t j = 0; j < npts; ++j) {
-    if (half[j] < 1 || half[j] > IRA_FDW_MAX_HALF) return IRA_E_SIZE;
     const int64_t n = fdw_chunks(half[j]);
     *total += n;
     *narrow += n == 0;
   }
-  return IRA_OK;
 }
 
 int64_t fdw_table_doubles(int32_t npts, int64_t total, int64_t narrow) { return (npts + 1 + total + narrow + 1) / 2; }
@@ -266,11 +246,11 @@ int64_t fdw_table_doubles(int32_t npts, int64_t total, int64_t narrow) { return 
 }  // namespace
 
 extern "C" int64_t ira_fdw_scratch_doubles(int32_t nch, const int32_t* half, int32_t npts) {
-  if (nch < 0 || nch > 65535 || npts < 0 || npts > IRA_FDW_MAX_POINTS) return IRA_E_SIZE;
-  if (npts > 0) IRA_CHECK_PTR(half);
-  int64_t total, narrow;
-  const int32_t rc = fdw_counts(half, npts, &total, &narrow);
+  if (nch < 0 || nch > 65535) return IRA_E_SIZE;
+  const int32_t rc = ira::wavelet_points_check(nullptr, half, npts, 0);
   if (rc != IRA_OK) return rc;
+  int64_t total, narrow;
+  fdw_counts(half, npts, &total, &narrow);
   return (int64_t)nch * total * IRA_FDW_SUMS + fdw_table_doubles(npts, total, narrow);
 }
 
@@ -280,13 +260,11 @@ extern "C" int32_t ira_fdw_response(const float* x_dev, const int64_t* off_dev, 
                                     double* scratch_dev, int64_t scratch_doubles, double* out_dev, void* stream) {
   IRA_CHECK_PTR(x_dev); IRA_CHECK_PTR(off_dev); IRA_CHECK_PTR(len_dev); IRA_CHECK_PTR(centre_dev); IRA_CHECK_PTR(rho);
   IRA_CHECK_PTR(half); IRA_CHECK_PTR(rho_dev); IRA_CHECK_PTR(half_dev); IRA_CHECK_PTR(scratch_dev); IRA_CHECK_PTR(out_dev);
-  if (nch < 0 || nch > 65535 || npts < 0 || npts > IRA_FDW_MAX_POINTS) return IRA_E_SIZE;
-  if (window != 0 && window != 1) return IRA_E_SIZE;
-  for (int32_t j = 0; j < npts; ++j)
-    if (!(isfinite(rho[j]) && rho[j] > 0.0 && rho[j] <= 0.5)) return IRA_E_SIZE;
-  int64_t total, narrow;
-  const int32_t rc = fdw_counts(half, npts, &total, &narrow);
+  if (nch < 0 || nch > 65535) return IRA_E_SIZE;
+  const int32_t rc = ira::wavelet_points_check(rho, half, npts, window);
   if (rc != IRA_OK) return rc;
+  int64_t total, narrow;
+  fdw_counts(half, npts, &total, &narrow);
   const int64_t sums = (int64_t)nch * total * IRA_FDW_SUMS;
   if (scratch_doubles < sums + fdw_table_doubles(npts, total, narrow)) return IRA_E_SIZE;
   if (nch == 0 || npts == 0) return IRA_OK;

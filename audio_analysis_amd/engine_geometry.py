@@ -1,0 +1,274 @@
+"""
+Geometry of the measure kernels, restated for the host in pure NumPy (neither torch nor the library is imported): the
+constants that mirror IRA_* defines of include/ira.h, the sizes and layouts the kernels derive from their arguments, and
+the table checks that several launchers of engine_measure.py share.  engine.py re-exports every name.
+"""
+from __future__ import annotations
+
+from typing import Dict, List, Optional, Tuple
+
+import numpy as np
+
+from .engine_plan import exclusive_cumsum
+
+TAIL_BLOCK = 512              # IRA_TAIL_BLOCK: samples per block of ira_tail_energy's suffix energies
+LUNDEBY_DOUBLES = 16          # IRA_LUNDEBY_DOUBLES
+LUNDEBY_MAX_BLOCKS = 4096     # IRA_LUNDEBY_MAX_BLOCKS
+LUNDEBY_STAGE = 4096          # samples a workgroup of the two sample passes stages; the largest block size
+LUNDEBY_MAX_LEN = 2047 * 4096
+MS_DOUBLES = 16               # IRA_MS_DOUBLES
+MS_MAX_GRID = 128             # IRA_MS_MAX_GRID
+MS_MAX_ORDER = 3              # IRA_MS_MAX_ORDER
+MS_TILE = 32                  # IRA_MS_TILE: points of j a workgroup of ira_multislope_gram stages at a time
+MS_REFINE_R = 3               # IRA_MS_REFINE_R
+MS_REFINED = 21               # IRA_MS_REFINED: (2 R + 1) * MS_MAX_ORDER, the stride of the refined grids
+ECHO_DOUBLES = 8              # IRA_ECHO_DOUBLES
+ECHO_CHUNK = 4096             # IRA_ECHO_CHUNK: samples per workgroup of the two sample passes, counted from the onset
+ECHO_MAX_LAG = 2048           # IRA_ECHO_MAX_LAG: the largest D (the halo the emit pass keeps of the chunk in front)
+ECHO_MAX_PARAMS = 16          # IRA_ECHO_MAX_PARAMS
+ECHO_PARAM_DOUBLES = 8        # IRA_ECHO_PARAM_DOUBLES
+NED_DOUBLES = 8               # IRA_NED_DOUBLES
+NED_TILE = 1024               # IRA_NED_TILE: positions a workgroup of ira_echo_density takes at a time when their span fits
+NED_MAX_DELTA = 2048          # IRA_NED_MAX_DELTA: the largest half window (W = 2 delta + 1 <= 4097)
+NED_MAX_THRESHOLDS = 3        # IRA_NED_MAX_THRESHOLDS
+NED_NAN_SILENT = 0x7fc00000   # IRA_NED_NAN_SILENT: the profile's NaN where the window holds digital silence (B == 0)
+NED_NAN_NONFINITE = 0x7fc00001  # IRA_NED_NAN_NONFINITE: the profile's NaN where B is not finite
+NED_SLOTS = 5120              # float64 squares a workgroup stages (NED_SLOTS of ira_echodensity.hip)
+REFL_DOUBLES = 8              # IRA_REFL_DOUBLES
+REFL_FIELDS = 6               # IRA_REFL_FIELDS
+REFL_TILE = 1024              # IRA_REFL_TILE: row entries a workgroup of ira_reflections takes
+REFL_MAX_HALF = 512           # IRA_REFL_MAX_HALF: the largest half smoothing window (W = 2 d + 1 <= 1025)
+REFL_MAX_DIRECT = 1024        # IRA_REFL_MAX_DIRECT
+REFL_MAX_BG = 2048            # IRA_REFL_MAX_BG
+REFL_MAX_KEEP = 64            # IRA_REFL_MAX_KEEP
+REFL_MAX_SEP = 1024           # the largest separation S
+REFL_UNBOUNDED = 1 << 40      # a Tn from here on is no bound (REFL_UNBOUNDED of ira_reflections.hip)
+XSPEC_FRAMES = 16             # IRA_XSPEC_FRAMES: frames a workgroup of ira_xspec_accumulate sums before it writes
+XSPEC_ROWS = 11               # IRA_XSPEC_ROWS
+XSPEC_MIN_FFT, XSPEC_MAX_FFT = 256, 8192
+FDW_FIELDS = 6                # IRA_FDW_FIELDS
+FDW_SUMS = 5                  # IRA_FDW_SUMS
+FDW_MAX_POINTS = 4096         # IRA_FDW_MAX_POINTS
+FDW_MAX_HALF = 1 << 20        # IRA_FDW_MAX_HALF
+FDW_CHUNK = 4096              # IRA_FDW_CHUNK: terms of a wide point a workgroup of ira_fdw_response sums
+FDW_NARROW_HALF = 127         # IRA_FDW_NARROW_HALF: up to here one wavefront takes the point
+FDW_WINDOWS = ("hann", "rect")
+BURST_STEPS = 8               # IRA_BURST_STEPS: steps of a point a wavefront of ira_burst_decay serves from one walk
+BURST_LANES = 64              # IRA_BURST_LANES: terms per round of that walk, one a lane
+BURST_CHANNELS = 4            # IRA_BURST_CHANNELS: channels (waves) per workgroup
+BURST_MAX_STEPS = 4096        # IRA_BURST_MAX_STEPS
+BURST_MAX_DELTA = 1 << 24     # IRA_BURST_MAX_DELTA: the largest |delta| in samples
+BURST_MAX_OUT_BYTES = 256 << 20  # Engine.burst_decay: one ira_burst_decay call writes at most this (the default map of 256 channels is 60 MB)
+MINPHASE_FIELDS = 8           # IRA_MINPHASE_FIELDS: Re X, Im X, Im T at k - 1, k, k + 1, the unwrapped excess phase at k - 1, k, k + 1
+MINPHASE_MAX_LOG2 = 21        # IRA_MINPHASE_MAX_LOG2
+MINPHASE_MIN_N = 32           # the smallest transform of the chain
+MINPHASE_MIN_FLOOR_DB = -300.0  # IRA_MINPHASE_MIN_FLOOR_DB
+MINPHASE_SCRATCH_BYTES = 4 << 30  # minphase_cut: the device scratch of one sub-batch of the minimum-phase chain stays under this
+
+
+def flat(a, dtype) -> Optional[np.ndarray]:
+    """A table as the kernels read it: contiguous, of this dtype, one dimension; None (a table a call does without) stays."""
+    return None if a is None else np.ascontiguousarray(a, dtype=dtype).reshape(-1)
+
+
+def same_rows(message: str, *tables) -> int:
+    """The rows of tables that hold one entry per row; ValueError(message) when they differ in size."""
+    n = int(np.size(tables[0]))
+    if any(np.size(v) != n for v in tables[1:]):
+        raise ValueError(message)
+    return n
+
+
+def whole_numbers(a, lo, hi) -> bool:
+    """Every entry is a whole number in lo .. hi (a bound may be an array that broadcasts); true of no entries."""
+    a = np.asarray(a)
+    return not a.size or bool(np.all(a == np.rint(a)) and np.all(a >= lo) and np.all(a <= hi))
+
+
+def segment_tables(base_off, base_len, chan_of_seg) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """The triple that places a segment in a sample buffer, in the kernels' types: int64, int64 and (the channel) int32."""
+    return flat(base_off, np.int64), flat(base_len, np.int64), flat(chan_of_seg, np.int32)
+
+
+def point_grid(rho: np.ndarray, half, window: str) -> np.ndarray:
+    """The check of a grid of frequency points (rho float64 (J,), as flat gives it): ValueError unless half has J entries,
+    J <= FDW_MAX_POINTS, window is one of FDW_WINDOWS, every rho is finite and in (0, 0.5] and every half a whole number
+    1 .. FDW_MAX_HALF.  Returns half as int32 (J,)."""
+    half = np.asarray(half).reshape(-1)
+    npts = same_rows("rho and half must be (J,)", rho, half)
+    if npts > FDW_MAX_POINTS:
+        raise ValueError(f"at most {FDW_MAX_POINTS} frequency points, got {npts}")
+    if window not in FDW_WINDOWS:
+        raise ValueError(f"window must be one of {FDW_WINDOWS}, got {window!r}")
+    if npts and not (np.all(np.isfinite(rho)) and np.all(rho > 0.0) and np.all(rho <= 0.5)):
+        raise ValueError("rho must be finite and in (0, 0.5]")
+    if not whole_numbers(half, 1, FDW_MAX_HALF):
+        raise ValueError(f"half must be whole numbers 1..{FDW_MAX_HALF}")
+    return flat(half, np.int32)
+
+
+def window_weights(weights, half: int, name: str) -> np.ndarray:
+    """The 2 * half + 1 weights of a window as float64 (W,), all finite and > 0 (`name`: the caller's word for half)."""
+    weights = flat(weights, np.float64)
+    if weights.size != 2 * half + 1 or not (np.all(np.isfinite(weights)) and np.all(weights > 0.0)):
+        raise ValueError(f"weights must be 2 * {name} + 1 finite values > 0")
+    return weights
+
+
+def xspec_frames(n, n_fft: int, hop: int) -> np.ndarray:
+    """K = 1 + (n - n_fft) // hop frames of n samples, 0 when n < n_fft (int64, elementwise)."""
+    n = np.asarray(n, dtype=np.int64)
+    return np.where(n >= n_fft, 1 + (n - n_fft) // hop, 0).astype(np.int64)
+
+
+def ned_positions(length, onset, step: int, kmax: int) -> np.ndarray:
+    """K = 0 if L <= o else min((L - 1 - o) // S + 1, Kmax) positions of a profile (int64, elementwise)."""
+    length, onset = np.asarray(length, dtype=np.int64), np.asarray(onset, dtype=np.int64)
+    return np.where(length > onset, np.minimum((length - 1 - onset) // int(step) + 1, int(kmax)), 0).astype(np.int64)
+
+
+def ned_tile_positions(delta: int, step: int) -> int:
+    """Positions a workgroup of ira_echo_density takes at a time (ned_geometry of ira_echodensity.hip, restated): NED_TILE
+    when their span fits NED_SLOTS, fewer for large steps and windows.  No result depends on it; tests place K at its
+    multiples."""
+    w, s = 2 * int(delta) + 1, int(step)
+    if 1 < s <= NED_SLOTS:
+        wq = -(-w // s)
+        t = min(NED_TILE, NED_SLOTS // s - wq + 1)
+        while t >= 1 and s * ((t - 1 + wq) | 1) > NED_SLOTS:
+            t -= 1
+        if t >= 1:
+            return t
+    return min(NED_TILE, (NED_SLOTS - w) // s + 1)
+
+
+def refl_row_room(length, direct: int, tn: int, background: int) -> np.ndarray:
+    """Entries of a channel's energy-time row as the host sizes it, for onset 0: min(L, Rmax), Rmax = D + Tn + B, L for
+    an unbounded Tn (int64, elementwise)."""
+    length = np.clip(np.asarray(length, dtype=np.int64), 0, None)
+    if int(tn) >= REFL_UNBOUNDED:
+        return length.copy()
+    return np.minimum(length, int(direct) + int(tn) + int(background)).astype(np.int64)
+
+
+def refl_tile_candidates(separation: int) -> int:
+    """Candidates a tile of REFL_TILE row entries can hold: two candidates lie more than S entries apart, so
+    ceil(REFL_TILE / (S + 1)) (ira_reflections.hip restated)."""
+    return (REFL_TILE + int(separation)) // (int(separation) + 1)
+
+
+def refl_scratch_doubles(nch: int, max_room: int, separation: int) -> int:
+    """Doubles of scratch ira_reflections needs: per channel and tile of the longest row a count and 4 doubles per
+    candidate the tile can hold (the geometry of ira_reflections.hip restated; the call checks it)."""
+    return int(nch) * (-(-int(max_room) // REFL_TILE)) * (1 + 4 * refl_tile_candidates(separation))
+
+
+def fdw_chunks(half) -> np.ndarray:
+    """Chunks of FDW_CHUNK terms of each point: ceil((2 H + 1) / FDW_CHUNK) for a wide point, 0 for a narrow one (H <=
+    FDW_NARROW_HALF), which one wavefront sums without a partial (int64, elementwise)."""
+    half = np.asarray(half, dtype=np.int64)
+    return np.where(half > FDW_NARROW_HALF, -(-(2 * half + 1) // FDW_CHUNK), 0).astype(np.int64)
+
+
+def fdw_scratch_doubles(nch: int, half) -> int:
+    """Doubles of scratch ira_fdw_response needs (ira_fdw_scratch_doubles restated; the call checks it): FDW_SUMS per
+    channel and chunk, then the int32 tables the plan launch builds (first chunk of each point and the total, the point
+    of each chunk, the narrow points)."""
+    chunks = fdw_chunks(half)
+    total, narrow, npts = int(chunks.sum()), int(np.count_nonzero(chunks == 0)), int(chunks.size)
+    return int(nch) * total * FDW_SUMS + (npts + 1 + total + narrow + 1) // 2
+
+
+def burst_table_offsets(half) -> np.ndarray:
+    """tab_off[j], the first entry of point j in the wavelet table of ira_burst_table: the points' 2 H + 1 entries lie one
+    after the other (int64, exclusive running sum)."""
+    half = flat(half, np.int64)
+    return exclusive_cumsum(2 * half + 1).astype(np.int64)
+
+
+def burst_table_doubles(half) -> int:
+    """Doubles of the wavelet table (ira_burst_table_doubles restated; both calls check it): (re, im) per entry, 2 H + 1
+    entries per point."""
+    half = flat(half, np.int64)
+    return 2 * int(np.sum(2 * half + 1))
+
+
+def burst_channels_per_call(npts: int, nsteps: int, max_out_bytes: int = BURST_MAX_OUT_BYTES) -> int:
+    """Channels one ira_burst_decay call of Engine.burst_decay takes: as many as keep its output of 16 bytes per (channel,
+    point, step) within BURST_MAX_OUT_BYTES, at least one, at most the 65535 of a launch."""
+    return int(max(1, min(65535, max_out_bytes // max(1, 16 * int(npts) * int(nsteps)))))
+
+
+def minphase_scratch_bytes(n_fft) -> np.ndarray:
+    """Device scratch of the minimum-phase chain per channel of transform size N, in bytes: X, G and T (16 (N/2 + 1) each),
+    the cepstrum (4 N), the wrapped and the unwrapped excess phase (8 (N/2 + 1) each) and a transform's work array (8 N):
+    44 N + 64, 92 MB at N = 2^21."""
+    return 44 * np.asarray(n_fft, dtype=np.int64) + 64
+
+
+def minphase_cut(n_fft, scratch_bytes: int = MINPHASE_SCRATCH_BYTES) -> List[Tuple[int, int]]:
+    """[(first, end), ..]: consecutive channels cut into sub-batches whose scratch (minphase_scratch_bytes) stays under
+    MINPHASE_SCRATCH_BYTES; a channel that alone exceeds it is a sub-batch of its own."""
+    need = minphase_scratch_bytes(n_fft).reshape(-1)
+    cuts, first, total = [], 0, 0
+    for i, b in enumerate(need.tolist()):
+        if i > first and total + b > scratch_bytes:
+            cuts.append((first, i))
+            first, total = i, 0
+        total += b
+    if need.size:
+        cuts.append((first, int(need.size)))
+    return cuts
+
+
+def lundeby_layout(base_off, base_len, chan_of_seg, blk_size, nblk, first_m) -> Dict[str, object]:
+    """Host side of the Lundeby row tables (pure NumPy): the tables in the kernels' types, every row's table offset
+    blk_off = j * (max nb + 1), table_doubles = nseg * (max nb + 1) (what ira_lundeby_scratch_doubles answers) and
+    max_chunks = max over the rows of ceil((nb + 1) / (4096 // B)), the grid width of the two sample passes.
+    ValueError for tables the kernels would refuse."""
+    base_off, base_len, chan_of_seg = segment_tables(base_off, base_len, chan_of_seg)
+    tabs = dict(base_off=base_off, base_len=base_len, chan_of_seg=chan_of_seg, blk_size=flat(blk_size, np.int32),
+                nblk=flat(nblk, np.int32), first_m=flat(first_m, np.int32))
+    n = same_rows("base_off, base_len, chan_of_seg, blk_size, nblk and first_m must have one entry per row", *tabs.values())
+    if n > 65535:
+        raise ValueError("at most 65535 rows per launch")
+    b, nb = tabs["blk_size"].astype(np.int64), tabs["nblk"].astype(np.int64)
+    if n and (b.min() < 1 or b.max() > LUNDEBY_STAGE):
+        raise ValueError(f"block sizes must be 1 .. {LUNDEBY_STAGE} samples")
+    if n and (nb.min() < 0 or nb.max() > LUNDEBY_MAX_BLOCKS):
+        raise ValueError(f"block counts must be 0 .. {LUNDEBY_MAX_BLOCKS}")
+    if n and tabs["first_m"].min() < 1:
+        raise ValueError("first_m must be at least 1 block")
+    if n and (tabs["base_len"].min() < 0 or tabs["base_len"].max() > LUNDEBY_MAX_LEN or np.any(nb * b > tabs["base_len"])):
+        raise ValueError(f"rows must hold their nb * B samples and at most {LUNDEBY_MAX_LEN}")
+    if n and tabs["chan_of_seg"].min() < 0:
+        raise ValueError("chan_of_seg must index the start array")
+    stride = int(nb.max()) + 1 if n else 1
+    tabs["blk_off"] = np.arange(n, dtype=np.int64) * stride
+    tabs["nseg"] = n
+    tabs["stride"] = stride
+    tabs["table_doubles"] = n * stride
+    per_chunk = LUNDEBY_STAGE // np.maximum(b, 1)
+    tabs["max_chunks"] = int(np.max(-(-(nb + 1) // per_chunk))) if n else 1
+    return tabs
+
+
+def multislope_slot_doubles(max_g: int) -> int:
+    """Doubles of a Gram slot of ira_multislope_gram for grids of at most max_g decay times: the lower triangle over the
+    g decays, the noise term and the constant 1."""
+    return (int(max_g) + 2) * (int(max_g) + 3) // 2
+
+
+def multislope_jobs(jobs, width: int, nseg: int, ngrids: int, nslots: int, max_g: int) -> np.ndarray:
+    """A job table of ira_multislope_gram (width 3: row, grid slot, Gram slot) or ira_multislope_search (width 4: row,
+    order, Gram slot, grid slot) as int32 (njobs, width), checked on the host: ValueError for an index out of range."""
+    jobs = np.ascontiguousarray(jobs, dtype=np.int32).reshape(-1, width)
+    if not 1 <= int(max_g) <= MS_MAX_GRID:
+        raise ValueError(f"a grid holds 1 .. {MS_MAX_GRID} decay times")
+    if jobs.size:
+        limits = (nseg, ngrids, nslots) if width == 3 else (nseg, MS_MAX_ORDER + 1, nslots, ngrids)
+        lows = (0, 0, 0) if width == 3 else (0, 1, 0, 0)
+        for col, (lo, hi) in enumerate(zip(lows, limits)):
+            if jobs[:, col].min() < lo or jobs[:, col].max() >= hi:
+                raise ValueError(f"column {col} of the job table must lie in [{lo}, {hi})")
+    return jobs

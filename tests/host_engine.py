@@ -25,7 +25,9 @@ from audio_analysis_amd import _lib
 from audio_analysis_amd.engine import ChannelBatch, Engine, HostFuture
 
 HOST_ONLY = {"ira_abi_version", "ira_error_string", "ira_fft_split", "ira_fft_smooth_split", "ira_band_tile_layout",
-             "ira_ar_partial_doubles", "ira_ar_exact_doubles", "ira_energy_scratch_doubles"}
+             "ira_ar_partial_doubles", "ira_ar_exact_doubles", "ira_energy_scratch_doubles", "ira_xcorr_scratch_doubles",
+             "ira_lundeby_scratch_doubles", "ira_mtf_scratch_doubles", "ira_echo_scratch_doubles", "ira_fdw_scratch_doubles",
+             "ira_burst_table_doubles"}
 
 
 class _RecordingLib:

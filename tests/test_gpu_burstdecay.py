@@ -169,6 +169,37 @@ def test_unit_impulse_gives_the_table_entry(window):
         assert got[0, j, 4, 0] == 1.0 and got[0, j, 4, 1] == 0.0    # t = 0: 0 dB at every frequency
 
 
+@pytest.mark.parametrize("window", R.WINDOWS)
+def test_fdw_response_of_a_unit_impulse_is_the_table_entry(window):
+    """What csrc/ira_wavelet.h holds by construction, as a value: for a channel that is zero but for x[p + k] = 1,
+    ira_fdw_response at the point (rho, H) returns (Re S0, Im S0) equal to entry k of ira_burst_table for that point and
+    window (np.array_equal: signed zeros are equal), A = |w(k)| and N = 2 H + 1.  One term is summed into zeros,
+    fma(v, cs, 0) is v * cs rounded once, and the sums of every other lane and chunk are exact zeros.  H: the last narrow
+    point, the first wide one, one full chunk of IRA_FDW_CHUNK terms, a second chunk of a single term.  The weight itself is
+    read from the table where the phasor is exactly +-1 or +-i: at rho = 0.5 (every k) and rho = 0.25 (odd k)."""
+    eng = _eng()
+    rho = np.array([0.5, 0.25, 1.0 / 3.0, 20.0 / 48000.0])
+    for h in (1, 127, 128, 2047, 2048):
+        ks = [-h, -1, 0, 1, h]
+        half = np.full(rho.size, h, dtype=np.int32)
+        chans = np.zeros((len(ks), 2 * h + 1), np.float32)
+        chans[np.arange(len(ks)), h + np.array(ks)] = 1.0
+        x_dev = eng.to_dev(np.concatenate([np.full(GUARD, np.nan, np.float32), chans.reshape(-1)]))
+        off = GUARD + np.arange(len(ks), dtype=np.int64) * (2 * h + 1)
+        centre_dev = eng.to_dev(np.full(len(ks), h, dtype=np.int64))
+        got = eng.fdw_response(x_dev, off, np.full(len(ks), 2 * h + 1), centre_dev, rho, half, window).cpu().numpy()
+        tab = eng.burst_table(rho, half, window)
+        entries = tab.table.cpu().numpy()[: tab.doubles].reshape(rho.size, 2 * h + 1, 2)
+        for c, k in enumerate(ks):
+            w = abs(entries[0, h + k, 0])                        # rho = 0.5: the phasor is (+-1, 0)
+            assert entries[0, h + k, 1] == 0.0 and (w == 1.0 if window == "rect" else 0.0 < w <= 1.0), (h, k, w)
+            if k % 2:
+                assert entries[1, h + k, 0] == 0.0 and abs(entries[1, h + k, 1]) == w, (h, k)   # rho = 0.25: (0, +-1)
+            for j in range(rho.size):
+                assert np.array_equal(got[c, j, :2], entries[j, h + k]), (window, h, float(rho[j]), k, got[c, j], entries[j, h + k])
+                assert got[c, j, 4] == w and got[c, j, 5] == 2 * h + 1, (window, h, float(rho[j]), k, got[c, j], w)
+
+
 def test_a_cell_does_not_depend_on_the_call_or_the_batch():
     rng = np.random.default_rng(204)
     rho, half = table([2, 33, 129, 1000], [0.1234567, 0.5])
