@@ -1,5 +1,5 @@
 """Guarded flat buffers for GPU tests that call the C-ABI on memory they own (test_gpu_modal_kernels.py,
-test_gpu_deconv_kernels.py): the segments of a launch lie in one 0xDEADBEEF-filled buffer, GUARD elements in front of
+test_gpu_deconv_kernels.py, test_gpu_minphase_kernels.py): the segments of a launch lie in one 0xDEADBEEF-filled buffer, GUARD elements in front of
 the first and behind the last, gaps of 1 to 7 elements between them, so offsets take every residue and a write outside
 a segment is seen when the buffer comes back."""
 import numpy as np

@@ -32,6 +32,7 @@ smaller constants, so the restatement is allowed the device's share once more), 
 2 E_X / |X_k| + 16 u pi, compared modulo 2 pi (numpy.unwrap is discontinuous where a step lies within the bound of pi; a
 whole turn is no error of the chain).  A group delay is the difference of two such phases over 4 pi / N.
 Against the analytic cases the restatement is allowed `second` (+ the phi_rel term), the device first + second.
+The minimum-phase response is held per sample to Bounds.response, derived in its docstring from the same terms.
 """
 import functools
 
@@ -150,6 +151,29 @@ class Bounds:
     def delay(self, phase_bound_lo, phase_bound_hi):
         """samples: two phase errors over 4 pi / N"""
         return (phase_bound_lo + phase_bound_hi) / (4.0 * np.pi / self.n)
+
+    def response(self, ref, h):
+        """Per sample of h = minimum_phase_ir(ref): how far the device's float32 h_min may lie from it.
+
+        h[n] = (1/N) sum_k w_k Re(M_k e^{2 pi i k n / N}), w_k = 2 but 1 at the edges, so |dh[n]| <= (2/N) sum_k |dM_k|.
+          M    M_k = e^{G_k} e^{i phi_min_k} moves by |M_k| (|dG_k| + |dphi_min_k|) to first order (both are below 1e-5;
+               the second order is allowed as a factor 1 + 2^-16).  dG_k per bin is the G line of the module docstring,
+               the device's and the restatement's share each: 2 (E_X / max(|X_k|, sqrt(P_floor)) + E_X / sqrt(P)) +
+               2 u (3 |G_k| + 2); dphi_min_k <= phi_min(), which already holds both shares.  exp, sincos and the two
+               products of ira_minphase_spectrum, and NumPy's, add 2 * 9 u |M_k| (tests/minphase_kernels_ref.py).
+                   spec = (2/N) sum_k |M_k| (dG_k + phi_min() + 18 u) (1 + 2^-16)
+          inv  the inverse transform of the exact M is off by c_inv u sqrt(2) ||M||_2 / N per sample (longfft_ref
+               docstring 6, inverse_const of the path taken, as for t_inv above), once for the device and once more for
+               numpy.fft: inv = 2 c_inv u sqrt(2) ||M||_2 / N
+          f32  the output is rounded to float32 once: 2^-24 (|h[n]| + spec + inv) + 2^-149
+        """
+        n = self.n
+        m = np.exp(ref["G"])
+        d_g = (2.0 * (self.e_x / np.maximum(self.mag, np.sqrt(ref["P_floor"])) + self.e_x / np.sqrt(ref["P"]))
+               + 2.0 * U * (3.0 * np.abs(ref["G"]) + 2.0))
+        spec = (2.0 / n) * float(np.sum(m * (d_g + self.phi_min() + 18.0 * U))) * (1.0 + 2.0 ** -16)
+        inv = 2.0 * L.inverse_const(n, *self.inverse_path) * U * np.sqrt(2.0) * float(np.sqrt(np.sum(m * m))) / n
+        return 2.0 ** -24 * (np.abs(np.asarray(h, dtype=np.float64)) + spec + inv) + 2.0 ** -149 + spec + inv
 
 
 def mod_turns(err):

@@ -6,7 +6,11 @@ both is asserted for every field of every record; the wrapped excess phase and t
 D = 5, 64, 100, 257 and 4097 (and 16) at oversample 2, 4 and 16 (N = 32 .. 2^17: the Bluestein length 32, the full-length
 direct transform at 64, half-length transforms above, an element of several workgroups and several unwrap tiles at 2^17), post_ms,
 onset and peak centres, silence, non-finite channels between good ones, sub-batches, a floor that engages, and the
-analytic cases of the restatement's module against the device.
+analytic cases of the restatement's module against the device.  Polarity: a channel and its negation, and channels whose
+samples sum below zero on every path the first transform takes, held without a 2 pi exemption (the device's Im X_0 is
++0.0 on all of them; measured on an MI355X, the unwrapped excess phase at the first grid point lies within 0.13 of its
+bound of the restatement's).  The minimum-phase response against the restatement's, per sample within Bounds.response
+(worst 0.26 of the bound, at N = 32).  The kernels alone, bin by bin: tests/test_gpu_minphase_kernels.py.
 """
 import functools
 import json
@@ -261,6 +265,88 @@ def test_a_floor_that_engages_on_a_comb():
         print(f"comb of {x.size} samples, N = {ref['n']}: {int(ref['floored'].sum())} floored bins, {excepted} within the "
               f"transform's error of the floor, device count {int(res.floored[ch])}")
     report("comb, floor -60 dB", worst)
+
+
+# ------------------------------------------------------------------------------------------------ polarity
+def _excess_bounds(ref, b, k, n):
+    """What hold() allows the unwrapped excess phase at k - 1, k, k + 1, and its count of ambiguous steps."""
+    bm = b.phi_min()
+    turns = np.count_nonzero(np.abs(np.diff(ref["wrapped"])) > np.pi)
+    unwrap = 2.0 * (turns + 64) * U * float(np.max(np.abs(ref["excess"])))
+    be = [bm + b.phi_rel(k + dk) + unwrap for dk in (-1, 0, 1)]
+    every = bm + b.phi_rel(np.arange(n // 2 + 1)) + unwrap
+    step = np.abs(R.wrap(np.diff(ref["wrapped"])))
+    return bm, be, int(np.count_nonzero(np.pi - step <= every[1:] + every[:-1]))
+
+
+def test_polarity_and_a_negative_sample_sum():
+    """A channel, its negation, a channel whose samples sum below zero, and one more such channel for every path the
+    first transform takes (N = 32 Bluestein, N = 64 the full-length direct transform, N = 32768 a half-length one of
+    several workgroups).  X_0 < 0 there: angle(X_0) is +pi by the +0.0 that numpy.fft.rfft leaves in Im X_0, and the unwrap
+    starts from that bin.  Every channel is held as it stands, and the unwrapped excess phase at the first grid point
+    is compared with the restatement's as a number, not modulo 2 pi: a -0.0 in the device's Im X_0 would move the whole
+    curve by 360 degrees."""
+    D = _mp()
+    eng = _eng()
+    a = channel(100, 71)
+    neg = (-a).astype(np.float32)
+    c = channel(257, 72, peak_at=4).copy()
+    c[4] = -5.0
+    c[:3] -= np.float32(0.5)
+    chans = [a, neg, c] + [(-channel(d, 73 + i)).astype(np.float32) for i, d in enumerate((5, 16, 4097))]
+    res = D.minphase_device(eng, eng.upload(chans), FS, D.MinPhaseSettings())
+    assert list(res.n_fft) == [512, 512, 2048, 32, 64, 32768] and list(res.centre) == [3, 3, 4, 3, 3, 3]
+    sums = [float(np.sum(x[:d].astype(np.float64))) for x, d in zip(chans, res.segment)]
+    assert sums[0] > 0.0 and all(v < 0.0 for v in sums[1:]), sums
+    out = D.minphase_results(res, FS, list("abcdef"))
+    held = []
+    for ch, x in enumerate(chans):
+        worst = {}
+        ref, b, _ = hold(res, ch, x, f"polarity, channel {ch} (sample sum {sums[ch]:.3g})", worst)
+        n, k = int(res.n_fft[ch]), res.bins[ch]
+        _, be, ambiguous = _excess_bounds(ref, b, k, n)
+        first = res.records[ch, 0, 6] - R.records(ref, k)[0, 6]
+        print(f"channel {ch}: sample sum {sums[ch]:.4g}, X_0 {ref['X'][0].real:.4g}, X_N/2 {ref['X'][-1].real:.4g}; unwrapped excess at "
+              f"the first grid point off by {first:.3g} rad ({abs(first) / be[1][0]:.3g} of its bound), ambiguous steps {ambiguous}")
+        if not ambiguous:
+            assert abs(first) <= be[1][0], (ch, first, be[1][0])
+        report(f"polarity, channel {ch}", worst)
+        held.append((ref, b, be, ambiguous))
+    # the negation against its original
+    assert bits(res.pmax[1:2])[0] == bits(res.pmax[0:1])[0] and res.floored[1] == res.floored[0]
+    assert np.array_equal(bits(res.records[1, :, 2:5]), bits(res.records[0, :, 2:5]))
+    assert np.array_equal(bits(res.records[1, :, :2]), bits(-res.records[0, :, :2]))
+    (_, b0, be0, amb0), (_, b1, be1, amb1) = held[0], held[1]
+    for q in range(3):
+        odd = R.wrap(res.records[1, :, 5 + q] - res.records[0, :, 5 + q] - np.pi)
+        assert np.all(np.abs(odd) <= 2.0 * np.maximum(be0[q], be1[q])), (q, float(np.max(np.abs(odd))))
+    if not (amb0 or amb1):
+        span_bound = 2.0 * np.degrees(2.0 * float(np.max(np.maximum(be0[1], be1[1]))))
+        assert abs(out[1].excess_phase_span_deg - out[0].excess_phase_span_deg) <= span_bound
+        tau_e = 2.0 * np.maximum(b0.delay(be0[0], be0[2]), b1.delay(be1[0], be1[2]))
+        assert np.all(np.abs(out[1].excess_group_delay_seconds - out[0].excess_group_delay_seconds) * FS <= tau_e)
+    tau_min = 2.0 * max(b0.delay(b0.phi_min(), b0.phi_min()), b1.delay(b1.phi_min(), b1.phi_min()))
+    assert np.all(np.abs(out[1].minimum_group_delay_seconds - out[0].minimum_group_delay_seconds) * FS <= tau_min)
+
+
+def test_the_response_against_the_restatement():
+    """minimum_phase_impulse_responses against minphase_ref.minimum_phase_ir on the mixed-length batch of
+    test_every_shape_against_the_restatement at oversample 4, per sample within Bounds.response."""
+    D = _mp()
+    lens = (5, 64, 100, 257, 4097, 16)
+    chans = [channel(n, i, peak_at=2 + i) for i, n in enumerate(lens)]
+    st = D.MinPhaseSettings(oversample=4)
+    hs = D.minimum_phase_impulse_responses(chans, FS, st)
+    worst = 0.0
+    for ch, (x, h) in enumerate(zip(chans, hs)):
+        d, n = R.sizes(x.size, 2 + ch, FS, 4)
+        assert h.dtype == np.float32 and h.shape == (d,) and d == lens[ch]
+        ref, b = reference(x, 2 + ch, d, n)
+        want = R.minimum_phase_ir(ref)
+        ratio = float(np.max(np.abs(h.astype(np.float64) - want) / b.response(ref, want)))
+        print(f"response, D = {d}, N = {n}: worst error / bound {ratio:.3g}")
+        worst = max(worst, ratio)
+    assert worst <= 1.0, worst
 
 
 # ------------------------------------------------------------------------------------------------ analytic cases
