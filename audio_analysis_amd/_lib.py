@@ -114,6 +114,9 @@ PROTOTYPES = {
     "ira_minphase_excess": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, vp, vp]),
     "ira_minphase_gather": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp]),
     "ira_minphase_spectrum": (i32, [vp, vp, vp, vp, vp, i32, i32, vp]),
+    "ira_mls_fold": (i32, [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp]),
+    "ira_mls_hadamard": (i32, [vp, i32, i32, vp]),
+    "ira_mls_finish": (i32, [vp, vp, i32, i32, i32, vp, vp, vp]),
 }
 
 

@@ -73,6 +73,9 @@ SOURCES = {
     "ira_burstdecay.hip": ["-ffp-contract=off"],
     # |X|^2 = re * re + im * im and the phase wrap d - 2 pi rint(d / 2 pi) round one operation at a time, like NumPy's
     "ira_minphase.hip": ["-ffp-contract=off"],
+    # the residual (x - Y / R)^2 and the response (W - W[0]) / scale round one operation at a time: the chain is held bit for
+    # bit to a NumPy restatement (the transform itself has only additions and subtractions, nothing to contract)
+    "ira_mls.hip": ["-ffp-contract=off"],
 }
 COMMON = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function"]
 

@@ -64,6 +64,16 @@ MINPHASE_MAX_LOG2 = 21        # IRA_MINPHASE_MAX_LOG2
 MINPHASE_MIN_N = 32           # the smallest transform of the chain
 MINPHASE_MIN_FLOOR_DB = -300.0  # IRA_MINPHASE_MIN_FLOOR_DB
 MINPHASE_SCRATCH_BYTES = 4 << 30  # minphase_cut: the device scratch of one sub-batch of the minimum-phase chain stays under this
+MLS_MIN_ORDER, MLS_MAX_ORDER = 2, 21  # IRA_MLS_MIN_ORDER, IRA_MLS_MAX_ORDER
+MLS_MAX_PERIODS = 1024        # IRA_MLS_MAX_PERIODS
+MLS_TILE_LOG2 = 12            # IRA_MLS_TILE_LOG2: the tile order T of ira_mls_hadamard
+MLS_FOLD_THREADS = 256        # IRA_MLS_FOLD_THREADS
+MLS_FOLD_BLOCKS = 128         # IRA_MLS_FOLD_BLOCKS: the most workgroups of ira_mls_fold along a channel
+MLS_SCRATCH_BYTES = 4 << 30   # mls.mls_device: the workspace of one chain of calls stays under this (256 channels at order 21)
+# feedback taps per order: a[n] = XOR over t of a[n - t]; each set gives the full period 2^m - 1 (tests walk them)
+MLS_TAPS = {2: (2, 1), 3: (3, 2), 4: (4, 3), 5: (5, 3), 6: (6, 5), 7: (7, 6), 8: (8, 6, 5, 4), 9: (9, 5), 10: (10, 7),
+            11: (11, 9), 12: (12, 6, 4, 1), 13: (13, 4, 3, 1), 14: (14, 5, 3, 1), 15: (15, 14), 16: (16, 15, 13, 4),
+            17: (17, 14), 18: (18, 11), 19: (19, 6, 2, 1), 20: (20, 17), 21: (21, 19)}
 
 
 def flat(a, dtype) -> Optional[np.ndarray]:
@@ -219,6 +229,108 @@ def minphase_cut(n_fft, scratch_bytes: int = MINPHASE_SCRATCH_BYTES) -> List[Tup
     if need.size:
         cuts.append((first, int(need.size)))
     return cuts
+
+
+def mls_taps(order: int, taps=None) -> Tuple[int, ...]:
+    """The feedback taps of an order as a descending tuple: MLS_TAPS[order], or the caller's -- distinct whole numbers
+    1 .. order with order among them.  ValueError for an order outside MLS_MIN_ORDER .. MLS_MAX_ORDER."""
+    if isinstance(order, bool) or not isinstance(order, (int, np.integer)) or not MLS_MIN_ORDER <= order <= MLS_MAX_ORDER:
+        raise ValueError(f"order must be a whole number {MLS_MIN_ORDER}..{MLS_MAX_ORDER}, got {order!r}")
+    if taps is None:
+        return MLS_TAPS[int(order)]
+    try:
+        tp = tuple(sorted({int(t) for t in taps if int(t) == t}, reverse=True))
+        ok = len(tp) == len(tuple(taps))
+    except (TypeError, ValueError):
+        ok, tp = False, ()
+    if not ok or len(tp) < 2 or tp[0] != order or tp[-1] < 1:
+        raise ValueError(f"taps must be distinct whole numbers 1..{order} with {order} among them, got {taps!r}")
+    return tp
+
+
+def _mls_recurrence(seed: np.ndarray, count: int, order: int, taps: Tuple[int, ...]) -> np.ndarray:
+    """v[n] = XOR over t of v[n - t] from the first `order` values on, `count` values in all.  Over GF(2) the feedback
+    polynomial satisfies p(x)^(2^j) = p(x^(2^j)), so v[n] = XOR over t of v[n - t 2^j] as well once n >= order 2^j: with the
+    largest such j a run of min(taps) 2^j values follows from the known ones in one vector operation."""
+    v = np.empty(max(count, order), dtype=seed.dtype)
+    v[:order] = seed
+    known = order
+    while known < count:
+        step = 1 << ((known // order).bit_length() - 1)
+        run = min(taps[-1] * step, count - known)
+        acc = v[known - taps[0] * step : known - taps[0] * step + run].copy()
+        for t in taps[1:]:
+            acc ^= v[known - t * step : known - t * step + run]
+        v[known : known + run] = acc
+        known += run
+    return v[:count]
+
+
+def mls_bits(order: int, taps=None) -> np.ndarray:
+    """One period of the sequence's bits, uint8 (2^order - 1,): a[n] = XOR over the taps t of a[n - t], a[0 .. order - 1] = 1.
+    The period is full when the taps are those of a primitive polynomial (mls_tables checks it)."""
+    tp = mls_taps(order, taps)
+    return _mls_recurrence(np.ones(order, dtype=np.uint8), (1 << order) - 1, order, tp)
+
+
+_MLS_TABLES: Dict[Tuple, Tuple[np.ndarray, np.ndarray]] = {}
+
+
+def mls_tables(order: int, taps=None) -> Tuple[np.ndarray, np.ndarray]:
+    """(G, out), int32 (P,) each, read-only, made once per (order, taps) -- the tables of ira_mls_fold and ira_mls_finish:
+      G[j]   = 1 << j for j < order, the XOR over t of G[j - t] after (the sequence's bits a[n + j] as a combination of the
+               state bits a[n .. n + order - 1])
+      S[i]   = sum over q < order of a[i + q] << q                        (the state at time i)
+      out[k] = S[(P - k) mod P]
+    With w[G[j]] = Y[j] the transform W = FWHT(w) holds c[k] = sum over n of s[n] Y[(n + k) mod P] at W[out[k]].
+    ValueError unless S is a permutation of 1 .. P, i.e. the taps give the full period."""
+    tp = mls_taps(order, taps)
+    key = (int(order), tp)
+    if key not in _MLS_TABLES:
+        m, p = int(order), (1 << int(order)) - 1
+        a = _mls_recurrence(np.ones(m, dtype=np.uint8), p + m, m, tp)
+        state = np.zeros(p, dtype=np.int32)
+        for q in range(m):
+            state |= a[q : q + p].astype(np.int32) << q
+        if not np.array_equal(np.bincount(state, minlength=p + 1)[1:], np.ones(p, dtype=np.int64)):
+            raise ValueError(f"taps {tp} do not give the full period {p} at order {m}")
+        g = _mls_recurrence(np.int32(1) << np.arange(m, dtype=np.int32), p, m, tp)
+        out = state[(p - np.arange(p)) % p]
+        g.setflags(write=False)
+        out.setflags(write=False)
+        _MLS_TABLES[key] = (g, out)
+    return _MLS_TABLES[key]
+
+
+def mls_fold_blocks(order: int) -> int:
+    """Workgroups of ira_mls_fold along a channel: ceil(P / MLS_FOLD_THREADS), at most MLS_FOLD_BLOCKS."""
+    return min(-(-((1 << int(order)) - 1) // MLS_FOLD_THREADS), MLS_FOLD_BLOCKS)
+
+
+def mls_scratch_bytes(nb: int, order: int) -> int:
+    """Device bytes of one chain of the three MLS calls on nb channels (the formula of include/ira.h): the workspace of
+    2^order doubles a channel and the fold's partial sums, a pair of doubles per channel and workgroup."""
+    return 8 * int(nb) * ((1 << int(order)) + 2 * mls_fold_blocks(order))
+
+
+def mls_sum_chain(order: int, periods: int) -> int:
+    """The longest chain of additions behind E or D of ira_mls_fold: a thread's own terms (ceil(P / (B MLS_FOLD_THREADS))
+    samples, R residual squares each), 6 levels of the wave's tree, 3 additions over the 4 waves, B over the workgroups."""
+    b = mls_fold_blocks(order)
+    per_thread = -(-((1 << int(order)) - 1) // (b * MLS_FOLD_THREADS))
+    return per_thread * max(1, int(periods)) + 6 + 3 + b
+
+
+def mls_pass_plan(order: int) -> List[Tuple[int, int]]:
+    """The passes of ira_mls_hadamard as (first bit, bits): the low min(order, MLS_TILE_LOG2) bits in LDS tiles, then the
+    bits above in passes of up to 8 (a tile of 2^a points x 2^(12 - a) columns keeps runs of 16 doubles); 9 bits go 5 + 4."""
+    plan = [(0, min(int(order), MLS_TILE_LOG2))]
+    lo, rem = MLS_TILE_LOG2, int(order) - MLS_TILE_LOG2
+    while rem > 0:
+        a = rem if rem <= 8 else (rem + 1) // 2
+        plan.append((lo, a))
+        lo, rem = lo + a, rem - a
+    return plan
 
 
 def lundeby_layout(base_off, base_len, chan_of_seg, blk_size, nblk, first_m) -> Dict[str, object]:

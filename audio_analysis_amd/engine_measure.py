@@ -1,15 +1,16 @@
 """
 The measure launchers of the device engine, one method per library call (or short chain of calls): ISO 3382-1 energy
 parameters and IACC, Lundeby, multi-slope fits, STI sums, harmonics, the echo criterion, echo density, reflections,
-transfer functions, FDW, burst decay, minimum phase, and the suffix-energy tables.  Each checks its tables on the host
-(engine_geometry holds what several share), allocates its outputs, uploads its job tables in one copy and enqueues the
-call.  MeasureLaunchers is a base class of engine.Engine, which supplies the plumbing (empty, out_view, job_tables, ...).
+transfer functions, FDW, burst decay, minimum phase, MLS measurement, and the suffix-energy tables.  Each checks its
+tables on the host (engine_geometry holds what several share), allocates its outputs, uploads its job tables in one copy
+and enqueues the call.  MeasureLaunchers is a base class of engine.Engine, which supplies the plumbing (empty, out_view,
+job_tables, ...).
 """
 from __future__ import annotations
 
 import math
 from dataclasses import dataclass
-from typing import TYPE_CHECKING, Dict, List, Sequence
+from typing import TYPE_CHECKING, Dict, List, Optional, Sequence
 
 import numpy as np
 
@@ -374,6 +375,73 @@ class MeasureLaunchers:
             d_so, d_nf = self.job_tables(spec_off, n_fft)
             check(self.lib.ira_minphase_spectrum(_ptr(g_dev), _ptr(tspec_dev), _ptr(d_so), _ptr(d_nf), _ptr(pmax_dev), n,
                                                  int(n_fft.max()), self.stream), "ira_minphase_spectrum")
+
+    # ------------------------------------------------------------------ MLS measurement (fast Hadamard transform)
+    def mls_device_tables(self, order: int, taps=None):
+        """(G, out) of mls_tables(order, taps) on the device, int32 (P,) each: made on the host and uploaded once per
+        engine and (order, taps)."""
+        tp = mls_taps(order, taps)
+        # (a copy goes up: the host's cached tables are read-only arrays)
+        return self._cached(("mls", int(order), tp),
+                            lambda: tuple(self._table_to_dev(v.copy()) for v in mls_tables(order, tp)))
+
+    @staticmethod
+    def _mls_sizes(nb: int, order: int, periods: Optional[int] = None) -> None:
+        mls_taps(order)                                             # (the order's own check)
+        if not 0 <= int(nb) <= 65535:
+            raise ValueError("at most 65535 channels per launch")
+        if periods is not None and not 1 <= int(periods) <= MLS_MAX_PERIODS:
+            raise ValueError(f"periods must be 1..{MLS_MAX_PERIODS}, got {periods}")
+
+    def mls_fold(self, x_dev, begin: np.ndarray, order: int, periods: int, taps=None):
+        """The periods of every channel folded into one and scattered through G (ira_mls_fold).  Channel e: periods * P
+        samples from begin[e] of x_dev (P = 2^order - 1; one order and one count of periods per call).  Returns (w float64
+        device (nb, 2^order): Y[n] at w[G[n]], 0 at w[0]; sums float64 device (nb, 2): E = sum Y^2 and the residual energy
+        D = sum (x - Y / periods)^2)."""
+        t = self.torch
+        begin = flat(begin, np.int64)
+        nb, order, periods = int(begin.size), int(order), int(periods)
+        self._mls_sizes(nb, order, periods)
+        if nb and (begin.min() < 0 or int(begin.max()) + periods * ((1 << order) - 1) > int(x_dev.numel())):
+            raise ValueError("every channel's periods must lie inside x_dev")
+        w = self.out_view(t.float64, nb, 1 << order)
+        sums = self.out_view(t.float64, nb, 2)
+        if nb:
+            g_dev, _ = self.mls_device_tables(order, taps)
+            scratch = self.empty(2 * nb * mls_fold_blocks(order), t.float64)
+            d_begin, = self.job_tables(begin)
+            with self.tagged(f"[{order}]"):
+                check(self.lib.ira_mls_fold(_ptr(x_dev), _ptr(d_begin), nb, order, periods, _ptr(g_dev), _ptr(w), _ptr(sums),
+                                            _ptr(scratch), self.stream), "ira_mls_fold")
+        return w, sums
+
+    def mls_hadamard(self, w_dev, nb: int, order: int) -> None:
+        """The natural-order Walsh-Hadamard transform of the nb rows of 2^order doubles of w_dev, in place, stages
+        h = 1, 2, 4 .. in that order (ira_mls_hadamard; mls_pass_plan(order) says in how many passes)."""
+        nb, order = int(nb), int(order)
+        self._mls_sizes(nb, order)
+        if int(w_dev.numel()) < nb << order:
+            raise ValueError("w_dev must hold nb rows of 2^order doubles")
+        if nb:
+            with self.tagged(f"[{order}]"):
+                check(self.lib.ira_mls_hadamard(_ptr(w_dev), nb, order, self.stream), "ira_mls_hadamard")
+
+    def mls_finish(self, w_dev, nb: int, order: int, periods: int, h_dev, h_off: np.ndarray, taps=None) -> None:
+        """h[k] = float32((W[out[k]] - W[0]) / (2^order periods)), k < P, of every row of the transformed workspace, written
+        at h_off[e] of h_dev (float32 device); nothing else of h_dev is touched (ira_mls_finish)."""
+        nb, order, periods = int(nb), int(order), int(periods)
+        h_off = flat(h_off, np.int64)
+        self._mls_sizes(nb, order, periods)
+        if h_off.size != nb or int(w_dev.numel()) < nb << order:
+            raise ValueError("h_off must be (nb,) and w_dev hold nb rows of 2^order doubles")
+        if nb and (h_off.min() < 0 or int(h_off.max()) + (1 << order) - 1 > int(h_dev.numel())):
+            raise ValueError("every response must lie inside h_dev")
+        if nb:
+            _, out_dev = self.mls_device_tables(order, taps)
+            d_off, = self.job_tables(h_off)
+            with self.tagged(f"[{order}]"):
+                check(self.lib.ira_mls_finish(_ptr(w_dev), _ptr(out_dev), nb, order, periods, _ptr(h_dev), _ptr(d_off),
+                                              self.stream), "ira_mls_finish")
 
     # ------------------------------------------------------------------ dual-channel spectral sums (Welch H1 / H2)
     def cross_spectra(self, x_dev, x_off: np.ndarray, y_off: np.ndarray, n: np.ndarray, n_fft: int, hop: int,

@@ -1078,6 +1078,44 @@ int32_t ira_minphase_gather(const double* spec_dev, const double* tspec_dev, con
 int32_t ira_minphase_spectrum(double* g_dev, const double* tspec_dev, const int64_t* spec_off_dev, const int32_t* nfft_dev,
                               const double* pmax_dev, int32_t nb, int32_t max_nfft, void* stream);
 
+/* ---- MLS impulse-response measurement: circular correlation with a maximum-length sequence by the fast Hadamard transform ---
+ * Nothing in the reference computes it; the entry points replace no reference function.  Host side, with the definition
+ * pinned: audio_analysis_amd/analyse/mls.py (`python -m analyse.mls`); the tables are made by engine_geometry.mls_tables.
+ * One order m per call (IRA_MLS_MIN_ORDER .. IRA_MLS_MAX_ORDER), P = 2^m - 1, R = periods (1 .. IRA_MLS_MAX_PERIODS, one
+ * value per call).  Channel e < nb reads the R P samples x_dev[begin_dev[e] ..] (int64 offsets into x_dev) and owns row e of
+ * the workspace w_dev, 2^m doubles at w_dev + e 2^m:
+ *     Y[n]  = sum over r = 0 .. R-1, ascending from 0.0, of (double) x[b + r P + n],  n < P
+ *     w     = zeros(2^m);  w[G[n]] = Y[n]            (g_dev: int32 (P,), a permutation of 1 .. P)              (ira_mls_fold)
+ *     E     = sum Y[n]^2;  D = sum over n and r of ((double) x[b + r P + n] - Y[n] / R)^2, 0 when R = 1         (ira_mls_fold)
+ *     W     = the Walsh-Hadamard transform of w in natural order: stages h = 1, 2, 4 .. 2^(m-1) in that order, each
+ *             (lo, hi) -> (lo + hi, lo - hi) with lo the lower index                                        (ira_mls_hadamard)
+ *     h[k]  = float32((W[out[k]] - W[0]) / (double)(2^m R)),  k < P   (out_dev: int32 (P,), a permutation of 1 .. P), written
+ *             at h_dev[h_off_dev[e] + k]; nothing else of h_dev is touched                                    (ira_mls_finish)
+ * W[0] is sum Y, so h is the circular correlation with the +-1 sequence with its DC value restored; the stage order fixes
+ * every rounding, so W equals a NumPy restatement of the same stages bit for bit.
+ * ira_mls_fold: sums_dev[2 e] = E, sums_dev[2 e + 1] = D.  Thread t of workgroup j of a channel (IRA_MLS_FOLD_THREADS
+ *   threads; B = min(ceil(P / IRA_MLS_FOLD_THREADS), IRA_MLS_FOLD_BLOCKS) workgroups) takes n = (j + i B)
+ *   IRA_MLS_FOLD_THREADS + t, i ascending, and adds Y^2 -- and, r ascending within n, the residual squares -- to its own
+ *   sums; a workgroup adds its threads' sums in a fixed tree (xor butterfly over 64 lanes, then the 4 waves ascending) and
+ *   writes the pair to scratch_dev; a second launch adds a channel's B pairs ascending from 0.0.  No float atomics: the sums
+ *   are the same in every call and batch.  scratch_dev: 2 nb B doubles; engine_geometry.mls_scratch_bytes(nb, m) =
+ *   8 nb (2^m + 2 B) is the workspace and the scratch together.
+ * ira_mls_hadamard: tiles of 2^IRA_MLS_TILE_LOG2 doubles in LDS, 16 elements a thread in registers.  m <= 12: one pass;
+ *   13 .. 20: a second over the bits 12 .. m-1; 21: 12 + 5 + 4 bits (engine_geometry.mls_pass_plan).
+ * Table values are masked to m bits before they index a row.  Checked before anything touches a device (IRA_E_NULL /
+ * IRA_E_SIZE): NULL pointers, nb 0..65535, the order, the periods.  nb = 0: IRA_OK, no launch.  Vector stores only. */
+#define IRA_MLS_MIN_ORDER 2
+#define IRA_MLS_MAX_ORDER 21
+#define IRA_MLS_MAX_PERIODS 1024
+#define IRA_MLS_TILE_LOG2 12              /* the tile order T of ira_mls_hadamard: 2^12 doubles = 32 KiB of LDS */
+#define IRA_MLS_FOLD_THREADS 256
+#define IRA_MLS_FOLD_BLOCKS 128           /* the most workgroups of ira_mls_fold (and ira_mls_finish) along a channel */
+int32_t ira_mls_fold(const float* x_dev, const int64_t* begin_dev, int32_t nb, int32_t order, int32_t periods,
+                     const int32_t* g_dev, double* w_dev, double* sums_dev, double* scratch_dev, void* stream);
+int32_t ira_mls_hadamard(double* w_dev, int32_t nb, int32_t order, void* stream);
+int32_t ira_mls_finish(const double* w_dev, const int32_t* out_dev, int32_t nb, int32_t order, int32_t periods, float* h_dev,
+                       const int64_t* h_off_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
