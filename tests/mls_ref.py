@@ -12,6 +12,9 @@ What is here
   * direct_ld: c[k] = sum over n of s[n] Y[(n + k) mod P] and h = (c - sum Y) / (2^m R) in numpy.longdouble, O(P^2), from
     the same float64 Y;
   * grid_int64: the same in int64 for samples on the PCM16 grid k / 32768, exact up to the one division;
+  * sampled_ld: the same h at chosen positions from math.fsum sums, O(P) a position, for the orders direct_ld cannot afford;
+  * sparse_response / sparse_period: twelve taps k / 256 and their period under the amplitude-0.5 sequence, for which the
+    chain is exact and gives 0.5 h back;
   * bound(m, R, Y) for inputs off the grid.
 
 The bound (u = 2^-53, gamma_k = k u / (1 - k u)).  Every W[i] is a signed sum of the 2^m entries of w formed by m stages of
@@ -175,6 +178,44 @@ def grid_int64(x, b, order, periods, taps=None):
 def bound(order, periods, y):
     """gamma_(m+2) sum |Y| / (2^m R): see the module's docstring."""
     return gamma(order + 2) * float(np.sum(np.abs(np.asarray(y, dtype=np.float64)))) / float((1 << order) * periods)
+
+
+def sparse_response(order, seed, taps=12):
+    """A response of `taps` non-zero values k / 256, 0 < |k| <= 255, at seeded indices with 0 and P - 1 among them."""
+    p = (1 << order) - 1
+    rng = np.random.default_rng(seed)
+    idx = np.concatenate([[0, p - 1], 1 + rng.choice(p - 2, taps - 2, replace=False)])
+    h = np.zeros(p)
+    h[idx] = rng.integers(1, 256, taps) * rng.choice([-1, 1], taps) / 256.0
+    return h
+
+
+def sparse_period(h, s, amplitude=0.5):
+    """One steady-state period y[n] = sum over j of h[j] amplitude s[(n - j) mod P] of a sparse h, tap by tap.  For
+    sparse_response and amplitude 0.5 every partial sum is a multiple of 2^-9 below 2^3: exact, in float32 as well."""
+    s = np.asarray(s, dtype=np.float64)
+    y = np.zeros(h.size)
+    for j in np.flatnonzero(h):
+        y += h[j] * amplitude * np.roll(s, j)
+    return y
+
+
+def sample_positions(order, seed, count):
+    """k = 0, 1, P - 1 and count - 3 seeded ones."""
+    p = (1 << order) - 1
+    rng = np.random.default_rng(seed)
+    return sorted({0, 1, p - 1} | {int(k) for k in 2 + rng.choice(p - 3, count - 3, replace=False)})
+
+
+def sampled_ld(y, s, order, periods, ks):
+    """h[k] at the positions ks from correctly rounded sums: c[k] = math.fsum of the signed Y (each term s[n] Y[(n + k) mod P]
+    is +-Y, exact), sum Y by math.fsum, then (c - sum Y) / (2^m R) in long double.  O(P) a position, any order."""
+    import math
+    y = np.asarray(y, dtype=np.float64)
+    s = np.asarray(s, dtype=np.float64)
+    sy = np.longdouble(math.fsum(y.tolist()))
+    scale = np.longdouble((1 << order) * periods)
+    return np.array([(np.longdouble(math.fsum((s * np.roll(y, -k)).tolist())) - sy) / scale for k in ks], dtype=np.longdouble)
 
 
 def bits_of(a):

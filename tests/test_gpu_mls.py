@@ -1,6 +1,8 @@
 """MLS measurement through the public functions of analyse/mls.py on the GPU, against tests/mls_ref.py: a known response
 recovered bit for bit from recordings on the PCM16 grid, the period signal-to-noise ratio, silence and a NaN channel, the
-epilogue's rules, independence of the batching, and the command line's round trip."""
+epilogue's rules, independence of the batching, the command line's round trip, and the measurement orders 14 .. 21: a sparse
+response on the 2^-9 grid recovered exactly (a closed form), Gaussian recordings bit for bit against the restatement and, at
+sampled positions, within mls_ref.bound of correctly rounded sums."""
 import json
 
 import numpy as np
@@ -121,12 +123,11 @@ def test_epilogue_follows_deconv_finish(eng):
     assert float(np.abs(got[1]).max()) < 0.5                 # the quiet channel keeps its level relative to the loud one
 
 
-def test_results_do_not_depend_on_the_batching(eng, monkeypatch):
+def _batching(eng, monkeypatch, order):
     from audio_analysis_amd import engine as E
     from audio_analysis_amd.analyse import mls as D
-    order = 8
     p = (1 << order) - 1
-    rng = np.random.default_rng(8)
+    rng = np.random.default_rng(order)
     # different lengths: R = 2, 4, 2, 3, 4 -- the chains are grouped by R
     chans = [rng.standard_normal((r + 1) * p + k).astype(np.float32) for k, r in enumerate((2, 4, 2, 3, 4))]
     st = D.MlsSettings(order=order)
@@ -140,6 +141,82 @@ def test_results_do_not_depend_on_the_batching(eng, monkeypatch):
         assert np.array_equal(R.bits_of(whole[c]), R.bits_of(one[0])) and np.array_equal(R.bits_of(cut[c]), R.bits_of(one[0]))
         assert res[c].period_snr_db == res_one[0].period_snr_db == res_cut[c].period_snr_db
         assert res[c].peak_samples == res_one[0].peak_samples
+
+
+def test_results_do_not_depend_on_the_batching(eng, monkeypatch):
+    _batching(eng, monkeypatch, 8)
+
+
+def test_results_do_not_depend_on_the_batching_at_order_16(eng, monkeypatch):
+    """Two passes of the transform and two samples a thread in the fold and the finish."""
+    _batching(eng, monkeypatch, 16)
+
+
+# ------------------------------------------------------------------------------------------- the measurement orders
+MEASUREMENT_ORDERS = tuple(range(14, 22))           # 0.3 s to 44 s of sequence at 48 kHz
+
+
+def _sequence(order):
+    from audio_analysis_amd.engine import mls_bits       # tests/test_mls_cpu.py holds it to the plain recurrence up here
+    return 1 - 2 * mls_bits(order).astype(np.int64)
+
+
+@pytest.mark.parametrize("order", MEASUREMENT_ORDERS)
+def test_a_sparse_response_comes_back_exactly(eng, order):
+    """Two channels, each R periods (3; 2 at order 21) of the amplitude-0.5 sequence circularly convolved with twelve taps
+    k / 256, indices 0 and P - 1 among them.  Every intermediate of the chain is an integer multiple of 2^-9 far below 2^53
+    (|Y| < 2^5, |W| < 2^(m + 5)), so nothing rounds and the response is 0.5 h exactly, zeros included.  The reference is the
+    closed form: it owes nothing to mls_ref.fwht."""
+    from audio_analysis_amd.analyse import mls as D
+    p, periods = (1 << order) - 1, 2 if order == 21 else 3
+    s = _sequence(order)
+    hs_true = [R.sparse_response(order, 10 * order + c) for c in range(2)]
+    recs = []
+    for h in hs_true:
+        y = R.sparse_period(h, s)
+        assert np.count_nonzero(h) == 12 and h[0] != 0.0 and h[p - 1] != 0.0
+        assert np.array_equal(np.rint(y * 512.0), y * 512.0) and np.abs(y).max() <= 6.0
+        recs.append(np.tile(y.astype(np.float32), periods + 1))
+    hs, res = D.mls_impulse_responses(recs, FS, D.MlsSettings(order=order, **RAW), eng=eng)
+    for c in range(2):
+        assert res[c].periods == periods and res[c].begin_samples == p
+        want = (0.5 * hs_true[c]).astype(np.float32)
+        differ = R.bits_of(hs[c]) != R.bits_of(want)
+        assert not differ.any(), f"order {order} channel {c}: {int(differ.sum())} samples differ, first at {int(np.argmax(differ))}"
+        assert res[c].period_snr_db == np.inf                # identical periods: D = 0
+
+
+@pytest.mark.parametrize("order", MEASUREMENT_ORDERS)
+def test_gaussian_recordings_at_the_measurement_orders(eng, order):
+    """Off the grid, R = 2, two channels: the response equals the restatement's to the bit, and at k = 0, 1, P - 1 and seeded
+    positions the restatement's float64 value lies within mls_ref.bound of correctly rounded sums (mls_ref.sampled_ld).
+    The device's float32 is that float64 rounded once more: half an ulp, 2^-24 |h|, on top.
+    Measured on an MI355X: equal to the bit at every order; the worst sampled error over the bound was 0 at orders 14, 15 and
+    16 (signed sums of that few float32 values still fit a float64 exactly at the sampled positions), 1.8e-4, 1.7e-4, 1.7e-4, 7.9e-5 and 1.1e-4 at
+    orders 17 .. 21."""
+    from audio_analysis_amd.analyse import mls as D
+    from audio_analysis_amd.engine import mls_tables
+    if np.finfo(np.longdouble).eps >= 2.0 ** -60:
+        pytest.skip("numpy.longdouble is no wider than float64 here")
+    p, periods = (1 << order) - 1, 2
+    rng = np.random.default_rng(2000 + order)
+    recs = [rng.standard_normal((periods + 1) * p).astype(np.float32) for _ in range(2)]
+    hs, res = D.mls_impulse_responses(recs, FS, D.MlsSettings(order=order, **RAW), eng=eng)
+    s = _sequence(order)
+    worst = 0.0
+    for c in range(2):
+        assert res[c].periods == periods
+        ch = R.fast_chain(recs[c], p, order, periods, tabs=mls_tables(order))
+        differ = R.bits_of(hs[c]) != R.bits_of(ch["h"])
+        assert not differ.any(), f"order {order} channel {c}: {int(differ.sum())} samples differ, first at {int(np.argmax(differ))}"
+        ks = R.sample_positions(order, 100 * order + c, 8 if c == 0 else 4)
+        ref = R.sampled_ld(ch["Y"], s, order, periods, ks)
+        bound = R.bound(order, periods, ch["Y"])
+        err = np.abs(ch["h64"][ks].astype(np.longdouble) - ref)
+        worst = max(worst, float(err.max() / bound))
+        assert np.all(err <= bound)
+        assert np.all(np.abs(hs[c][ks].astype(np.longdouble) - ref) <= bound + 2.0 ** -24 * np.abs(ref))
+    print(f"order {order} R {periods}: worst sampled error {worst:.3g} of the bound")
 
 
 def test_generate_then_deconvolve_round_trips_a_room(eng, tmp_path, capsys):

@@ -165,6 +165,57 @@ def test_fast_chain_recovers_a_known_response_exactly():
         assert np.array_equal(got, h.astype(np.float64))
 
 
+MEASUREMENT_ORDERS = tuple(range(14, 22))           # 0.3 s to 44 s of sequence at 48 kHz: beyond what direct_ld can afford
+
+
+@pytest.mark.parametrize("order", MEASUREMENT_ORDERS)
+def test_fast_chain_at_sampled_positions_of_the_measurement_orders(order):
+    """Gaussian float32 input, R = 2: at k = 0, 1, P - 1 and seeded positions the float64 chain lies within
+    gamma_(m+2) sum |Y| / (2^m R) of correctly rounded sums (mls_ref.sampled_ld, O(P) a position).  The tables are the
+    engine's (the plain loops of mls_ref.tables take seconds up here); the sequence is checked against the plain recurrence."""
+    if np.finfo(np.longdouble).eps >= 2.0 ** -60:
+        pytest.skip("numpy.longdouble is no wider than float64 here")
+    from audio_analysis_amd.engine import mls_bits, mls_tables
+    p, periods = (1 << order) - 1, 2
+    a = mls_bits(order)
+    assert np.array_equal(a, R.bits(order))
+    s = 1 - 2 * a.astype(np.int64)
+    x = np.random.default_rng(1000 + order).standard_normal(p + periods * p).astype(np.float32)
+    ch = R.fast_chain(x, p, order, periods, tabs=mls_tables(order))
+    ks = R.sample_positions(order, order, 16 if order < 19 else 8)
+    assert {0, 1, p - 1} <= set(ks) and len(ks) >= 8
+    err = np.abs(ch["h64"][ks].astype(np.longdouble) - R.sampled_ld(ch["Y"], s, order, periods, ks))
+    bound = R.bound(order, periods, ch["Y"])
+    print(f"order {order} R {periods}: worst sampled error {float(err.max()):.3e}, {float(err.max() / bound):.3g} of the bound")
+    assert np.all(err <= bound)
+
+
+def test_sampled_sums_equal_the_direct_sums_where_both_can_run():
+    if np.finfo(np.longdouble).eps >= 2.0 ** -60:
+        pytest.skip("numpy.longdouble is no wider than float64 here")
+    order, periods = 10, 3
+    p = (1 << order) - 1
+    y = R.fold(np.random.default_rng(5).standard_normal(periods * p).astype(np.float32), 0, p, periods)
+    ks = R.sample_positions(order, 1, 12)
+    a, b = R.sampled_ld(y, R.sequence(order), order, periods, ks), R.direct_ld(y, order, periods)[ks]
+    # direct_ld adds P + 1 terms in long double (2^-64 each); sampled_ld rounds c and sum Y to float64 once (2^-53 each)
+    assert np.max(np.abs(a - b)) <= ((p + 2) * 2.0 ** -64 + 2.0 * 2.0 ** -53) * np.abs(y).sum() / ((1 << order) * periods)
+
+
+@pytest.mark.parametrize("order", (14, 16, 21))
+def test_fast_chain_recovers_a_sparse_response_exactly_at_measurement_orders(order):
+    """Twelve taps k / 256 under the amplitude-0.5 sequence: every intermediate of the chain is an integer multiple of 2^-9
+    below 2^(m + 5), so 0.5 h comes back exactly, zeros included -- a reference that owes nothing to fwht."""
+    from audio_analysis_amd.engine import mls_bits, mls_tables
+    p, periods = (1 << order) - 1, 2 if order == 21 else 3
+    h = R.sparse_response(order, order)
+    assert np.count_nonzero(h) == 12 and h[0] != 0.0 and h[p - 1] != 0.0 and np.array_equal(np.rint(h * 256.0), h * 256.0)
+    y = R.sparse_period(h, 1 - 2 * mls_bits(order).astype(np.int64))
+    assert np.array_equal(np.rint(y * 512.0), y * 512.0) and np.array_equal(y.astype(np.float32).astype(np.float64), y)
+    ch = R.fast_chain(np.tile(y.astype(np.float32), periods), 0, order, periods, tabs=mls_tables(order))
+    assert np.array_equal(R.bits_of(ch["h64"]), R.bits_of(0.5 * h)) and np.array_equal(R.bits_of(ch["h"]), R.bits_of((0.5 * h).astype(np.float32)))
+
+
 def test_the_engine_tables_drive_the_restated_chain():
     """engine.mls_tables is what the kernels read: the chain with them equals the chain with the plain-loop tables."""
     from audio_analysis_amd.engine import mls_tables
