@@ -68,6 +68,10 @@ struct SmoothPlan {
   int pairs;                        // forward transform of an interleaved real signal with the untangling FUSED into pass 2:
                                     // the intermediate is stored in MIRROR-PAIR tiles -- tile 0 = rows {0, n1/2}, tile p =
                                     // rows {p, n1 - p} (n1 even, c2 = 2) -- so that Z[k] and Z[n - k] meet in one workgroup
+  int pq;                           // pairs: the first 2 pq of the n1/2 - 1 mirror pairs p >= 1 sit two to a tile, QUAD tile q =
+                                    // rows {p, p + 1, n1 - p - 1, n1 - p}, p = 2 q + 1 (pass 2 then stores X[k], X[k + 1] as one
+                                    // 32-byte run on either side); an odd pair n1/2 - 1 keeps a two-row tile behind them.
+                                    // Tile order in the intermediate: {0, n1/2}, the quads, the odd pair (row_of, pass 1)
   double pstep_c, pstep_s;          // pairs: cos / sin of -pi (256 / 2) / n2, the step of W_2n^k between a thread's
                                     // consecutive pass-2 elements (k advances by 128 n1)
   int sparse_q;                     // narrow-band path: jobs whose band hull spans <= sparse_q * n2 bins skip pass 1 (0: off)
@@ -606,14 +610,23 @@ __global__ __launch_bounds__(SM_THREADS, ((MODE == SM_SIGNAL || !HALF) ? 6 : 5))
   IRA_STAMP(P.stamp, s2);
   cd* w = work + (long long)e * P.n;
   const int C2 = P.c2;
-  // SM_SIGNAL with HALF = the MIRROR-PAIR layout of the intermediate (SmoothPlan::pairs): position j of a column stands for
-  // row k1 = j/2 (even j; tile j/2, member 0) or its mirror n1 - j/2 (odd j; member 1) -- j = 0 / 1 are the two rows that
-  // mirror themselves, 0 and n1/2 -- so that neighbouring lanes write the two members of one tile: 32 contiguous bytes.
+  // SM_SIGNAL with HALF = the MIRROR-PAIR layout of the intermediate (SmoothPlan::pairs, pq): position j of a column is
+  // member m of a pass-2 tile -- j = 0 / 1 the two rows that mirror themselves, 0 and n1/2; then four positions per quad
+  // tile, rows {p, p + 1, n1 - p - 1, n1 - p}; last the two of an odd pair -- so that neighbouring lanes write the members
+  // of one tile: 32 or 64 contiguous bytes.  The tile of position j starts at N2 (j - m).
   constexpr bool PAIRS = MODE == SM_SIGNAL && HALF;
+  const int Q4 = 4 * P.pq;
+  auto pair_member = [&](int j) -> int {                   // m, with bit 2 set for a quad tile
+    const int t = j - 2;
+    return t < 0 ? j : (t < Q4 ? 4 + (t & 3) : t - Q4);
+  };
   auto row_of = [&](int j) -> int {
     if (!PAIRS) return j;
-    const int q = j >> 1;
-    return (j & 1) ? (q == 0 ? (N1 >> 1) : N1 - q) : q;
+    if (j < 2) return j == 0 ? 0 : (N1 >> 1);
+    const int t = j - 2;
+    if (t >= Q4) return t == Q4 ? (N1 >> 1) - 1 : (N1 >> 1) + 1;
+    const int p = 2 * (t >> 2) + 1, m = t & 3;
+    return m < 2 ? p + m : N1 - p - (3 - m);
   };
   for (int base = 0; base < total1; base += SM_THREADS * SM_UC) {
     cd th[SM_UC], tl[SM_UC];                               // the twiddle factors W_n^(k1 n2) of the batch: loads first
@@ -634,9 +647,11 @@ __global__ __launch_bounds__(SM_THREADS, ((MODE == SM_SIGNAL || !HALF) ? 6 : 5))
       if (i >= total1) continue;
       const int c = (int)fdiv((unsigned)i, P.dn1), j = i - c * N1, k1 = row_of(j);
       const int n2 = n2_0 + c;
-      const int kt = PAIRS ? (j >> 1) : (int)fdiv((unsigned)k1, P.dc2);                 // tile of k1 in pass 2
-      const int km = PAIRS ? (j & 1) : k1 - kt * C2;                                     // and its place in the tile
-      w[(IRA_ABL(P.ablate & 2)) ? (long long)bx * total1 + i : (long long)kt * ((long long)N2 * C2) + (long long)n2 * C2 + km] =
+      const int pm = PAIRS ? pair_member(j) : 0;
+      const int ct = PAIRS ? ((pm & 4) ? 4 : 2) : C2;                                    // rows of k1's tile in pass 2,
+      const int km = PAIRS ? (pm & 3) : k1 - (int)fdiv((unsigned)k1, P.dc2) * C2;        // its place in the tile
+      const int k0 = PAIRS ? j - km : k1 - km;                                           // and the rows in front of the tile
+      w[(IRA_ABL(P.ablate & 2)) ? (long long)bx * total1 + i : (long long)k0 * N2 + (long long)n2 * ct + km] =
           ira::cmul(r[c * LD + ((IRA_ABL(P.ablate & 128)) ? k1 : dif_slot(k1, P.p1))], ira::cmul(th[u], tl[u]));
     }
   }
@@ -710,11 +725,14 @@ template <int OUT>
 __global__ __launch_bounds__(SM_THREADS) void smooth_rows_kernel(SmoothPlan P, SJobs J, const cd* __restrict__ work) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   cd* a = reinterpret_cast<cd*>(smem);
-  const int C = P.c2, N1 = P.n1, N2 = P.n2;
+  const int N1 = P.n1, N2 = P.n2;
   const int LD = P.ld2;                                    // column stride in LDS
-  cd* twl = a + (size_t)C * LD;
   unsigned bx, by;
   ira::xcd_remap(bx, by);
+  // SM_OUT_SPEC_PAIRS: workgroup 0 has the tile of rows {0, n1/2}, 1 .. pq the quad tiles, pq + 1 the odd pair (SmoothPlan::pq)
+  const bool quad = OUT == SM_OUT_SPEC_PAIRS && bx >= 1u && bx <= (unsigned)P.pq;
+  const int C = OUT == SM_OUT_SPEC_PAIRS ? (quad ? 4 : 2) : P.c2;
+  cd* twl = a + (size_t)C * LD;
   const int e = (int)by, tid = threadIdx.x;
   const int k1_0 = (int)bx * C;
   const cd* w = work + (long long)e * P.n;
@@ -739,6 +757,8 @@ __global__ __launch_bounds__(SM_THREADS) void smooth_rows_kernel(SmoothPlan P, S
   }
   const cd twv = twiddle_lds_fetch(P.t2, N2, tid);        // issued first: shares the round trip of the tile load below
   const int total2 = N2 * C;
+  // first element of the tile: the pair tiles lie behind 0 (workgroup 0) or 4 bx - 2 (every other workgroup) rows
+  const long long tile0 = OUT == SM_OUT_SPEC_PAIRS ? (long long)N2 * (bx == 0u ? 0 : 4 * (int)bx - 2) : (long long)bx * total2;
   for (int base = 0; base < total2; base += SM_THREADS * SM_U) {
     // Clamped index for the load AND for the LDS store (a lane past the end rewrites the last element with its own value):
     // behind an `if (i < total2)` the compiler sinks each load into its store's branch -- eight serial round trips.
@@ -747,7 +767,7 @@ __global__ __launch_bounds__(SM_THREADS) void smooth_rows_kernel(SmoothPlan P, S
     for (int u = 0; u < SM_U; ++u) {
       int i = base + tid + SM_THREADS * u;
       i = i < total2 ? i : total2 - 1;
-      raw[u] = w[(long long)bx * total2 + i];               // this tile: n2 * C + c, contiguous
+      raw[u] = w[tile0 + i];                                // this tile: n2 * C + c, contiguous
     }
     // (nothing may be scheduled across this line: left alone, hipcc 7.2 sinks every load to its LDS store to save
     // registers -- load, s_waitcnt vmcnt(0), ds_write, eight times in a row: eight serial memory round trips per tile,
@@ -763,7 +783,8 @@ __global__ __launch_bounds__(SM_THREADS) void smooth_rows_kernel(SmoothPlan P, S
       // sinking happens before scheduling).  Same family as the `if (i < total)` guards of round 2, DESIGN.md section 4.3.
       // Worth 1.6 % here (0.976 -> 0.960 ms per 64 channels): the tile's loads are not what its workgroup waits for.  (The
       // same rewrite of fdiv() itself costs the pass-1 kernels 10-17 more spilled registers and loses 3 %.)
-      const int row = (int)(__umulhi((unsigned)i, P.dc2.magic) + (unsigned)i * P.c2_one);
+      const int row = OUT == SM_OUT_SPEC_PAIRS ? i >> (quad ? 2 : 1)
+                                               : (int)(__umulhi((unsigned)i, P.dc2.magic) + (unsigned)i * P.c2_one);
       a[(i - row * C) * LD + row] = raw[u];
     }
   }
@@ -781,7 +802,45 @@ __global__ __launch_bounds__(SM_THREADS) void smooth_rows_kernel(SmoothPlan P, S
     // (round 3 wrote Z out and read it back twice in a separate pass, smooth_half_split_kernel: 11.5 MB per 10 s channel).
     // W_2n^k = exp(-i pi k / n) along a thread's elements (k2 advances by 128: k by 128 n1) by rotation from an exactly
     // reduced start value; a handful of steps.
-    const int p = (int)bx;
+    if (quad) {
+      // Rows {p, p + 1, n1 - p - 1, n1 - p} = members 0 .. 3; member m mirrors 3 - m.  Lane parity picks the row of each
+      // adjacent couple, so that two neighbouring lanes store X[k], X[k + 1]: one 32-byte run on the row side and one on
+      // the mirror side (a lone 16-byte bin per lane left every 128-byte line of the spectrum to eight workgroups).  A lane
+      // carries the rotation of both its rows: each (row, k2) is on the chain it has in a two-row tile -- the same start
+      // k2 = tid / 2, the same steps of 128.
+      const int p = 2 * (int)bx - 1, m = tid & 1;
+      const long long k_lo = (long long)(p + m) + (long long)N1 * (tid >> 1);
+      const long long k_hi = (long long)(N1 - p - 1 + m) + (long long)N1 * (tid >> 1);
+      double cs = 1.0, sn = 0.0, ch = 1.0, sh = 0.0;
+      sincospi(-(double)k_lo / (double)n, &sn, &cs);
+      sincospi(-(double)k_hi / (double)n, &sh, &ch);
+      const cd* r_lo = r + m * LD;
+      const cd* r_hi = r + (2 + m) * LD;
+      const cd* m_lo = r + (3 - m) * LD;
+      const cd* m_hi = r + (1 - m) * LD;
+      cd* o_lo = J.spec_out + out1 + k_lo;
+      cd* o_hi = J.spec_out + out1 + k_hi;
+      for (int k2 = tid >> 1; k2 < N2; k2 += SM_THREADS / 2) {
+        const int s = dif_slot(k2, P.p2), sm = dif_slot(N2 - 1 - k2, P.p2);
+        {
+          const auto [ev, od] = ira::hermitian_parts(r_lo[s], m_lo[sm]);
+          *o_lo = cd{ev.re + (cs * od.re - sn * od.im), ev.im + (cs * od.im + sn * od.re)};
+          const double nc = cs * P.pstep_c - sn * P.pstep_s;
+          sn = sn * P.pstep_c + cs * P.pstep_s;
+          cs = nc;
+        }
+        {
+          const auto [ev, od] = ira::hermitian_parts(r_hi[s], m_hi[sm]);
+          *o_hi = cd{ev.re + (ch * od.re - sh * od.im), ev.im + (ch * od.im + sh * od.re)};
+          const double nc = ch * P.pstep_c - sh * P.pstep_s;
+          sh = sh * P.pstep_c + ch * P.pstep_s;
+          ch = nc;
+        }
+        o_lo += (long long)N1 * (SM_THREADS / 2);
+        o_hi += (long long)N1 * (SM_THREADS / 2);
+      }
+    } else {
+    const int p = bx == 0u ? 0 : (N1 >> 1) - 1;                            // the self-mirroring rows, or the odd pair
     const int ra = p, rb = p == 0 ? (N1 >> 1) : N1 - p;
     double cs = 1.0, sn = 0.0;
     {
@@ -806,6 +865,7 @@ __global__ __launch_bounds__(SM_THREADS) void smooth_rows_kernel(SmoothPlan P, S
       const double nc = cs * P.pstep_c - sn * P.pstep_s;
       sn = sn * P.pstep_c + cs * P.pstep_s;
       cs = nc;
+    }
     }
   } else
   for (int i = tid; i < N2 * C; i += SM_THREADS) {
@@ -1121,7 +1181,8 @@ int32_t make_smooth_plan(int32_t n, const void* t1, const void* t2, const void* 
   { const int v = ira_tune_int("IRA_SMOOTH_C1", 0); if (v >= 1 && n2 % v == 0) P->c1 = v; }
   { const int v = ira_tune_int("IRA_SMOOTH_C2", 0); if (v >= 1 && n1 % v == 0) P->c2 = v; }
   P->pairs = pairs ? 1 : 0;
-  if (pairs) P->c2 = 2;                                  // a tile = a row and its mirror row
+  if (pairs) P->c2 = 2;                                  // a tile = a row and its mirror row, or two such pairs (pq)
+  P->pq = pairs ? (n1 / 2 - 1) / 2 : 0;
   {
     const double step = -3.14159265358979323846 * (double)(SM_THREADS / 2) / (double)n2;
     P->pstep_c = std::cos(step);
@@ -1195,10 +1256,13 @@ extern "C" int32_t ira_rfft_smooth(const float* x_dev, const int64_t* xoff_dev, 
   const size_t l1 = ((size_t)P.c1 * P.ld1 + SM_TW) * sizeof(cd), l2 = ((size_t)P.c2 * P.ld2 + SM_TW) * sizeof(cd);
   cd* work = reinterpret_cast<cd*>(work_dev);
   if (pairs) {
+    // tiles of pass 2: rows {0, n1/2}, pq quads, the odd pair if there is one; LDS for the widest of them
+    const int tiles = 1 + P.pq + ((P.n1 / 2 - 1) & 1);
+    const size_t lp = ((size_t)(P.pq > 0 ? 4 : 2) * P.ld2 + SM_TW) * sizeof(cd);
     IRA_TRY_HIP(allow_lds(smooth_cols_kernel<SM_SIGNAL, true>, l1));
-    IRA_TRY_HIP(allow_lds(smooth_rows_kernel<SM_OUT_SPEC_PAIRS>, l2));
+    IRA_TRY_HIP(allow_lds(smooth_rows_kernel<SM_OUT_SPEC_PAIRS>, lp));
     smooth_cols_kernel<SM_SIGNAL, true><<<dim3(P.n2 / P.c1, nb), SM_THREADS, l1, st>>>(P, J, work);
-    smooth_rows_kernel<SM_OUT_SPEC_PAIRS><<<dim3(P.n1 / 2, nb), SM_THREADS, l2, st>>>(P, J, work);
+    smooth_rows_kernel<SM_OUT_SPEC_PAIRS><<<dim3(tiles, nb), SM_THREADS, lp, st>>>(P, J, work);
     IRA_RETURN_LAUNCH();
   }
   IRA_TRY_HIP(allow_lds(smooth_cols_kernel<SM_SIGNAL>, l1));
