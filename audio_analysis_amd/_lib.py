@@ -119,6 +119,16 @@ PROTOTYPES = {
     "ira_mls_finish": (i32, [vp, vp, i32, i32, i32, vp, vp, vp]),
 }
 
+# name -> (restype, argtypes) of the symbols include/ira_equalise.h declares (a second header: ira.h keeps its own set).
+EQUALISE_PROTOTYPES = {
+    "ira_eq_power": (i32, [vp, vp, i32, vp, i32, vp, i32, vp, vp, i32, vp, vp]),
+    "ira_eq_pyramid": (i32, [vp, i32, i32, vp]),
+    "ira_eq_smooth": (i32, [vp, vp, vp, i32, i32, vp, vp]),
+    "ira_eq_invert": (i32, [vp, vp, vp, vp, f64, vp, i32, i32, vp, vp, vp]),
+    "ira_eq_gather": (i32, [vp, vp, i32, vp, i32, i32, i32, vp, vp]),
+    "ira_eq_taper": (i32, [vp, vp, vp, i32, i32, i32, vp, vp]),
+}
+
 
 class IraError(RuntimeError):
     pass
@@ -160,7 +170,7 @@ def load():
     have = int(version())
     if have != ABI_VERSION:
         raise IraError(f"{path} has ABI version {have}, this package binds version {ABI_VERSION}: {rebuild}")
-    for name, (res, args) in PROTOTYPES.items():
+    for name, (res, args) in [*PROTOTYPES.items(), *EQUALISE_PROTOTYPES.items()]:
         try:
             fn = getattr(lib, name)
         except AttributeError:

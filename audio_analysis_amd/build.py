@@ -76,6 +76,9 @@ SOURCES = {
     # the residual (x - Y / R)^2 and the response (W - W[0]) / scale round one operation at a time: the chain is held bit for
     # bit to a NumPy restatement (the transform itself has only additions and subtractions, nothing to contract)
     "ira_mls.hip": ["-ffp-contract=off"],
+    # power sums, the pyramid's pairwise sums, the window sums and the quotients of the inversion round one operation at a
+    # time: every kernel is held bit for bit to a NumPy restatement
+    "ira_equalise.hip": ["-ffp-contract=off"],
 }
 COMMON = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function"]
 
@@ -123,7 +126,7 @@ def build_tuning(verbose: bool = True) -> Path:
 
 def build(force: bool = False, verbose: bool = False) -> Path:
     hipcc = _hipcc()
-    headers = list(CSRC.glob("*.h")) + [CSRC.parent.parent / "include" / "ira.h"]
+    headers = list(CSRC.glob("*.h")) + [CSRC.parent.parent / "include" / h for h in ("ira.h", "ira_equalise.h")]
     jobs = []
     objs = []
     for name, extra in SOURCES.items():

@@ -65,6 +65,11 @@ MINPHASE_MIN_N = 32           # the smallest transform of the chain
 MINPHASE_MIN_FLOOR_DB = -300.0  # IRA_MINPHASE_MIN_FLOOR_DB
 MINPHASE_SCRATCH_BYTES = 4 << 30  # minphase_cut: the device scratch of one sub-batch of the minimum-phase chain stays under this
 MLS_MIN_ORDER, MLS_MAX_ORDER = 2, 21  # IRA_MLS_MIN_ORDER, IRA_MLS_MAX_ORDER
+EQ_TILE_LOG2 = 11             # IRA_EQ_TILE_LOG2: levels of the pyramid a pass of ira_eq_pyramid builds from one LDS tile
+EQ_TILE = 1 << EQ_TILE_LOG2   # IRA_EQ_TILE
+EQ_MAX_MEMBERS = 256          # IRA_EQ_MAX_MEMBERS: channels one averaged row holds
+EQ_MAX_SMOOTHING = 48         # the narrowest smoothing, 1/48 octave
+EQ_SCRATCH_BYTES = 4 << 30    # equalise_cut: the device scratch of one sub-batch of rows stays under this
 MLS_MAX_PERIODS = 1024        # IRA_MLS_MAX_PERIODS
 MLS_TILE_LOG2 = 12            # IRA_MLS_TILE_LOG2: the tile order T of ira_mls_hadamard
 MLS_FOLD_THREADS = 256        # IRA_MLS_FOLD_THREADS
@@ -219,16 +224,92 @@ def minphase_scratch_bytes(n_fft) -> np.ndarray:
 def minphase_cut(n_fft, scratch_bytes: int = MINPHASE_SCRATCH_BYTES) -> List[Tuple[int, int]]:
     """[(first, end), ..]: consecutive channels cut into sub-batches whose scratch (minphase_scratch_bytes) stays under
     MINPHASE_SCRATCH_BYTES; a channel that alone exceeds it is a sub-batch of its own."""
-    need = minphase_scratch_bytes(n_fft).reshape(-1)
+    return cut_under(minphase_scratch_bytes(n_fft).reshape(-1), scratch_bytes)
+
+
+def cut_under(need: np.ndarray, budget: int) -> List[Tuple[int, int]]:
+    """[(first, end), ..]: consecutive entries of need (bytes each) cut into runs whose sum stays under budget; an entry
+    that alone exceeds it is a run of its own."""
     cuts, first, total = [], 0, 0
     for i, b in enumerate(need.tolist()):
-        if i > first and total + b > scratch_bytes:
+        if i > first and total + b > budget:
             cuts.append((first, i))
             first, total = i, 0
         total += b
     if need.size:
         cuts.append((first, int(need.size)))
     return cuts
+
+
+def equalise_layout(n_fft: int) -> Tuple[np.ndarray, np.ndarray]:
+    """(offsets, lengths) of the levels of a row's pyramid, int64 each (eq_level of ira_equalise.hip): n_0 = N/2 + 1,
+    n_(j+1) = (n_j + 1) >> 1 until n_j = 1, level j at n_0 + .. + n_(j-1) doubles from the row's start.  log2(N) + 1 levels,
+    N + log2(N) doubles a row."""
+    lens = [int(n_fft) // 2 + 1]
+    while lens[-1] > 1:
+        lens.append((lens[-1] + 1) >> 1)
+    lens = np.asarray(lens, dtype=np.int64)
+    return exclusive_cumsum(lens), lens
+
+
+def equalise_row_doubles(n_fft: int) -> int:
+    off, lens = equalise_layout(n_fft)
+    return int(off[-1] + lens[-1])
+
+
+def equalise_windows(n_fft: int, smoothing: int) -> Tuple[np.ndarray, np.ndarray]:
+    """(lo, hi) int32 (N/2 + 1,) of 1/b-octave smoothing, b = smoothing: lo_k = ceil(k 2^(-1/(2b))), hi_k = min(floor(k
+    2^(1/(2b))), N/2), float64 NumPy; b = 0: lo = hi = k."""
+    b, half = int(smoothing), int(n_fft) // 2
+    if not 0 <= b <= EQ_MAX_SMOOTHING:
+        raise ValueError(f"smoothing must be a whole number 0 .. {EQ_MAX_SMOOTHING} (1/b octave, 0 = none), got {smoothing}")
+    k = np.arange(half + 1, dtype=np.float64)
+    if b == 0:
+        return k.astype(np.int32), k.astype(np.int32)
+    lo = np.ceil(k * 2.0 ** (-1.0 / (2.0 * b)))
+    hi = np.minimum(np.floor(k * 2.0 ** (1.0 / (2.0 * b))), float(half))
+    return lo.astype(np.int32), hi.astype(np.int32)
+
+
+def equalise_tables(n_fft: int, sample_rate_hz: float, f_low: float, f_high: float, transition_octaves: float, reg_in_db: float,
+                    reg_out_db: float, tilt_db_per_octave: float) -> Tuple[np.ndarray, np.ndarray]:
+    """(t, beta) float64 (N/2 + 1,): the target t_k = 10^(tilt log2(f_k / 1000) / 20), t_0 = t_1, and the regularisation
+    beta_k = 10^(beta_dB / 10), beta_dB = reg_in + w (reg_out - reg_in), w = 0.5 (1 - cos pi u), u = clamp(log2(f_low /
+    f_k) / transition, 0, 1) below the band and clamp(log2(f_k / f_high) / transition, 0, 1) above it; w = 1 at k = 0."""
+    half = int(n_fft) // 2
+    f = np.arange(half + 1, dtype=np.float64) * float(sample_rate_hz) / float(n_fft)
+    f[0] = f[1]
+    t = 10.0 ** (float(tilt_db_per_octave) * np.log2(f / 1000.0) / 20.0)
+    below = np.clip(np.log2(float(f_low) / f) / float(transition_octaves), 0.0, 1.0)
+    above = np.clip(np.log2(f / float(f_high)) / float(transition_octaves), 0.0, 1.0)
+    u = np.where(f < float(f_low), below, above)
+    w = 0.5 * (1.0 - np.cos(np.pi * u))
+    w[0] = 1.0
+    beta = 10.0 ** ((float(reg_in_db) + w * (float(reg_out_db) - float(reg_in_db))) / 10.0)
+    return t, beta
+
+
+def equalise_taper(taps: int, fade: float) -> np.ndarray:
+    """v float64 (taps,): 1 up to n0 = taps - rint(fade taps), from n0 on 0.5 (1 + cos(pi (n - n0 + 1) / (taps - n0 + 1)))."""
+    taps = int(taps)
+    n0 = taps - int(np.rint(float(fade) * taps))
+    v = np.ones(taps, dtype=np.float64)
+    n = np.arange(n0, taps, dtype=np.float64)
+    v[n0:] = 0.5 * (1.0 + np.cos(np.pi * (n - n0 + 1.0) / float(taps - n0 + 1)))
+    return v
+
+
+def equalise_scratch_bytes(n_fft: int, members) -> np.ndarray:
+    """Device scratch of the equalisation chain per row of `members` channels at transform size N, in bytes: the members'
+    spectra (8 N each), the pyramid (8 N), S (4 N), c and G (8 N each), the cepstrum (4 N), T (8 N), g (4 N), F (8 N) and a
+    transform's work array (8 N): (8 members + 60) N + 1024."""
+    return (8 * np.asarray(members, dtype=np.int64) + 60) * int(n_fft) + 1024
+
+
+def equalise_cut(n_fft: int, members, scratch_bytes: int = EQ_SCRATCH_BYTES) -> List[Tuple[int, int]]:
+    """[(first, end), ..]: consecutive whole rows cut into sub-batches whose scratch (equalise_scratch_bytes) stays under
+    EQ_SCRATCH_BYTES; a row that alone exceeds it is a sub-batch of its own."""
+    return cut_under(equalise_scratch_bytes(n_fft, members).reshape(-1), scratch_bytes)
 
 
 def mls_taps(order: int, taps=None) -> Tuple[int, ...]:

@@ -1,7 +1,7 @@
 """
 The measure launchers of the device engine, one method per library call (or short chain of calls): ISO 3382-1 energy
 parameters and IACC, Lundeby, multi-slope fits, STI sums, harmonics, the echo criterion, echo density, reflections,
-transfer functions, FDW, burst decay, minimum phase, MLS measurement, and the suffix-energy tables.  Each checks its
+transfer functions, FDW, burst decay, minimum phase, equalisation, MLS measurement, and the suffix-energy tables.  Each checks its
 tables on the host (engine_geometry holds what several share), allocates its outputs, uploads its job tables in one copy
 and enqueues the call.  MeasureLaunchers is a base class of engine.Engine, which supplies the plumbing (empty, out_view,
 job_tables, ...).
@@ -375,6 +375,145 @@ class MeasureLaunchers:
             d_so, d_nf = self.job_tables(spec_off, n_fft)
             check(self.lib.ira_minphase_spectrum(_ptr(g_dev), _ptr(tspec_dev), _ptr(d_so), _ptr(d_nf), _ptr(pmax_dev), n,
                                                  int(n_fft.max()), self.stream), "ira_minphase_spectrum")
+
+    # ------------------------------------------------------------------ equalisation (smoothing pyramid, inversion, taper)
+    @staticmethod
+    def _eq_sizes(nrows: int, n_fft: int) -> int:
+        n = int(n_fft)
+        if not 0 <= int(nrows) <= 65535:
+            raise ValueError("at most 65535 rows per launch")
+        if not (MINPHASE_MIN_N <= n <= 1 << MINPHASE_MAX_LOG2 and n & (n - 1) == 0):
+            raise ValueError(f"n_fft must be a power of two {MINPHASE_MIN_N}..2^{MINPHASE_MAX_LOG2}, got {n_fft}")
+        return n
+
+    def eq_power(self, spec_dev, spec_off: np.ndarray, members: Sequence[Sequence[int]], n_fft: int, spec2_dev=None,
+                 spec2_off: Optional[np.ndarray] = None, pyr=None):
+        """Level 0 of every row's pyramid (ira_eq_power): row r = the mean over members[r] (indices into spec_off, in this
+        order) of |X|^2, times |F|^2 of the row's second spectrum at spec2_off[r] when spec2_dev is given.  Returns the
+        pyramid buffer, float64 device (rows, equalise_row_doubles(n_fft)); pyr: one to write into instead."""
+        t = self.torch
+        spec_off = flat(spec_off, np.int64)
+        nrows = len(members)
+        n = self._eq_sizes(nrows, n_fft)
+        counts = np.array([len(m) for m in members], dtype=np.int64)
+        table = np.array([int(i) for m in members for i in m], dtype=np.int64)
+        if nrows and (counts.min() < 1 or counts.max() > EQ_MAX_MEMBERS):
+            raise ValueError(f"a row holds 1 .. {EQ_MAX_MEMBERS} members")
+        if table.size and (table.min() < 0 or table.max() >= spec_off.size):
+            raise ValueError("members must index spec_off")
+        if spec2_dev is not None:
+            spec2_off = flat(spec2_off, np.int64)
+            if spec2_off is None or spec2_off.size != nrows:
+                raise ValueError("spec2_off must give one offset per row")
+        row_doubles = equalise_row_doubles(n)
+        if pyr is None:
+            pyr = self.out_view(t.float64, nrows, row_doubles)
+        elif tuple(pyr.shape) != (nrows, row_doubles):
+            raise ValueError("pyr must be (rows, equalise_row_doubles(n_fft))")
+        if nrows:
+            first = np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)
+            d_so, d_m, d_f, d_s2 = self.job_tables(spec_off, table.astype(np.int32), first,
+                                                   spec2_off if spec2_dev is not None else None)
+            check(self.lib.ira_eq_power(_ptr(spec_dev), _ptr(d_so), int(spec_off.size), _ptr(d_m), int(table.size), _ptr(d_f),
+                                        nrows, _ptr(spec2_dev), _ptr(d_s2), n, _ptr(pyr), self.stream), "ira_eq_power")
+        return pyr
+
+    def eq_pyramid(self, pyr, n_fft: int) -> None:
+        """The upper levels of every row's pyramid from level 0, in place (ira_eq_pyramid)."""
+        n = self._eq_sizes(int(pyr.shape[0]), n_fft)
+        if pyr.ndim != 2 or int(pyr.shape[1]) != equalise_row_doubles(n):
+            raise ValueError("pyr must be (rows, equalise_row_doubles(n_fft))")
+        if pyr.shape[0]:
+            check(self.lib.ira_eq_pyramid(_ptr(pyr), int(pyr.shape[0]), n, self.stream), "ira_eq_pyramid")
+
+    def eq_smooth(self, pyr, lo: np.ndarray, hi: np.ndarray, n_fft: int):
+        """S_k = W(lo_k, hi_k) / (hi_k - lo_k + 1) of every row (ira_eq_smooth): float64 device (rows, N/2 + 1).  lo, hi: (N/2 + 1,)
+        whole numbers with 0 <= lo <= hi <= N/2, one pair per call."""
+        nrows = int(pyr.shape[0])
+        n = self._eq_sizes(nrows, n_fft)
+        if pyr.ndim != 2 or int(pyr.shape[1]) != equalise_row_doubles(n):
+            raise ValueError("pyr must be (rows, equalise_row_doubles(n_fft))")
+        half = n // 2
+        lo_in, hi_in = np.asarray(lo).reshape(-1), np.asarray(hi).reshape(-1)
+        if lo_in.size != half + 1 or hi_in.size != half + 1:
+            raise ValueError("lo and hi must have n_fft / 2 + 1 entries")
+        if not (whole_numbers(lo_in, 0, half) and whole_numbers(hi_in, 0, half) and np.all(lo_in <= hi_in)):
+            raise ValueError("lo and hi must be whole numbers with 0 <= lo <= hi <= n_fft / 2")
+        d_lo, d_hi = self.job_tables(lo_in.astype(np.int32), hi_in.astype(np.int32))
+        out = self.out_view(self.torch.float64, nrows, n // 2 + 1)
+        if nrows:
+            check(self.lib.ira_eq_smooth(_ptr(pyr), _ptr(d_lo), _ptr(d_hi), nrows, n, _ptr(out), self.stream), "ira_eq_smooth")
+        return out
+
+    def eq_invert(self, s_dev, ref: np.ndarray, target: np.ndarray, beta: np.ndarray, max_gain: float, c_off: np.ndarray,
+                  n_fft: int, c_dev=None):
+        """c = (a t + beta) / (s + beta), s = S / ref, a = sqrt(s), max_gain where it exceeds that, as the complex (c, 0) of row
+        r at c_off[r] (in complex doubles), and the clamped bins per row (ira_eq_invert).  A row whose ref is not a positive
+        finite number gets c = 1.  Returns (c float64 device, clamped int64 device (rows,))."""
+        t = self.torch
+        ref, c_off = flat(ref, np.float64), flat(c_off, np.int64)
+        target, beta = flat(target, np.float64), flat(beta, np.float64)
+        nrows = same_rows("ref and c_off must be (rows,)", ref, c_off)
+        n = self._eq_sizes(nrows, n_fft)
+        nbins = n // 2 + 1
+        if target.size != nbins or beta.size != nbins:
+            raise ValueError("target and beta must have n_fft / 2 + 1 entries")
+        if not (float(max_gain) > 0.0 and math.isfinite(float(max_gain))):
+            raise ValueError(f"max_gain must be a positive finite number, got {max_gain}")
+        if tuple(s_dev.shape) != (nrows, nbins):
+            raise ValueError("s_dev must be (rows, n_fft / 2 + 1)")
+        if nrows and (c_off.min() < 0 or np.any(np.diff(np.sort(c_off)) < nbins)):
+            raise ValueError("c_off must place the rows n_fft / 2 + 1 bins apart")
+        if c_dev is None:
+            c_dev = self.empty(2 * (int(c_off.max()) + nbins) if nrows else 0, t.float64)
+        elif nrows and c_dev.numel() < 2 * (int(c_off.max()) + nbins):
+            raise ValueError("c_dev is too short for c_off")
+        clamped = self.empty(nrows, t.int64)
+        if nrows:
+            d_ref, d_co = self.job_tables(ref, c_off)
+            d_t, d_b = self.to_dev(target), self.to_dev(beta)
+            check(self.lib.ira_eq_invert(_ptr(s_dev), _ptr(d_ref), _ptr(d_t), _ptr(d_b), float(max_gain), _ptr(d_co), nrows, n,
+                                         _ptr(c_dev), _ptr(clamped), self.stream), "ira_eq_invert")
+        return c_dev, clamped[:nrows]
+
+    def eq_gather(self, src_dev, src_off: np.ndarray, stride: int, bins: np.ndarray, n_fft: int):
+        """src[src_off[r] + stride * bins[j]] per (row, grid point), offsets and stride in doubles (ira_eq_gather): float64
+        device (rows, J).  bins: whole numbers 0 .. N/2, one table per call."""
+        src_off = flat(src_off, np.int64)
+        nrows = int(src_off.size)
+        n = self._eq_sizes(nrows, n_fft)
+        bins_in = np.asarray(bins).reshape(-1)
+        npts = int(bins_in.size)
+        if npts > FDW_MAX_POINTS:
+            raise ValueError(f"at most {FDW_MAX_POINTS} frequency points, got {npts}")
+        if not whole_numbers(bins_in, 0, n // 2):
+            raise ValueError("bins must be whole numbers 0 .. n_fft / 2")
+        if int(stride) not in (1, 2):
+            raise ValueError("stride must be 1 or 2")
+        if nrows and (src_off.min() < 0 or int(src_off.max()) + int(stride) * (n // 2) >= src_dev.numel()):
+            raise ValueError("src_off leaves the source")
+        out = self.out_view(self.torch.float64, nrows, npts)
+        if nrows and npts:
+            d_so, d_b = self.job_tables(src_off, bins_in.astype(np.int32))
+            check(self.lib.ira_eq_gather(_ptr(src_dev), _ptr(d_so), int(stride), _ptr(d_b), nrows, npts, n, _ptr(out),
+                                         self.stream), "ira_eq_gather")
+        return out
+
+    def eq_taper(self, g_dev, g_off: np.ndarray, taper: np.ndarray, n_fft: int):
+        """f[r, n] = float32((double)g[g_off[r] + n] * taper[n]), n < taps (ira_eq_taper): float32 device (rows, taps)."""
+        g_off, taper = flat(g_off, np.int64), flat(taper, np.float64)
+        nrows, taps = int(g_off.size), int(taper.size)
+        n = self._eq_sizes(nrows, n_fft)
+        if not 1 <= taps <= n // 2:
+            raise ValueError(f"1 <= taps <= n_fft / 2, got {taps} at n_fft {n}")
+        if nrows and (g_off.min() < 0 or int(g_off.max()) + taps > g_dev.numel()):
+            raise ValueError("g_off leaves the source")
+        out = self.out_view(self.torch.float32, nrows, taps)
+        if nrows:
+            d_go = self.job_tables(g_off)[0]
+            check(self.lib.ira_eq_taper(_ptr(g_dev), _ptr(d_go), _ptr(self.to_dev(taper)), nrows, taps, n, _ptr(out),
+                                        self.stream), "ira_eq_taper")
+        return out
 
     # ------------------------------------------------------------------ MLS measurement (fast Hadamard transform)
     def mls_device_tables(self, order: int, taps=None):
