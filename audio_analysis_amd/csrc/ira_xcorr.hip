@@ -195,7 +195,10 @@ __global__ __launch_bounds__(XC_THREADS) void xcorr_partial_kernel(
 
 // One wave per (segment, partition): lane q owns entries q, q + 64, ... of the record and adds the partition's chunks in
 // ascending order (coalesced reads, no cross-lane step).  A partition without samples gives zeros.  Not ira::fold_records:
-// a lane owns entries, not chunks, and the chunk range comes from the partition's limits.
+// a lane owns entries, not chunks, and the chunk range comes from the partition's limits.  Like ira::fold_records it never
+// reads past its records: the range stops at the rec_stride - nlim chunks pass 1 was launched over, so a segment longer than
+// the max_len the caller stated comes out cut at that many chunks instead of reading its neighbour's records, and an onset
+// past the end of the file (L < 0) gives the empty segment it gives in pass 1, not a chunk range that starts below zero.
 __global__ __launch_bounds__(IRA_WAVE) void xcorr_fold_kernel(
     const int64_t* __restrict__ len, const int32_t* __restrict__ lchan, const int32_t* __restrict__ rchan,
     const int64_t* __restrict__ onset, const int64_t* __restrict__ limits, int nlim, int T, int64_t rec_stride,
@@ -203,7 +206,7 @@ __global__ __launch_bounds__(IRA_WAVE) void xcorr_fold_kernel(
   const int seg = blockIdx.x, j = blockIdx.y;
   const int64_t ol = onset[lchan[seg]], orr = onset[rchan[seg]];
   const int64_t o = ol < orr ? ol : orr;
-  const int64_t L = o < 0 ? 0 : len[seg] - o;
+  const int64_t L = o < 0 || o > len[seg] ? 0 : len[seg] - o;
   int64_t a = j == 0 ? 0 : limits[(int64_t)seg * nlim + j - 1];
   int64_t b = j == nlim ? L : limits[(int64_t)seg * nlim + j];
   a = a < 0 ? 0 : (a < L ? a : L);
@@ -211,7 +214,9 @@ __global__ __launch_bounds__(IRA_WAVE) void xcorr_fold_kernel(
   const int nrec = 2 * T + 3;
   const double* rec = scratch + (int64_t)seg * rec_stride * nrec;
   double* dst = out + ((int64_t)seg * (nlim + 1) + j) * nrec;
-  const int64_t c_lo = a / XC_CHUNK, c_hi = a < b ? (b - 1) / XC_CHUNK : -1;
+  const int64_t chunks = rec_stride - nlim;
+  const int64_t c_lo = a / XC_CHUNK, c_last = a < b ? (b - 1) / XC_CHUNK : -1;
+  const int64_t c_hi = c_last < chunks ? c_last : chunks - 1;
   for (int q = threadIdx.x; q < nrec; q += IRA_WAVE) {
     double v = 0.0;
     for (int64_t c = c_lo; c <= c_hi; ++c) v += rec[(c + j) * nrec + q];

@@ -629,6 +629,10 @@ int32_t ira_energy_windows(const float* x_dev, const int64_t* base_off_dev, cons
  *     across partition boundaries and in front of the onset, never wrapped), then El = sum_n l[o + n]^2, Er = sum_n r[o + n]^2.
  *   Float64 products and sums of the exact float32 samples, in an order that depends on the segment's length, onset and
  *   limits alone (bit-identical whatever the batch, the segment's place in it or its alignment); no atomics.
+ *   Every limit is clamped to 0 .. L and an upper limit below its partition's lower one gives an empty partition (zeros),
+ *   as does every partition of a segment whose o is negative or past its len.  A len above max_len is a caller's error that
+ *   stays inside the scratch: such a segment comes out cut at the ceil(max_len / 4096) chunks of 4096 rows (counted from o)
+ *   that its records were sized for, like a row of ira_mtf_sums.
  *   max_len >= every len (< 2^31); nseg <= 65535; scratch_dev holds as many doubles as the size call returns
  *   (IRA_E_SIZE, negative, for arguments out of range; the size call is host only).  Argument errors are reported
  *   before anything is launched. */

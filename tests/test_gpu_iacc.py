@@ -1,7 +1,7 @@
 """
 ISO 3382-1 inter-channel cross-correlation on the device (ira_onset_index + ira_xcorr_windows,
-audio_analysis_amd.analyse.iacc) against a long-double NumPy restatement of the definitions in the module's docstring,
-written out here; a closed form that does not use the restatement; band signals against the oracle's float64 filter bank.
+audio_analysis_amd.analyse.iacc) against a long-double NumPy restatement of the definitions in the module's docstring
+(xcorr_ref.py); a closed form that does not use the restatement; band signals against the oracle's float64 filter bank.
 
 Tolerance of the raw sums (the energy tests' tolerance): |C_dev - C_ref| <= 1e-12 sqrt(El_ref Er_ref) per partition and lag,
 El and Er to 1e-12 relative.  NumPy float64 sums of a 100 003-sample pair sit 7.6e-18 from the long-double values on that
@@ -19,6 +19,7 @@ import numpy as np
 import pytest
 
 from oracle import ira_oracle as O
+from xcorr_ref import narrow, ref_coefficient, ref_onset, ref_sums
 
 pytestmark = pytest.mark.gpu
 
@@ -28,52 +29,7 @@ CH = 4096                # XC_CHUNK of audio_analysis_amd/csrc/ira_xcorr.hip: ro
 LD = np.longdouble
 
 
-# ------------------------------------------------------------------------------------------------ the restatement
-def ref_onset(x, onset_db=-20.0):
-    x = np.asarray(x, dtype=np.float32)
-    e = x.astype(np.float64) ** 2
-    p = int(np.argmax(np.abs(x)))
-    return int(np.flatnonzero(e[: p + 1] >= e[p] * 10.0 ** (onset_db / 10.0))[0])
-
-
-def ref_sums(l, r, o, limits, tmax):
-    """(K + 1, 2T + 3) long double: per partition [a, b) of n = 0 .. L - 1 (counted from o; limits past L give empty
-    partitions) C(tau) = sum l[o + n] r[o + n + tau] on a zero-padded right channel, tau = -T .. T, then El, Er."""
-    l = np.asarray(l, dtype=np.float32).astype(LD)
-    r = np.asarray(r, dtype=np.float32).astype(LD)
-    n = l.size
-    assert r.size == n
-    length = n - o
-    rp = np.zeros(n + 2 * tmax, dtype=LD)                # rp[m + T] = r[m], zeros for m < 0 and m >= N
-    rp[tmax : tmax + n] = r
-    edges = [0] + [min(int(v), length) for v in limits] + [length]
-    out = np.zeros((len(edges) - 1, 2 * tmax + 3), dtype=LD)
-    for j, (a, b) in enumerate(zip(edges[:-1], edges[1:])):
-        if b <= a:
-            continue
-        ls = l[o + a : o + b]
-        for k, tau in enumerate(range(-tmax, tmax + 1)):
-            out[j, k] = np.sum(ls * rp[tmax + o + a + tau : tmax + o + b + tau])
-        out[j, 2 * tmax + 1] = np.sum(ls * ls)
-        out[j, 2 * tmax + 2] = np.sum(r[o + a : o + b] ** 2)
-    return out
-
-
-def narrow(ref, t_from, t_to):
-    """The record of max lag t_to cut out of one of max lag t_from >= t_to (C(tau) does not depend on T)."""
-    d = t_from - t_to
-    return np.concatenate([ref[:, d : d + 2 * t_to + 1], ref[:, 2 * t_from + 1 :]], axis=1)
-
-
-def ref_coefficient(rec):
-    """(IACC, tau in samples, |IACF| of every lag) of one summed record, float64."""
-    rec = np.asarray(rec, dtype=np.float64)
-    tmax = (rec.size - 3) // 2
-    iacf = np.abs(rec[: 2 * tmax + 1] / math.sqrt(rec[-2] * rec[-1]))
-    k = int(np.argmax(iacf))
-    return float(iacf[k]), k - tmax, iacf
-
-
+# ------------------------------------------------------------------------------------------------ the restatement: xcorr_ref.py
 def assert_sums(dev, ref, what):
     ref64 = ref.astype(np.float64)
     nlag = ref.shape[1] - 2

@@ -74,16 +74,60 @@ def _same(a, b):
 
 
 # ------------------------------------------------------------------------------------------------ the kernel
+# A thread holds quads u < 16 of four samples, 1024 samples apart (ira_mtf.hip): lengths either side of the stride at which
+# a thread's next quad becomes empty, and last quads of 1, 2, 3 and 4 samples (cnt % 4) on both sides of it and of a chunk
+_EDGE_LENS = [2, 4, 5, 6, 1022, 1023, 1024, 1025, 2050, C - 2, C + 2]
+
+
 @pytest.mark.parametrize("nf", [1, 14, 16])
 def test_ragged_launch_vs_restatement(nf):
     eng = _eng()
-    lens = [1, 3, C - 1, C, C + 1, 2 * C + 5, 100003]
+    lens = [1, 3, C - 1, C, C + 1, 2 * C + 5, 100003] + _EDGE_LENS
     rows = [_noise_row(10 + i, n) for i, n in enumerate(lens)]
     freqs = {1: (12.5,), 14: R.FREQS, 16: R.FREQS + (16.0, 20.0)}[nf]
     w_rows = [R.turns(freqs, (44100, 48000)[i % 2]) for i in range(len(rows))]
     got = device_sums(eng, rows, w_rows)
     assert got.shape == (len(rows), 2 * nf + 1)
     check_rows(got, rows, w_rows, f"ragged launch, nf = {nf}")
+
+
+def test_every_frequency_count_on_short_rows():
+    """nf = 1 .. 16, each a launch of its own (the record, the LDS table and the fold's stride are sized by nf)."""
+    eng = _eng()
+    lens = [1, 6, 1023, 1026, 2050, C + 2]
+    rows = [_noise_row(40 + i, n) for i, n in enumerate(lens)]
+    freqs = R.FREQS + (16.0, 20.0)
+    worst = (0.0, 0.0)
+    for nf in range(1, 17):
+        w_rows = [R.turns(freqs[:nf], (44100, 48000)[i % 2]) for i in range(len(rows))]
+        got = device_sums(eng, rows, w_rows)
+        assert got.shape == (len(rows), 2 * nf + 1)
+        worst = tuple(map(max, worst, check_rows(got, rows, w_rows, f"short rows, nf = {nf}")))
+    print(f"short rows, nf = 1 .. 16: max relative error of E {worst[0]:.3e}, max absolute error of m {worst[1]:.3e}")
+
+
+def test_integer_rows_exact_energy_and_quarter_turn_sums():
+    """Integer-valued samples (|x| <= 127): every square and every partial sum is an integer far below 2^53, so E is exact
+    in any order, bit for bit.  At w = 0, 0.25 and 0.5 turns per sample the phase w n reduces exactly to a multiple of a
+    quarter turn, where sincospi returns exactly 0 and +-1, so the three phasor factors, their products and the sums are
+    exact too: A = E and B = 0 at w = 0, the sums over n % 4 with signs (+, 0, -, 0) and (0, +, 0, -) at 0.25, the
+    alternating sum and 0 at 0.5.  Asserted as equalities (a zero may carry either sign)."""
+    eng = _eng()
+    lens = [1, 3] + _EDGE_LENS + [C - 1, C, C + 1, 2 * C + 5]
+    rng = np.random.default_rng(2025)
+    rows = [rng.integers(-127, 128, n).astype(np.float32) for n in lens]
+    got = device_sums(eng, rows, [[0.0, 0.25, 0.5]] * len(rows))
+    exact = True
+    for i, x in enumerate(rows):
+        e = x.astype(np.int64) ** 2
+        e4 = np.concatenate([e, np.zeros(-e.size % 4, np.int64)]).reshape(-1, 4).sum(axis=0)
+        want = [e.sum(), e.sum(), 0, e4[0] - e4[2], e4[1] - e4[3], e4[0] - e4[1] + e4[2] - e4[3], 0]
+        assert got[i, 0].view(np.uint64) == np.float64(want[0]).view(np.uint64), (lens[i], got[i, 0], want[0])
+        if not np.array_equal(got[i], np.array(want, np.float64)):
+            exact = False
+            print(f"length {lens[i]}: got {got[i].tolist()}, want {want}")
+    print(f"integer rows at w = 0, 0.25, 0.5: A and B exact at every length: {exact}")
+    assert exact
 
 
 def test_long_row_of_2_21_samples():
