@@ -1,11 +1,19 @@
 // Peak pick, Schroeder energy-decay curve, threshold crossings and decay-line fits.
 // Compiled with -ffp-contract=off: the f64 interpolation/regression arithmetic must round like
 // NumPy's (no fused multiply-add), see reference analyse/decay.py:173-260.
-#include "ira_common.h"
-#include "ira_log.h"
-#include "ira_reduce.h"
+#include "ira_edc_tile.h"
 
 namespace {
+
+using ira::EDC_PER_THREAD;
+using ira::EDC_THREADS;
+using ira::EDC_TILE;
+using ira::EdcDb;
+using ira::EdcSpan;
+using ira::edc_tile_count;
+using ira::edc_tile_span;
+using ira::np_max;
+using ira::qnan;
 
 // ------------------------------------------------------------------------------------------------
 // a2: argmax |x| with first-maximum-wins.  Key = (bits(|x|) << 32) | (0xFFFFFFFF - index):
@@ -72,11 +80,7 @@ __global__ __launch_bounds__(PEAK_THREADS) void peak_partial_kernel(
       best = k > best ? k : best;
     }
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const unsigned long long other = __shfl_xor(best, o, 64);
-    best = other > best ? other : best;
-  }
+  best = ira::wave_max_int(best);
   __shared__ unsigned long long wbest[PEAK_THREADS / IRA_WAVE];
   if ((threadIdx.x & 63) == 0) wbest[threadIdx.x >> 6] = best;
   __syncthreads();
@@ -99,32 +103,33 @@ __global__ void peak_decode_kernel(unsigned long long* __restrict__ keys, float*
 }
 
 // ------------------------------------------------------------------------------------------------
-// a3: Schroeder EDC.  A segment is cut into 4096-sample tiles counted from its END (the direction
-// numpy.cumsum(e[::-1]) accumulates in); one 256-thread workgroup scans one tile: every thread owns 16 consecutive
-// samples (four 16-byte loads issued together: one memory round trip per tile), forms their suffix sums serially,
-// the wave combines thread totals with shuffles and the four waves meet through LDS -- one barrier per tile.
+// a3: Schroeder EDC.  A segment is cut into 4096-sample tiles counted from its END (ira_edc_tile.h); one 256-thread
+// workgroup scans one tile: every thread owns 16 consecutive samples (four 16-byte loads issued together: one memory round
+// trip per tile), forms their suffix sums serially, the wave combines thread totals with shuffles and the four waves meet
+// through LDS -- one barrier per tile.
 //   edc_sums_kernel   (tiles x segments)   tile totals
 //   edc_carry_kernel  (1 wave / segment)   carry[j] = energy behind tile j, and the normaliser edc[0]
 //   edc_emit_kernel   (tiles x segments)   re-scan, add the carry, 10*log10(max(edc,eps)/edc[0]) floored -> float32
-// Every kernel (the fused fit kernel below included) runs the SAME scan code and forms a value as
-// (suffix sum inside the tile) + carry[j], so the normaliser is bit-identical to the value the emit pass produces at
-// index 0 (=> edc_db[0] is exactly 0 dB, which the 0 dB crossing needs) and the fit kernel sees the emitted curve.
+// Every kernel (the fused fit kernels below included) forms a value as tile_suffix_scan's sum inside the tile + carry[j]
+// and converts it with EdcDb, so the normaliser is bit-identical to the value the emit pass produces at index 0 (=> edc_db[0]
+// is exactly 0 dB, which the 0 dB crossing needs) and the fit kernels see the emitted curve.
 // ------------------------------------------------------------------------------------------------
-constexpr int EDC_THREADS = 256;
-constexpr int EDC_PER_THREAD = 16;
-constexpr int EDC_TILE = EDC_THREADS * EDC_PER_THREAD;
 constexpr int EDC_WAVES = EDC_THREADS / IRA_WAVE;
 // scratch per segment: tot[0 .. T) | carry[0 .. T) | ... | norm (last double); T <= EDC_MAX_TILES
 constexpr int EDC_MAX_TILES = IRA_EDC_SCRATCH_DOUBLES / 2 - 1;
-static_assert(EDC_TILE == 4096, "the host sizes its checks with 4096-sample tiles");
+constexpr int EDC_CARRY = IRA_EDC_SCRATCH_DOUBLES / 2, EDC_NORM = IRA_EDC_SCRATCH_DOUBLES - 1;
 
 struct EdcShared {
   double wave_tot[2][EDC_WAVES];     // double-buffered by tile parity: one barrier per tile is enough
 };
 
-// The thread's 16 samples of a tile of tile_len valid samples (zeros beyond): local indices 16t .. 16t+15.
-__device__ __forceinline__ void tile_load(const float* __restrict__ src, int tile_len, float x[EDC_PER_THREAD]) {
-  ira::load_run<EDC_PER_THREAD>(src, 0, tile_len, x);
+// The thread's 16 samples of tile j of an n-sample segment (zeros beyond a short tile's length): the tile's local indices
+// 16t .. 16t+15.  The fused fits issue this one tile AHEAD of its use (phase B walks consecutive tiles), so that the memory
+// round trip of tile j-1 runs under the scan and the logarithms of tile j.
+__device__ __forceinline__ EdcSpan tile_load(const float* __restrict__ src, long long n, long long j, float x[EDC_PER_THREAD]) {
+  const EdcSpan sp = edc_tile_span(n, j);
+  ira::load_run<EDC_PER_THREAD>(src + sp.lo, 0, sp.len(), x);
+  return sp;
 }
 
 // Inclusive suffix sums (within the tile) of the squared samples at the thread's 16 positions.  parity = tile
@@ -163,15 +168,13 @@ __global__ __launch_bounds__(EDC_THREADS) void edc_sums_kernel(
   const int seg = blockIdx.y;
   const int64_t j = blockIdx.x;
   const int64_t n = len[seg];
-  const int64_t ntiles = (n + EDC_TILE - 1) / EDC_TILE;
+  const int64_t ntiles = edc_tile_count(n);
   if (j >= ntiles) return;
   // segments whose producer delivered tile energies (edc_tiles_from_parts_kernel) scan only the tile that holds their first
   // sample: the normaliser edc[0] = tot[T-1] + carry[T-1] must be the value the emit / fit scans form at index 0
   if (part_off != nullptr && part_off[seg] >= 0 && j < ntiles - 1) return;
-  const int64_t hi = n - j * EDC_TILE;
-  const int64_t lo = hi - EDC_TILE > 0 ? hi - EDC_TILE : 0;
   float xv[EDC_PER_THREAD];
-  tile_load(x + off[seg] + lo, (int)(hi - lo), xv);
+  tile_load(x + off[seg], n, j, xv);
   double s[EDC_PER_THREAD];
   tile_suffix_scan(xv, sh, 0, s);
   if (threadIdx.x == 0) scratch[(int64_t)seg * IRA_EDC_SCRATCH_DOUBLES + j] = s[0];
@@ -191,8 +194,7 @@ __global__ __launch_bounds__(128) void edc_tiles_from_parts_kernel(const int64_t
                                                                    const int32_t* __restrict__ part_tiles,
                                                                    double* __restrict__ scratch) {
   const int seg = blockIdx.y;
-  const int64_t n = len[seg];
-  const int64_t ntiles = (n + EDC_TILE - 1) / EDC_TILE;
+  const int64_t ntiles = edc_tile_count(len[seg]);
   const int64_t po = part_off[seg];
   if (po < 0) return;
   const int wgs = part_wgs[seg], tiles = part_tiles[seg];
@@ -204,10 +206,6 @@ __global__ __launch_bounds__(128) void edc_tiles_from_parts_kernel(const int64_t
   }
 }
 
-// ira::np_max keeps a NaN: a NaN sample makes the reference's whole curve NaN (decay.py:151-166), an infinite one NaN
-// before it and the floor after it.
-using ira::np_max;
-
 // One wave per segment: exclusive prefix sums of the tile totals (in blocks of 64 with a shuffle scan; any fixed
 // association will do, every later kernel reads THESE carries) and the normaliser edc[0] = tot[T-1] + carry[T-1],
 // which is exactly how the emit pass forms the value at index 0.
@@ -217,9 +215,8 @@ __global__ __launch_bounds__(IRA_WAVE) void edc_carry_kernel(const int64_t* __re
   if (seg >= nseg) return;
   const int64_t n = len[seg];
   if (n <= 0) return;
-  const int q = IRA_EDC_SCRATCH_DOUBLES / 2;
   double* sc = scratch + (int64_t)seg * IRA_EDC_SCRATCH_DOUBLES;
-  const int ntiles = (int)((n + EDC_TILE - 1) / EDC_TILE);
+  const int ntiles = (int)edc_tile_count(n);
   const int lane = threadIdx.x;
   double base = 0.0;
   for (int j0 = 0; j0 < ntiles; j0 += IRA_WAVE) {
@@ -229,21 +226,11 @@ __global__ __launch_bounds__(IRA_WAVE) void edc_carry_kernel(const int64_t* __re
     const double incl = ira::wave_prefix(tot, lane, excl);
     const double carry = base + excl;
     if (j < ntiles) {
-      sc[q + j] = carry;
-      if (j == ntiles - 1) sc[IRA_EDC_SCRATCH_DOUBLES - 1] = np_max(tot + carry, eps);
+      sc[EDC_CARRY + j] = carry;
+      if (j == ntiles - 1) sc[EDC_NORM] = np_max(tot + carry, eps);
     }
     base = base + __shfl(incl, 63, 64);
   }
-}
-
-// dB value of one suffix sum: 10 log10(max(sum, eps) / norm) through the table log2 (ira_log.h): ~30 instructions per
-// sample instead of ~110 for an f64 divide + log10, same value to ~1e-14 dB; sum == norm gives exactly 0 dB.
-// Shared by the emit pass and the fused fit kernel so that both see the same float32 curve bit for bit.
-__device__ __forceinline__ double edc_db64(double sum, double eps, double norm, double lnorm, bool fast,
-                                           const ira::LogTabEntry* ltab) {
-  const double v = np_max(sum, eps);
-  if (fast && v > 1e-300 && v < 1e300) return 3.0102999566398120 * (ira::log2_table(v, ltab) - lnorm);
-  return 10.0 * log10(v / norm);
 }
 
 __global__ __launch_bounds__(EDC_THREADS) void edc_emit_kernel(
@@ -255,30 +242,27 @@ __global__ __launch_bounds__(EDC_THREADS) void edc_emit_kernel(
   const int seg = blockIdx.y;
   const int64_t j = blockIdx.x;
   const int64_t n = len[seg];
-  const int64_t ntiles = (n + EDC_TILE - 1) / EDC_TILE;
-  if (j >= ntiles) return;
-  const int64_t hi = n - j * EDC_TILE;
-  const int64_t lo = hi - EDC_TILE > 0 ? hi - EDC_TILE : 0;
-  const int tl = (int)(hi - lo);
+  if (j >= edc_tile_count(n)) return;
   float xv[EDC_PER_THREAD];
-  tile_load(x + off[seg] + lo, tl, xv);
+  const EdcSpan sp = tile_load(x + off[seg], n, j, xv);
+  const int64_t lo = sp.lo;
+  const int tl = sp.len();
   ira::build_log_table(ltab, threadIdx.x);
   const double* sc = scratch + (int64_t)seg * IRA_EDC_SCRATCH_DOUBLES;
-  const double carry = sc[IRA_EDC_SCRATCH_DOUBLES / 2 + j];
-  const double norm = sc[IRA_EDC_SCRATCH_DOUBLES - 1];
+  const double carry = sc[EDC_CARRY + j];
+  const double norm = sc[EDC_NORM];
   double s[EDC_PER_THREAD];
   tile_suffix_scan(xv, sh, 0, s);                      // its barrier also publishes the log table
-  const bool fast = norm > 1e-300 && norm < 1e300;
-  const double lnorm = fast ? ira::log2_table(norm, ltab) : 0.0;
+  const EdcDb D(norm, eps, floor_db, ltab);
   float* dst = out ? out + out_off[seg] + lo : nullptr;
   double* dst64 = out64 ? out64 + out_off[seg] + lo : nullptr;
   const int i0 = EDC_PER_THREAD * threadIdx.x;
   float o[EDC_PER_THREAD];
 #pragma unroll
   for (int r = 0; r < EDC_PER_THREAD; ++r) {
-    const double db = edc_db64(s[r] + carry, eps, norm, lnorm, fast, ltab);
-    if (dst64 && i0 + r < tl) dst64[i0 + r] = db;      // unfloored f64 (optional dB smoothing, decay.py:161-164)
-    o[r] = (float)np_max(db, floor_db);
+    const double db = D.db64(s[r] + carry);
+    if (dst64 && i0 + r < tl) dst64[i0 + r] = db;
+    o[r] = D.floored(db);
   }
   if (dst) {
     if (i0 + EDC_PER_THREAD <= tl) {
@@ -365,20 +349,52 @@ __device__ __forceinline__ void block_sum3(double& a, double& b, double& c, FitS
   for (int w = 0; w < nw; ++w) { a += sh.red[0][w]; b += sh.red[1][w]; c += sh.red[2][w]; }
 }
 
-// first index i with y_rel[i] <= target  (float32 compare, like `curve <= target` under NEP 50)
-__device__ __forceinline__ double crossing_time_from_index(const float* y, float peak, long long idx, long long n,
-                                                           double target, const TimeAxis& ta) {
-  if (idx >= n) return __longlong_as_double(0x7ff8000000000000ll);  // NaN = "no crossing"
+// Target level k of 2 nranges + ncross: the ranges' (hi, lo) pairs, then the plain crossings; 0 beyond them.
+__device__ __forceinline__ double fit_target(const FitParams& P, int k) {
+  if (k < 2 * P.nranges) return (k & 1) ? P.lo[k >> 1] : P.hi[k >> 1];
+  return k < 2 * P.nranges + P.ncross ? P.cross[k - 2 * P.nranges] : 0.0;
+}
+
+// Time at which the curve crosses `target`, interpolated between the samples around idx = the first index with
+// y[idx] <= target (float32 compare, like `curve <= target` under NEP 50).  y_prev, y_at = y[idx - 1], y[idx], read only
+// when 0 < idx < n.
+__device__ __forceinline__ double crossing_time(long long idx, long long n, float y_prev, float y_at, double target,
+                                                const TimeAxis& ta) {
+  if (idx >= n) return qnan();                               // "no crossing"
   if (idx == 0) return (double)ta.at(0);
   const double t0 = (double)ta.at(idx - 1);
   const double t1 = (double)ta.at(idx);
-  const double y0 = (double)(y[idx - 1] - peak);
-  const double y1 = (double)(y[idx] - peak);
+  const double y0 = (double)y_prev;
+  const double y1 = (double)y_at;
   if (y1 == y0) return t1;
   double frac = (target - y0) / (y1 - y0);
   if (frac == frac) frac = fmin(fmax(frac, 0.0), 1.0);       // numpy.clip keeps NaN (a NaN neighbour: decay.py:192-196)
   return t0 + frac * (t1 - t0);
 }
+
+// ---- the fit records: IRA_FIT_DOUBLES doubles = ok, ts, te, slope, intercept, r2, rt60, npts ------------------------------
+// A range without a fit: ok = 0 beside what is known of it (NaN for the rest).
+__device__ __forceinline__ void write_refused(double* o, double ts, double te, double npts) {
+  o[0] = 0.0; o[1] = ts; o[2] = te;
+  for (int k = 3; k < 7; ++k) o[k] = qnan();
+  o[7] = npts;
+}
+// A curve without any: every range refused, every crossing NaN.
+__device__ __forceinline__ void write_all_refused(const FitParams& P, double* fo, double* co) {
+  for (int r = 0; r < P.nranges; ++r) write_refused(fo + r * IRA_FIT_DOUBLES, qnan(), qnan(), qnan());
+  for (int j = 0; j < P.ncross && co; ++j) co[j] = qnan();
+}
+// The fitted line; ok only for a falling one.
+__device__ __forceinline__ void write_line(double* o, double ts, double te, double slope, double icpt, double r2,
+                                           long long npts) {
+  const bool neg = slope < 0.0;                              // also false for NaN (stt == 0)
+  o[0] = neg ? 1.0 : 0.0;
+  o[1] = ts; o[2] = te; o[3] = slope; o[4] = icpt;
+  o[5] = r2;
+  o[6] = -60.0 / slope;
+  o[7] = (double)npts;
+}
+static_assert(IRA_FIT_DOUBLES == 8, "the record writers fill eight doubles");
 
 // Long curves (decay / band EDCs of whole files): the first-crossing search is done by MANY workgroups per curve
 // (grid chunks x curves), each taking the minimum crossing index of its chunk into an index slot per target with
@@ -404,12 +420,7 @@ __global__ __launch_bounds__(XS_THREADS) void crossing_search_kernel(const float
   const int ntargets = 2 * P.nranges + P.ncross;
   float targets[FIT_MAX_TARGETS];
 #pragma unroll
-  for (int k = 0; k < FIT_MAX_TARGETS; ++k) {
-    double tv = 0.0;
-    if (k < 2 * P.nranges) tv = (k & 1) ? P.lo[k >> 1] : P.hi[k >> 1];
-    else if (k < ntargets) tv = P.cross[k - 2 * P.nranges];
-    targets[k] = (float)tv;
-  }
+  for (int k = 0; k < FIT_MAX_TARGETS; ++k) targets[k] = (float)fit_target(P, k);
   long long first[FIT_MAX_TARGETS];
 #pragma unroll
   for (int k = 0; k < FIT_MAX_TARGETS; ++k) first[k] = n;
@@ -436,6 +447,30 @@ __global__ __launch_bounds__(XS_THREADS) void crossing_search_kernel(const float
   }
 }
 
+// One regression pass of curve_fit_kernel: f(t, y - peak) for every sample of [a0, a1] whose float32 time lies in
+// [ts32, te32], thread tid taking a0 + tid, a0 + tid + blockDim.x, ...  y is read in batches of FIT_U independent loads per
+// thread: with one load per iteration a single workgroup streaming a long range is bound by one memory latency per element.
+template <typename F>
+__device__ __forceinline__ void masked_sweep(const float* __restrict__ y, float peak, long long a0, long long a1, float ts32,
+                                             float te32, const TimeAxis& ta, F f) {
+  const int tid = threadIdx.x, nt = blockDim.x;
+  for (long long b0 = a0; b0 <= a1; b0 += (long long)nt * FIT_U) {
+    float yv[FIT_U];
+#pragma unroll
+    for (int u = 0; u < FIT_U; ++u) {
+      const long long i = b0 + tid + (long long)nt * u;
+      yv[u] = i <= a1 ? y[i] : 0.0f;
+    }
+#pragma unroll
+    for (int u = 0; u < FIT_U; ++u) {
+      const long long i = b0 + tid + (long long)nt * u;
+      if (i > a1) continue;
+      const float tf = ta.at(i);
+      if (tf >= ts32 && tf <= te32) f(tf, yv[u] - peak);
+    }
+  }
+}
+
 __global__ void curve_fit_kernel(const float* __restrict__ ybase, const int64_t* __restrict__ off,
                                  const int64_t* __restrict__ len, FitParams P, double* __restrict__ fit_out,
                                  double* __restrict__ cross_out, int pre_searched) {
@@ -444,7 +479,6 @@ __global__ void curve_fit_kernel(const float* __restrict__ ybase, const int64_t*
   const long long n = len[c];
   const float* y = ybase + off[c];
   const int tid = threadIdx.x, nt = blockDim.x;
-  const double qnan = __longlong_as_double(0x7ff8000000000000ll);
   const TimeAxis ta{P.t_axis, P.t_mul, P.t_div};
   double* fo = fit_out + (int64_t)c * P.nranges * IRA_FIT_DOUBLES;
   double* co = cross_out ? cross_out + (int64_t)c * P.ncross : nullptr;
@@ -476,11 +510,7 @@ __global__ void curve_fit_kernel(const float* __restrict__ ybase, const int64_t*
     if (usable && ((double)peak - P.floor_db) < P.min_peak_above_floor) usable = false;
   }
   if (!usable) {
-    if (tid == 0) {
-      for (int r = 0; r < P.nranges; ++r)
-        for (int k = 0; k < IRA_FIT_DOUBLES; ++k) fo[r * IRA_FIT_DOUBLES + k] = (k == 0) ? 0.0 : qnan;
-      for (int j = 0; j < P.ncross && co; ++j) co[j] = qnan;
-    }
+    if (tid == 0) write_all_refused(P, fo, co);
     return;
   }
 
@@ -488,10 +518,7 @@ __global__ void curve_fit_kernel(const float* __restrict__ ybase, const int64_t*
   // Fixed-size, fully unrolled arrays so they stay in registers (runtime-indexed arrays go to scratch).
   const int ntargets = 2 * P.nranges + P.ncross;
   if (tid < FIT_MAX_TARGETS) {
-    double tv = 0.0;
-    if (tid < 2 * P.nranges) tv = (tid & 1) ? P.lo[tid >> 1] : P.hi[tid >> 1];
-    else if (tid < ntargets) tv = P.cross[tid - 2 * P.nranges];
-    sh.tgt[tid] = tv;
+    sh.tgt[tid] = fit_target(P, tid);
     long long start = n;
     if (pre_searched && tid < ntargets) {
       // indices found by crossing_search_kernel (slots alias the head of this curve's output record)
@@ -536,107 +563,59 @@ __global__ void curve_fit_kernel(const float* __restrict__ ybase, const int64_t*
     __syncthreads();
     if (all_found) break;
   }
-  const double* targets_d = sh.tgt;
+  // crossing time of target k from its first-crossing index; the curve is read only where the interpolation needs it
+  const auto cross_at = [&](int k) {
+    const long long idx = sh.idx[k];
+    const bool inside = idx > 0 && idx < n;
+    return crossing_time(idx, n, inside ? y[idx - 1] - peak : 0.0f, inside ? y[idx] - peak : 0.0f, sh.tgt[k], ta);
+  };
 
-  if (co && tid == 0) {
-    for (int j = 0; j < P.ncross; ++j) {
-      const int k = 2 * P.nranges + j;
-      co[j] = crossing_time_from_index(y, peak, sh.idx[k], n, targets_d[k], ta);
-    }
-  }
+  if (co && tid == 0)
+    for (int j = 0; j < P.ncross; ++j) co[j] = cross_at(2 * P.nranges + j);
 
   // ---- per range: crossing times -> float32 mask -> two-pass regression ----------------------------------
   for (int r = 0; r < P.nranges; ++r) {
     const long long i_hi = sh.idx[2 * r], i_lo = sh.idx[2 * r + 1];
-    const double ts = crossing_time_from_index(y, peak, i_hi, n, targets_d[2 * r], ta);
-    const double te = crossing_time_from_index(y, peak, i_lo, n, targets_d[2 * r + 1], ta);
+    const double ts = cross_at(2 * r);
+    const double te = cross_at(2 * r + 1);
     double* o = fo + r * IRA_FIT_DOUBLES;
     bool ok = !(isnan(ts) || isnan(te) || te <= ts);
     if (!ok) {
-      if (tid == 0) { o[0] = 0.0; o[1] = ts; o[2] = te; for (int k = 3; k < IRA_FIT_DOUBLES; ++k) o[k] = qnan; }
+      if (tid == 0) write_refused(o, ts, te, qnan());
       continue;
     }
     const float ts32 = (float)ts, te32 = (float)te;
     long long a0 = i_hi - 2; if (a0 < 0) a0 = 0;
     long long a1 = i_lo + 2; if (a1 > n - 1) a1 = n - 1;
     // pass 1: count, sum t, sum y
-    // The three passes read y in batches of FIT_U independent loads per thread: with one load per iteration a single
-    // workgroup streaming a long range is bound by one memory latency per element.
     double cnt = 0.0, st = 0.0, sy = 0.0;
-    for (long long b0 = a0; b0 <= a1; b0 += (long long)nt * FIT_U) {
-      float yv[FIT_U];
-#pragma unroll
-      for (int u = 0; u < FIT_U; ++u) {
-        const long long i = b0 + tid + (long long)nt * u;
-        yv[u] = i <= a1 ? y[i] : 0.0f;
-      }
-#pragma unroll
-      for (int u = 0; u < FIT_U; ++u) {
-        const long long i = b0 + tid + (long long)nt * u;
-        if (i > a1) continue;
-        const float tf = ta.at(i);
-        if (tf >= ts32 && tf <= te32) { cnt += 1.0; st += (double)tf; sy += (double)(yv[u] - peak); }
-      }
-    }
+    masked_sweep(y, peak, a0, a1, ts32, te32, ta, [&](float tf, float yr) {
+      cnt += 1.0; st += (double)tf; sy += (double)yr;
+    });
     block_sum3(cnt, st, sy, sh);
     const long long npts = (long long)cnt;
     if (npts < P.min_points) {
-      if (tid == 0) { o[0] = 0.0; o[1] = ts; o[2] = te; for (int k = 3; k < 7; ++k) o[k] = qnan; o[7] = (double)npts; }
+      if (tid == 0) write_refused(o, ts, te, (double)npts);
       continue;
     }
     const double tm = st / cnt, ym = sy / cnt;
     // pass 2: centred second moments
     double stt = 0.0, sty = 0.0, syy = 0.0;
-    for (long long b0 = a0; b0 <= a1; b0 += (long long)nt * FIT_U) {
-      float yv[FIT_U];
-#pragma unroll
-      for (int u = 0; u < FIT_U; ++u) {
-        const long long i = b0 + tid + (long long)nt * u;
-        yv[u] = i <= a1 ? y[i] : 0.0f;
-      }
-#pragma unroll
-      for (int u = 0; u < FIT_U; ++u) {
-        const long long i = b0 + tid + (long long)nt * u;
-        if (i > a1) continue;
-        const float tf = ta.at(i);
-        if (tf >= ts32 && tf <= te32) {
-          const double dt = (double)tf - tm, dy = (double)(yv[u] - peak) - ym;
-          stt += dt * dt; sty += dt * dy; syy += dy * dy;
-        }
-      }
-    }
+    masked_sweep(y, peak, a0, a1, ts32, te32, ta, [&](float tf, float yr) {
+      const double dt = (double)tf - tm, dy = (double)yr - ym;
+      stt += dt * dt; sty += dt * dy; syy += dy * dy;
+    });
     block_sum3(stt, sty, syy, sh);
     const double slope = sty / stt;
     const double icpt = ym - slope * tm;
     // pass 3: residual sum of squares against the fitted line (decay.py:244-247)
     double sres = 0.0, d1 = 0.0, d2 = 0.0;
-    for (long long b0 = a0; b0 <= a1; b0 += (long long)nt * FIT_U) {
-      float yv[FIT_U];
-#pragma unroll
-      for (int u = 0; u < FIT_U; ++u) {
-        const long long i = b0 + tid + (long long)nt * u;
-        yv[u] = i <= a1 ? y[i] : 0.0f;
-      }
-#pragma unroll
-      for (int u = 0; u < FIT_U; ++u) {
-        const long long i = b0 + tid + (long long)nt * u;
-        if (i > a1) continue;
-        const float tf = ta.at(i);
-        if (tf >= ts32 && tf <= te32) {
-          const double e = (double)(yv[u] - peak) - (slope * (double)tf + icpt);
-          sres += e * e;
-        }
-      }
-    }
+    masked_sweep(y, peak, a0, a1, ts32, te32, ta, [&](float tf, float yr) {
+      const double e = (double)yr - (slope * (double)tf + icpt);
+      sres += e * e;
+    });
     block_sum3(sres, d1, d2, sh);
-    if (tid == 0) {
-      const bool neg = slope < 0.0;  // also false for NaN (stt == 0)
-      o[0] = neg ? 1.0 : 0.0;
-      o[1] = ts; o[2] = te; o[3] = slope; o[4] = icpt;
-      o[5] = syy > 0.0 ? 1.0 - sres / syy : 0.0;
-      o[6] = -60.0 / slope;
-      o[7] = (double)npts;
-    }
+    if (tid == 0) write_line(o, ts, te, slope, icpt, syy > 0.0 ? 1.0 - sres / syy : 0.0, npts);
   }
 }
 
@@ -678,20 +657,7 @@ struct EdcFitRange {
   int ok, pad;
 };
 
-struct EdcFitShared {
-  EdcShared scan;
-  ira::LogTabEntry ltab[ira::LOGTAB_N];
-  double carry[EDC_MAX_TILES + 1];
-  float db[EDC_TILE];
-  EdcFitRange rng[FIT_MAX_RANGES];
-  double part[EDC_WAVES][FIT_MAX_RANGES][6];
-  unsigned long long found[FIT_MAX_TARGETS];      // local index of the first crossing in the tile in LDS
-  long long idx[FIT_MAX_TARGETS];                 // first index with edc_db <= target; n = never
-  float y_at[FIT_MAX_TARGETS], y_prev[FIT_MAX_TARGETS];
-  float tgt32[FIT_MAX_TARGETS];
-  int first_tile[FIT_MAX_TARGETS];                // tile (counted from the END) where the search starts; -1 = never
-};
-
+// what phase B needs in LDS; phase A's struct starts with it
 struct EdcMomentsShared {
   EdcShared scan;
   ira::LogTabEntry ltab[ira::LOGTAB_N];
@@ -700,44 +666,26 @@ struct EdcMomentsShared {
   double part[EDC_WAVES][FIT_MAX_RANGES][6];
 };
 
-// Samples of tile j (counted from the end of the segment) into registers: issued one tile AHEAD of its use (phase B walks
-// consecutive tiles), so that the memory round trip of tile j-1 runs under the scan and the logarithms of tile j.
-__device__ __forceinline__ void edc_tile_fetch(const float* __restrict__ src, long long n, int j, float xv[EDC_PER_THREAD]) {
-  const long long hi = n - (long long)j * EDC_TILE;
-  const long long lo = hi - EDC_TILE > 0 ? hi - EDC_TILE : 0;
-  tile_load(src + lo, (int)(hi - lo), xv);
-}
+struct EdcFitShared : EdcMomentsShared {
+  double carry[EDC_MAX_TILES + 1];
+  unsigned long long found[FIT_MAX_TARGETS];      // local index of the first crossing in the tile in LDS
+  long long idx[FIT_MAX_TARGETS];                 // first index with edc_db <= target; n = never
+  float y_at[FIT_MAX_TARGETS], y_prev[FIT_MAX_TARGETS];
+  float tgt32[FIT_MAX_TARGETS];
+  int first_tile[FIT_MAX_TARGETS];                // tile (counted from the END) where the search starts; -1 = never
+};
 
-// dB curve of tile j from its pre-fetched samples into sh.db, in time order.  Same scan, same carry and same conversion
-// as edc_emit_kernel.  The caller alternates `parity` between consecutive calls.
-__device__ __forceinline__ void edc_tile_to_lds(const float xv[EDC_PER_THREAD], long long n, int j, double eps,
-                                                double floor_db, double norm, double lnorm, bool fast, int parity,
-                                                EdcFitShared& sh, long long& tstart, int& tlen) {
-  const long long hi = n - (long long)j * EDC_TILE;
-  tstart = hi - EDC_TILE > 0 ? hi - EDC_TILE : 0;
-  tlen = (int)(hi - tstart);
+// The float32 dB curve of a tile of tlen valid samples from its pre-fetched samples into db[0 .. tlen), in time order;
+// carry = the energy behind the tile.  The caller alternates `parity` between consecutive calls.
+__device__ __forceinline__ void edc_tile_to_lds(const float xv[EDC_PER_THREAD], int tlen, double carry, const EdcDb& D,
+                                                EdcShared& scan, int parity, float* db) {
   double s[EDC_PER_THREAD];
-  tile_suffix_scan(xv, sh.scan, parity, s);
-  const double carry = sh.carry[j];
+  tile_suffix_scan(xv, scan, parity, s);
   const int i0 = EDC_PER_THREAD * threadIdx.x;
 #pragma unroll
   for (int r = 0; r < EDC_PER_THREAD; ++r)
-    if (i0 + r < tlen) sh.db[i0 + r] = (float)np_max(edc_db64(s[r] + carry, eps, norm, lnorm, fast, sh.ltab), floor_db);
+    if (i0 + r < tlen) db[i0 + r] = D.db32(s[r] + carry);
   __syncthreads();
-}
-
-__device__ __forceinline__ double crossing_time_from_values(long long idx, long long n, float y_prev, float y_at,
-                                                            double target, const TimeAxis& ta) {
-  if (idx >= n) return __longlong_as_double(0x7ff8000000000000ll);  // NaN = "no crossing"
-  if (idx == 0) return (double)ta.at(0);
-  const double t0 = (double)ta.at(idx - 1);
-  const double t1 = (double)ta.at(idx);
-  const double y0 = (double)y_prev;
-  const double y1 = (double)y_at;
-  if (y1 == y0) return t1;
-  double frac = (target - y0) / (y1 - y0);
-  if (frac == frac) frac = fmin(fmax(frac, 0.0), 1.0);       // numpy.clip keeps NaN (a NaN neighbour: decay.py:192-196)
-  return t0 + frac * (t1 - t0);
 }
 
 __global__ __launch_bounds__(EDC_THREADS) __attribute__((amdgpu_waves_per_eu(4, 4))) void edc_fit_kernel(
@@ -749,16 +697,13 @@ __global__ __launch_bounds__(EDC_THREADS) __attribute__((amdgpu_waves_per_eu(4, 
   const int seg = blockIdx.x;
   const long long n = len[seg];
   const int tid = threadIdx.x;
-  const double qnan = __longlong_as_double(0x7ff8000000000000ll);
   const TimeAxis ta{nullptr, P.t_mul, P.t_div};
   double* fo = fit_out ? fit_out + (int64_t)seg * P.nranges * IRA_FIT_DOUBLES : nullptr;
   double* co = cross_out ? cross_out + (int64_t)seg * P.ncross : nullptr;
   const int ntargets = 2 * P.nranges + P.ncross;
   if (n <= 0) {
     if (tid == 0) {
-      for (int r = 0; r < P.nranges; ++r)
-        for (int k = 0; k < IRA_FIT_DOUBLES; ++k) fo[r * IRA_FIT_DOUBLES + k] = (k == 0) ? 0.0 : qnan;
-      for (int j = 0; j < P.ncross && co; ++j) co[j] = qnan;
+      write_all_refused(P, fo, co);
       scratch[(int64_t)seg * IRA_EDC_SCRATCH_DOUBLES + 3] = -1.0;      // nchunks < 0: records already written
     }
     return;
@@ -766,19 +711,15 @@ __global__ __launch_bounds__(EDC_THREADS) __attribute__((amdgpu_waves_per_eu(4, 
   ira::build_log_table(sh.ltab, tid);
   const float* src = x + off[seg];
   double* sc = scratch + (int64_t)seg * IRA_EDC_SCRATCH_DOUBLES;
-  const int ntiles = (int)((n + EDC_TILE - 1) / EDC_TILE);
-  for (int j = tid; j < ntiles; j += EDC_THREADS) sh.carry[j] = sc[IRA_EDC_SCRATCH_DOUBLES / 2 + j];
-  const double norm = sc[IRA_EDC_SCRATCH_DOUBLES - 1];
-  const bool fast = norm > 1e-300 && norm < 1e300;
+  const int ntiles = (int)edc_tile_count(n);
+  for (int j = tid; j < ntiles; j += EDC_THREADS) sh.carry[j] = sc[EDC_CARRY + j];
+  const double norm = sc[EDC_NORM];
   __syncthreads();
-  const double lnorm = fast ? ira::log2_table(norm, sh.ltab) : 0.0;
+  const EdcDb D(norm, eps, floor_db, sh.ltab);
 
   // ---- where each target's search starts -------------------------------------------------------------------------
   if (tid < FIT_MAX_TARGETS) {
-    double tv = 0.0;
-    if (tid < 2 * P.nranges) tv = (tid & 1) ? P.lo[tid >> 1] : P.hi[tid >> 1];
-    else if (tid < ntargets) tv = P.cross[tid - 2 * P.nranges];
-    const float t32 = (float)tv;
+    const float t32 = (float)fit_target(P, tid);
     sh.tgt32[tid] = t32;
     sh.idx[tid] = n;
     sh.y_at[tid] = 0.0f; sh.y_prev[tid] = 0.0f;
@@ -824,8 +765,9 @@ __global__ __launch_bounds__(EDC_THREADS) __attribute__((amdgpu_waves_per_eu(4, 
     long long tstart; int tlen;
     {
       float xv[EDC_PER_THREAD];
-      edc_tile_fetch(src, n, j, xv);
-      edc_tile_to_lds(xv, n, j, eps, floor_db, norm, lnorm, fast, parity, sh, tstart, tlen);
+      const EdcSpan sp = tile_load(src, n, j, xv);
+      tstart = sp.lo; tlen = sp.len();
+      edc_tile_to_lds(xv, tlen, sh.carry[j], D, sh.scan, parity, sh.db);
     }
     parity ^= 1;
     if (tid < FIT_MAX_TARGETS) sh.found[tid] = 0xffffffffffffffffull;
@@ -848,30 +790,29 @@ __global__ __launch_bounds__(EDC_THREADS) __attribute__((amdgpu_waves_per_eu(4, 
       else if (tstart > 0) {
         // the sample before this tile is the LAST sample of tile j+1: its suffix sum is its own energy + carry[j+1]
         const double v = (double)src[tstart - 1];
-        sh.y_prev[tid] = (float)np_max(edc_db64(v * v + sh.carry[j + 1], eps, norm, lnorm, fast, sh.ltab), floor_db);
+        sh.y_prev[tid] = D.db32(v * v + sh.carry[j + 1]);
       }
     }
     __syncthreads();
   }
 
-  if (co && tid == 0) {
-    for (int jc = 0; jc < P.ncross; ++jc) {
-      const int k = 2 * P.nranges + jc;
-      co[jc] = crossing_time_from_values(sh.idx[k], n, sh.y_prev[k], sh.y_at[k], P.cross[jc], ta);
-    }
-  }
+  // crossing time of target k from what phase A left in LDS
+  const auto cross_at = [&](int k) { return crossing_time(sh.idx[k], n, sh.y_prev[k], sh.y_at[k], fit_target(P, k), ta); };
+
+  if (co && tid == 0)
+    for (int jc = 0; jc < P.ncross; ++jc) co[jc] = cross_at(2 * P.nranges + jc);
   if (P.nranges == 0) return;
 
   // ---- the ranges: crossing times, index window, mid-range shifts; and the chunking of phase B --------------------------
   if (tid < FIT_MAX_RANGES) {
     EdcFitRange g;
-    g.ok = 0; g.ts = g.te = qnan; g.tmid = g.ymid = 0.0; g.ts32 = g.te32 = 0.0f; g.a0 = 0; g.a1 = -1; g.pad = 0;
+    g.ok = 0; g.ts = g.te = qnan(); g.tmid = g.ymid = 0.0; g.ts32 = g.te32 = 0.0f; g.a0 = 0; g.a1 = -1; g.pad = 0;
     double flat_y = 0.0;
     if (tid < P.nranges) {
       const int r = tid;
       const long long i_hi = sh.idx[2 * r], i_lo = sh.idx[2 * r + 1];
-      g.ts = crossing_time_from_values(i_hi, n, sh.y_prev[2 * r], sh.y_at[2 * r], P.hi[r], ta);
-      g.te = crossing_time_from_values(i_lo, n, sh.y_prev[2 * r + 1], sh.y_at[2 * r + 1], P.lo[r], ta);
+      g.ts = cross_at(2 * r);
+      g.te = cross_at(2 * r + 1);
       g.ok = !(isnan(g.ts) || isnan(g.te) || g.te <= g.ts) ? 1 : 0;
       if (g.ok) {
         g.a0 = i_hi - 2 > 0 ? i_hi - 2 : 0;
@@ -928,7 +869,7 @@ __global__ __launch_bounds__(EDC_THREADS) void edc_moments_kernel(
   const double h0 = sc[0], h1 = sc[1], h2 = sc[2], h3 = sc[3];
   const long long n = len[seg];
   const long long so = off[seg];
-  const double nrm = sc[IRA_EDC_SCRATCH_DOUBLES - 1];
+  const double nrm = sc[EDC_NORM];
   const int nchunks = (int)ira::uniform(h3);
   if (c >= nchunks) return;
   const int j_first = (int)ira::uniform(h0), j_last = (int)ira::uniform(h1), K = (int)ira::uniform(h2);
@@ -947,35 +888,26 @@ __global__ __launch_bounds__(EDC_THREADS) void edc_moments_kernel(
   const float* src = x + ira::uniform(so);
   const long long nn = ira::uniform(n);
   const double norm = ira::uniform(nrm);
-  const bool fast = norm > 1e-300 && norm < 1e300;
   __syncthreads();
-  const double lnorm = fast ? ira::log2_table(norm, sh.ltab) : 0.0;
+  const EdcDb D(norm, eps, floor_db, sh.ltab);
   const int j_hi = j_first - c * K;
   const int j_lo = j_hi - K + 1 > j_last ? j_hi - K + 1 : j_last;
   const int lane = tid & 63, wave = tid >> 6;
   int parity = 0;
   float xv[EDC_PER_THREAD];
-  edc_tile_fetch(src, nn, j_hi, xv);
-  double carry = sc[IRA_EDC_SCRATCH_DOUBLES / 2 + j_hi];
+  tile_load(src, nn, j_hi, xv);
+  double carry = sc[EDC_CARRY + j_hi];
   for (int j = j_hi; j >= j_lo; --j) {
     float xn[EDC_PER_THREAD];
     double carry_next = 0.0;
     if (j > j_lo) {                                            // next tile's samples and carry: in flight during this tile's work
-      edc_tile_fetch(src, nn, j - 1, xn);
-      carry_next = sc[IRA_EDC_SCRATCH_DOUBLES / 2 + j - 1];
+      tile_load(src, nn, j - 1, xn);
+      carry_next = sc[EDC_CARRY + j - 1];
     }
-    const long long hi = nn - (long long)j * EDC_TILE;
-    const long long tstart = hi - EDC_TILE > 0 ? hi - EDC_TILE : 0;
-    const int tlen = (int)(hi - tstart);
-    {
-      double sfx[EDC_PER_THREAD];
-      tile_suffix_scan(xv, sh.scan, parity, sfx);
-      const int i0 = EDC_PER_THREAD * tid;
-#pragma unroll
-      for (int r = 0; r < EDC_PER_THREAD; ++r)
-        if (i0 + r < tlen) sh.db[i0 + r] = (float)np_max(edc_db64(sfx[r] + carry, eps, norm, lnorm, fast, sh.ltab), floor_db);
-    }
-    __syncthreads();
+    const EdcSpan sp = edc_tile_span(nn, j);
+    const long long tstart = sp.lo;
+    const int tlen = sp.len();
+    edc_tile_to_lds(xv, tlen, carry, D, sh.scan, parity, sh.db);
     parity ^= 1;
     for (int r = 0; r < P.nranges; ++r) {
       const EdcFitRange g = sh.rng[r];                       // uniform
@@ -1017,7 +949,6 @@ __global__ __launch_bounds__(256) void edc_line_kernel(int nseg, FitParams P, co
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= nseg * P.nranges) return;
   const int seg = t / P.nranges, r = t - seg * P.nranges;
-  const double qnan = __longlong_as_double(0x7ff8000000000000ll);
   const double* sc = scratch + (int64_t)seg * IRA_EDC_SCRATCH_DOUBLES;
   const int nchunks = (int)sc[3];
   if (nchunks < 0) return;                                   // empty segment: written by edc_fit_kernel
@@ -1026,7 +957,7 @@ __global__ __launch_bounds__(256) void edc_line_kernel(int nseg, FitParams P, co
   const bool ok = rec[6] != 0.0;
   double* o = fit_out + ((int64_t)seg * P.nranges + r) * IRA_FIT_DOUBLES;
   if (!ok) {
-    o[0] = 0.0; o[1] = ts; o[2] = te; for (int k = 3; k < IRA_FIT_DOUBLES; ++k) o[k] = qnan;
+    write_refused(o, ts, te, qnan());
     return;
   }
   double cnt = 0.0, su = 0.0, sw = 0.0, suu = 0.0, suw = 0.0, sww = 0.0;
@@ -1036,11 +967,11 @@ __global__ __launch_bounds__(256) void edc_line_kernel(int nseg, FitParams P, co
   }
   const long long npts = (long long)cnt;
   if (npts < P.min_points) {
-    o[0] = 0.0; o[1] = ts; o[2] = te; for (int k = 3; k < 7; ++k) o[k] = qnan; o[7] = (double)npts;
+    write_refused(o, ts, te, (double)npts);
     return;
   }
-  if (rec[6] == 2.0 && npts >= 2) {                          // every value in the mask is rec[7]: a flat line, refused
-    o[0] = 0.0; o[1] = ts; o[2] = te; o[3] = 0.0; o[4] = rec[7]; o[5] = 0.0; o[6] = -INFINITY; o[7] = (double)npts;
+  if (rec[6] == 2.0 && npts >= 2) {                          // every value in the mask is rec[7]: the line of slope exactly
+    write_line(o, ts, te, 0.0, rec[7], 0.0, npts);           // 0 through it, which is not a falling one (rt60 = -inf)
     return;
   }
   // centred moments from the shifted sums (shift = mid-range: the subtractions lose nothing that matters in f64)
@@ -1050,12 +981,41 @@ __global__ __launch_bounds__(256) void edc_line_kernel(int nseg, FitParams P, co
   const double tm = tmid + um, ym = ymid + wm;
   const double icpt = ym - slope * tm;
   const double sres = syy - slope * sty;                     // residual sum of squares of the least-squares line
-  const bool neg = slope < 0.0;                              // also false for NaN (stt == 0)
-  o[0] = neg ? 1.0 : 0.0;
-  o[1] = ts; o[2] = te; o[3] = slope; o[4] = icpt;
-  o[5] = syy > 0.0 ? 1.0 - fmax(sres, 0.0) / syy : 0.0;
-  o[6] = -60.0 / slope;
-  o[7] = (double)npts;
+  write_line(o, ts, te, slope, icpt, syy > 0.0 ? 1.0 - fmax(sres, 0.0) / syy : 0.0, npts);
+}
+
+// ---- host side -----------------------------------------------------------------------------------------------------------------
+// The fit request of ira_curve_fits and ira_edc_fits, checked and packed; the caller adds what only it has.
+int32_t fit_params(const double* ranges_hi_lo, int32_t nranges, int32_t min_points, const double* cross_targets,
+                   int32_t ncross, const double* fit_out_dev, const double* cross_out_dev, FitParams* P) {
+  if (nranges < 0 || nranges > FIT_MAX_RANGES || ncross < 0 || ncross > FIT_MAX_CROSS) return IRA_E_SIZE;
+  if (nranges > 0) { IRA_CHECK_PTR(ranges_hi_lo); IRA_CHECK_PTR(fit_out_dev); }
+  if (ncross > 0) { IRA_CHECK_PTR(cross_targets); IRA_CHECK_PTR(cross_out_dev); }
+  *P = FitParams{};
+  for (int r = 0; r < nranges; ++r) { P->hi[r] = ranges_hi_lo[2 * r]; P->lo[r] = ranges_hi_lo[2 * r + 1]; }
+  for (int j = 0; j < ncross; ++j) P->cross[j] = cross_targets[j];
+  P->nranges = nranges; P->ncross = ncross; P->min_points = min_points;
+  return IRA_OK;
+}
+
+// The size checks of the EDC entry points, then tile totals -> carries and normaliser in the segments' scratch.  With
+// tile_part, a segment whose part_off is >= 0 takes all totals but its first tile's from the producer's partials.
+int32_t edc_launch_carries(const float* x_dev, const int64_t* off_dev, const int64_t* len_dev, int32_t nseg, int64_t max_len,
+                           double eps, double* scratch_dev, const double* tile_part_dev, const int64_t* part_off_dev,
+                           const int32_t* part_wgs_dev, const int32_t* part_tiles_dev, hipStream_t st, int* ntiles_out) {
+  if (max_len <= 0 || max_len > (int64_t)EDC_MAX_TILES * EDC_TILE) return IRA_E_SIZE;
+  if (nseg > 65535) return IRA_E_SIZE;
+  if (tile_part_dev != nullptr && (part_off_dev == nullptr || part_wgs_dev == nullptr || part_tiles_dev == nullptr))
+    return IRA_E_NULL;
+  const int ntiles = (int)edc_tile_count(max_len);
+  edc_sums_kernel<<<dim3(ntiles, nseg), EDC_THREADS, 0, st>>>(x_dev, off_dev, len_dev, scratch_dev,
+                                                              tile_part_dev ? part_off_dev : nullptr);
+  if (tile_part_dev != nullptr && ntiles > 1)
+    edc_tiles_from_parts_kernel<<<dim3((ntiles - 1 + 127) / 128, nseg), 128, 0, st>>>(len_dev, tile_part_dev, part_off_dev,
+                                                                                      part_wgs_dev, part_tiles_dev, scratch_dev);
+  edc_carry_kernel<<<nseg, IRA_WAVE, 0, st>>>(len_dev, nseg, eps, scratch_dev);
+  *ntiles_out = ntiles;
+  return IRA_OK;
 }
 
 }  // namespace
@@ -1085,12 +1045,11 @@ extern "C" int32_t ira_edc_db(const float* x_dev, const int64_t* off_dev, const 
   if (edc_db_dev == nullptr && edc_db64_dev == nullptr) return IRA_E_NULL;
   IRA_CHECK_PTR(edc_off_dev); IRA_CHECK_PTR(scratch_dev);
   if (nseg <= 0) return nseg == 0 ? IRA_OK : IRA_E_SIZE;
-  if (max_len <= 0 || max_len > (int64_t)EDC_MAX_TILES * EDC_TILE) return IRA_E_SIZE;
   hipStream_t st = (hipStream_t)stream;
-  const int ntiles = (int)((max_len + EDC_TILE - 1) / EDC_TILE);
-  if (nseg > 65535) return IRA_E_SIZE;
-  edc_sums_kernel<<<dim3(ntiles, nseg), EDC_THREADS, 0, st>>>(x_dev, off_dev, len_dev, scratch_dev, nullptr);
-  edc_carry_kernel<<<nseg, IRA_WAVE, 0, st>>>(len_dev, nseg, eps, scratch_dev);
+  int ntiles;
+  const int32_t rc = edc_launch_carries(x_dev, off_dev, len_dev, nseg, max_len, eps, scratch_dev, nullptr, nullptr, nullptr,
+                                        nullptr, st, &ntiles);
+  if (rc != IRA_OK) return rc;
   edc_emit_kernel<<<dim3(ntiles, nseg), EDC_THREADS, 0, st>>>(x_dev, off_dev, len_dev, eps, floor_db, edc_db_dev,
                                                               edc_db64_dev, edc_off_dev, scratch_dev);
   IRA_RETURN_LAUNCH();
@@ -1104,29 +1063,18 @@ extern "C" int32_t ira_edc_fits(const float* x_dev, const int64_t* off_dev, cons
                                 double* scratch_dev, const double* tile_part_dev, const int64_t* part_off_dev,
                                 const int32_t* part_wgs_dev, const int32_t* part_tiles_dev, void* stream) {
   IRA_CHECK_PTR(x_dev); IRA_CHECK_PTR(off_dev); IRA_CHECK_PTR(len_dev); IRA_CHECK_PTR(scratch_dev);
-  if (nranges < 0 || nranges > FIT_MAX_RANGES || ncross < 0 || ncross > FIT_MAX_CROSS) return IRA_E_SIZE;
-  if (nranges > 0) { IRA_CHECK_PTR(ranges_hi_lo); IRA_CHECK_PTR(fit_out_dev); }
-  if (ncross > 0) { IRA_CHECK_PTR(cross_targets); IRA_CHECK_PTR(cross_out_dev); }
+  FitParams P;
+  int32_t rc = fit_params(ranges_hi_lo, nranges, min_points, cross_targets, ncross, fit_out_dev, cross_out_dev, &P);
+  if (rc != IRA_OK) return rc;
+  P.floor_db = floor_db; P.t_mul = t_mul; P.t_div = t_div;
   if (edc_db_dev != nullptr) IRA_CHECK_PTR(edc_off_dev);
   if (nseg <= 0) return nseg == 0 ? IRA_OK : IRA_E_SIZE;
-  if (max_len <= 0 || max_len > (int64_t)EDC_MAX_TILES * EDC_TILE) return IRA_E_SIZE;
-  if (nseg > 65535) return IRA_E_SIZE;
-  FitParams P{};
-  for (int r = 0; r < nranges; ++r) { P.hi[r] = ranges_hi_lo[2 * r]; P.lo[r] = ranges_hi_lo[2 * r + 1]; }
-  for (int j = 0; j < ncross; ++j) P.cross[j] = cross_targets[j];
-  P.nranges = nranges; P.ncross = ncross; P.min_points = min_points; P.rel_to_peak = 0;
-  P.floor_db = floor_db; P.min_peak_above_floor = 0.0; P.t_mul = t_mul; P.t_div = t_div; P.t_axis = nullptr;
   hipStream_t st = (hipStream_t)stream;
-  const int ntiles = (int)((max_len + EDC_TILE - 1) / EDC_TILE);
   IRA_TRY_HIP(allow_lds(edc_fit_kernel, sizeof(EdcFitShared)));
-  if (tile_part_dev != nullptr && (part_off_dev == nullptr || part_wgs_dev == nullptr || part_tiles_dev == nullptr))
-    return IRA_E_NULL;
-  edc_sums_kernel<<<dim3(ntiles, nseg), EDC_THREADS, 0, st>>>(x_dev, off_dev, len_dev, scratch_dev,
-                                                              tile_part_dev ? part_off_dev : nullptr);
-  if (tile_part_dev != nullptr && ntiles > 1)
-    edc_tiles_from_parts_kernel<<<dim3((ntiles - 1 + 127) / 128, nseg), 128, 0, st>>>(len_dev, tile_part_dev, part_off_dev,
-                                                                                      part_wgs_dev, part_tiles_dev, scratch_dev);
-  edc_carry_kernel<<<nseg, IRA_WAVE, 0, st>>>(len_dev, nseg, eps, scratch_dev);
+  int ntiles;
+  rc = edc_launch_carries(x_dev, off_dev, len_dev, nseg, max_len, eps, scratch_dev, tile_part_dev, part_off_dev, part_wgs_dev,
+                          part_tiles_dev, st, &ntiles);
+  if (rc != IRA_OK) return rc;
   if (nranges + ncross > 0)
     edc_fit_kernel<<<nseg, EDC_THREADS, sizeof(EdcFitShared), st>>>(x_dev, off_dev, len_dev, eps, floor_db, P,
                                                                      scratch_dev, fit_out_dev,
@@ -1165,15 +1113,12 @@ extern "C" int32_t ira_curve_fits(const float* y_dev, const int64_t* off_dev, co
                                   double min_peak_above_floor, double* fit_out_dev, double* cross_out_dev,
                                   void* stream) {
   IRA_CHECK_PTR(y_dev); IRA_CHECK_PTR(off_dev); IRA_CHECK_PTR(len_dev);
-  if (nranges < 0 || nranges > FIT_MAX_RANGES || ncross < 0 || ncross > FIT_MAX_CROSS) return IRA_E_SIZE;
-  if (nranges > 0) { IRA_CHECK_PTR(ranges_hi_lo); IRA_CHECK_PTR(fit_out_dev); }
-  if (ncross > 0) { IRA_CHECK_PTR(cross_targets); IRA_CHECK_PTR(cross_out_dev); }
+  FitParams P;
+  const int32_t rc = fit_params(ranges_hi_lo, nranges, min_points, cross_targets, ncross, fit_out_dev, cross_out_dev, &P);
+  if (rc != IRA_OK) return rc;
+  P.rel_to_peak = rel_to_peak; P.floor_db = floor_db; P.min_peak_above_floor = min_peak_above_floor;
+  P.t_mul = t_mul; P.t_div = t_div; P.t_axis = t_axis_dev;
   if (ncurves <= 0) return ncurves == 0 ? IRA_OK : IRA_E_SIZE;
-  FitParams P{};
-  for (int r = 0; r < nranges; ++r) { P.hi[r] = ranges_hi_lo[2 * r]; P.lo[r] = ranges_hi_lo[2 * r + 1]; }
-  for (int j = 0; j < ncross; ++j) P.cross[j] = cross_targets[j];
-  P.nranges = nranges; P.ncross = ncross; P.min_points = min_points; P.rel_to_peak = rel_to_peak;
-  P.floor_db = floor_db; P.min_peak_above_floor = min_peak_above_floor; P.t_mul = t_mul; P.t_div = t_div; P.t_axis = t_axis_dev;
   const int threads = max_len <= 2048 ? 64 : (max_len <= 32768 ? 256 : 1024);
   hipStream_t st = (hipStream_t)stream;
   const int ntargets = 2 * nranges + ncross;

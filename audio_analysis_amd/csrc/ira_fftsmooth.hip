@@ -15,6 +15,7 @@
 #include <type_traits>
 
 #include "ira_bandmask.h"
+#include "ira_edc_tile.h"
 #include "ira_fft_reg.h"
 
 namespace {
@@ -664,22 +665,21 @@ __global__ __launch_bounds__(SM_THREADS, ((MODE == SM_SIGNAL || !HALF) ? 6 : 5))
 
 // ---- pass 2: N2-point transforms for C adjacent k1.  grid (N1 / C, jobs) --------------------------------------------------
 // ---- tile energies of the band signals, from the second pass's own output stage (round 5) ---------------------------------
-// The Schroeder EDC of a band signal (ira_edc.hip) starts from the energies of its 4096-sample tiles, counted from the END
-// of the signal; edc_sums_kernel got them by reading every band signal again right after this pass had written it (config
+// The Schroeder EDC of a band signal (ira_edc.hip) starts from the energies of its tiles (ira_edc_tile.h: 4096 samples, counted
+// from the END of the signal); edc_sums_kernel got them by reading every band signal again right after this pass had written it (config
 // 3: 12.8 GB per step).  The values are all here: after the in-LDS transform the tile `r` holds the workgroup's N2 x C
 // outputs k = k1 + N1 k2 (a comb through the whole signal), and what was stored is float32(re / n), float32(-im / n).
 // Thread j sums the squares of the workgroup's samples that fall into EDC tile j, in a fixed order (columns, then k2
 // ascending), in float64 (the square of a float32 value is exact) -> part[((job * 2 + signal) * wgs + bx) * ntile + j];
 // edc_tiles_from_parts_kernel adds the wgs partials of a tile in a fixed order.  No atomics: the totals do not depend on
 // scheduling.  (A half_out job writes ONE signal of 2 n samples, 2 k and 2 k + 1 from re and im: both go to signal 0.)
-constexpr int SM_EDC_TILE = 4096;                           // = EDC_TILE of ira_edc.hip (checked by ira_edc_fits's caller contract)
 __device__ __forceinline__ void band_tile_partials(const SmoothPlan& P, const SJobs& J, const cd* r, int LD, int k1_0, int e,
                                                    unsigned bx, bool second, int tid) {
   const long long n = P.n;
   const int C = P.c2, N1 = P.n1, N2 = P.n2;
   const bool half = J.half_out != 0;
   const long long len = half ? 2 * n : n;
-  const int ntile = (int)((len + SM_EDC_TILE - 1) / SM_EDC_TILE), wgs = N1 / C;
+  const int ntile = (int)ira::edc_tile_count(len), wgs = N1 / C;
   const double sc = 1.0 / (double)n;
   // layout [job][signal][workgroup][tile]: a workgroup's partials of one signal are contiguous (first version: [tile][workgroup],
   // 2 x 118 scattered 8-byte stores per workgroup -- the pass lost more than ira_edc_fits gained)
@@ -691,7 +691,8 @@ __device__ __forceinline__ void band_tile_partials(const SmoothPlan& P, const SJ
     const int j = idx / CS, cs = idx - j * CS;
     double s1 = 0.0, s2 = 0.0;
     if (j < ntile) {
-      const long long hi = len - (long long)j * SM_EDC_TILE, lo = hi > SM_EDC_TILE ? hi - SM_EDC_TILE : 0;   // samples [lo, hi)
+      const ira::EdcSpan sp = ira::edc_tile_span(len, j);
+      const long long lo = sp.lo, hi = sp.hi;
       const long long klo = half ? lo / 2 : lo, khi = half ? hi / 2 : hi;      // (len and the tile length are even: so are lo, hi)
       for (int c = cs; c < C; c += CS) {
         const long long k1 = k1_0 + c, a = klo - k1, b = khi - k1;
@@ -1283,7 +1284,7 @@ extern "C" int32_t ira_band_tile_layout(int32_t n, int32_t half_out, int32_t* ti
   const int32_t rc = make_smooth_plan(n, dummy, dummy, dummy, &P);
   if (rc != IRA_OK) return rc;
   const long long len = half_out ? 2ll * n : (long long)n;
-  *tiles = (int32_t)((len + SM_EDC_TILE - 1) / SM_EDC_TILE);
+  *tiles = (int32_t)ira::edc_tile_count(len);
   *workgroups = P.n1 / P.c2;
   return IRA_OK;
 }

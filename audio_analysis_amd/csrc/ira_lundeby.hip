@@ -14,7 +14,7 @@
 // which sample in which order is a function of B (and, for the partial tail block, of its length) alone, never of the
 // address.  No atomics; every reduction tree is fixed.
 #include "ira_common.h"
-#include "ira_log.h"
+#include "ira_edc_tile.h"
 #include "ira_lundeby_rows.h"
 #include "ira_reduce.h"
 
@@ -371,7 +371,7 @@ __global__ __launch_bounds__(LB_THREADS) void lundeby_estimate_kernel(
 // ------------------------------------------------------------------------------------------------
 // Pass 2: the curve.  A wave takes a block of its chunk: lane l owns the block's samples [l per, (l + 1) per),
 // per = ceil(B / 64), and forms their suffix sums from its last sample down; the lanes' totals meet in a suffix scan towards
-// the higher lanes.  edc[i] = (suffix inside the block) + base[j]; then the dB chain of ira_edc_db (same table logarithm):
+// the higher lanes.  edc[i] = (suffix inside the block) + base[j]; then the dB chain of ira_edc_db (ira::EdcDb):
 // max(., eps) / max(edc[0], eps) -> 10 log10 -> max(., floor_db) -> float32.  The float32 values replace the samples in LDS
 // and leave with 16-byte stores.  A band row may be written over the signal it is read from: a workgroup has read its chunk
 // before it writes it, and no other workgroup touches that chunk.
@@ -400,9 +400,7 @@ __global__ __launch_bounds__(LB_THREADS) void edc_truncated_kernel(
   __syncthreads();
   const double* base = suffix + ira::uniform(blk_off[row]);
   const double first = ira::uniform(rec_in[(int64_t)row * IRA_LUNDEBY_DOUBLES + 14]);
-  const double norm = ira::np_max(first, eps);
-  const bool fast = norm > 1e-300 && norm < 1e300;
-  const double lnorm = fast ? ira::log2_table(norm, ltab) : 0.0;
+  const ira::EdcDb D(ira::np_max(first, eps), eps, floor_db, ltab);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int per = (r.B + IRA_WAVE - 1) / IRA_WAVE;
   for (int jl = wave; jl < nj; jl += LB_WAVES) {
@@ -423,11 +421,7 @@ __global__ __launch_bounds__(LB_THREADS) void edc_truncated_kernel(
       run = d * d + run;
       // edc[0] sums the same energies in another order (the estimate's E[0] + base[0]): a later sample may come out one
       // float64 rounding above it, and is held to it, so that no sample of the curve lies above 0 dB
-      const double sum = (c0 + b0 + i == 0) ? first : fmin(run + bj, first);
-      const double v = ira::np_max(sum, eps);
-      const double db = (fast && v > 1e-300 && v < 1e300) ? 3.0102999566398120 * (ira::log2_table(v, ltab) - lnorm)
-                                                           : 10.0 * log10(v / norm);
-      stage[b0 + i] = (float)ira::np_max(db, floor_db);
+      stage[b0 + i] = D.db32((c0 + b0 + i == 0) ? first : fmin(run + bj, first));
     }
   }
   __syncthreads();

@@ -113,6 +113,8 @@ __device__ __forceinline__ T wave_suffix(T v, int lane, T& excl) {
 
 // numpy.maximum: a NaN operand gives NaN (fmax would drop it)
 __device__ __forceinline__ double np_max(double a, double b) { return (a != a) ? a : fmax(a, b); }
+// the quiet NaN numpy.nan is
+__device__ __forceinline__ double qnan() { return __longlong_as_double(0x7ff8000000000000ll); }
 
 // float32 <-> a key whose unsigned order is the float order (no value maps to key 0)
 __device__ __forceinline__ uint32_t float_key(float f) {
