@@ -106,6 +106,9 @@ def run_bundle_metrics(bundle_root: str | Path, settings=None, use_mono_downmix_
     fixed-width records to rank 0.  Returns ([(tap name, channel name), ...], records (channels x METRICS_WIDTH)) on
     rank 0 and (None, None) elsewhere.  No PNGs, no Markdown: this is the data-parallel axis of the reference's
     serial loop (bundle.py:56-67) without its per-file plotting.
+    The report runs at the bundle's own rate, meta.json's sample_rate_hz (48 000 when the key is missing): with
+    settings=None that rate is put into FullReportSettings, and settings whose sample_rate_hz is another rate raise
+    ValueError (the ingest already refuses taps whose header disagrees with meta.json).
     """
     import numpy as np
 
@@ -136,10 +139,17 @@ def run_bundle_metrics(bundle_root: str | Path, settings=None, use_mono_downmix_
         lo, hi = _dist.shard_files(len(taps), rank, world)
         mine = taps[lo:hi]
     eng = get_engine()
-    fr = FullReport(eng, settings or FullReportSettings())
+    rate = int(meta.get("sample_rate_hz", 48_000) or 48_000)
+    # the bundle's own rate drives every block (segment bounds, band tables, frequency axes), not only the ingest's header
+    # check: without settings the report runs at meta.json's rate, and settings for another rate are refused
+    if settings is None:
+        settings = FullReportSettings(sample_rate_hz=rate)
+    elif int(settings.sample_rate_hz) != rate:
+        raise ValueError(f"The report settings are for {int(settings.sample_rate_hz)} Hz, but the bundle's meta.json says "
+                         f"{rate} Hz.")
+    fr = FullReport(eng, settings)
     rows, labels = [], []
     step = max(1, int(taps_per_step))
-    rate = int(meta.get("sample_rate_hz", 48_000) or 48_000)
     groups = [mine[a : a + step] for a in range(0, len(mine), step)]
 
     # diagnostics (IRA_BUNDLE_TIMING=1): host seconds per phase of the loop; nothing is timed when the switch is off

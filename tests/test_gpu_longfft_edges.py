@@ -438,6 +438,13 @@ def edge_bands(n):
            ("bandpass wide", _rec(3.0, (1.5, 3.5), (0.3 * nb, 0.45 * nb)))]
     if n % 2 == 0:
         out.append(("one bin Nyquist", _one_bin(n // 2)))
+    # coinciding edges (x0 == x1: the ramp is the step f >= x1, and every bin takes the full formula -- what the band
+    # tables give for the top band of a 44.1 kHz recording, tests/test_gpu_rates.py): the low-pass side of a band-pass at
+    # the last bin and at an interior one, a high-pass, and a low-pass with both edges at bin 0 (nothing passes)
+    out += [("coincide lowpass edges at the last bin", _rec(3.0, (1.5, 3.5), (float(nb - 1), float(nb - 1)))),
+            ("coincide lowpass edges inside", _rec(3.0, (1.5, 3.5), (float(nb // 3), float(nb // 3)))),
+            ("coincide highpass edges", _rec(2.0, hp=(float(nb // 3), float(nb // 3)))),
+            ("coincide lowpass edges at bin 0", _rec(1.0, lp=(0.0, 0.0)))]
     return out
 
 
@@ -519,6 +526,15 @@ def test_band_inverse_edges(n):
     assert np.count_nonzero(masks[0]) == 1 and masks[0][0] == 1.0
     assert np.count_nonzero(masks[1]) == 1 and masks[1][1] == 1.0
     assert masks[3][-1] == 1.0 and 0.0 < masks[3][-3] < 1.0 and np.all(masks[4] == 1.0)
+    by_name = {name: m for (name, _), m in zip(bands, masks)}
+    k = nb // 3
+    m = by_name["coincide lowpass edges at the last bin"]
+    assert m[-1] == 0.0 and np.all(m[4:-1] == 1.0) and np.all(m[:2] == 0.0)              # the step f >= x1 cuts the edge bin
+    m = by_name["coincide lowpass edges inside"]
+    assert np.all(m[k:] == 0.0) and np.all(m[4:k] == 1.0)
+    m = by_name["coincide highpass edges"]
+    assert np.all(m[:k] == 0.0) and np.all(m[k:] == 1.0)
+    assert np.all(by_name["coincide lowpass edges at bin 0"] == 0.0)
     # hand-made spectra: one non-zero bin each, at 0, 1, a band's first / centre / last bin and the last bin
     hand = []
     for k in sorted({0, 1, 2, nb // 2, int(0.45 * nb), nb - 1}):
