@@ -129,6 +129,12 @@ EQUALISE_PROTOTYPES = {
     "ira_eq_taper": (i32, [vp, vp, vp, i32, i32, i32, vp, vp]),
 }
 
+# name -> (restype, argtypes) of the symbols include/ira_edr.h declares (the third header of the same library).
+EDR_PROTOTYPES = {
+    "ira_edr_power": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, i32, vp, vp]),
+    "ira_edr_integrate": (i32, [vp, vp, vp, vp, vp, i32, i32, f64, f64, vp, vp, vp, vp]),
+}
+
 
 class IraError(RuntimeError):
     pass
@@ -170,7 +176,7 @@ def load():
     have = int(version())
     if have != ABI_VERSION:
         raise IraError(f"{path} has ABI version {have}, this package binds version {ABI_VERSION}: {rebuild}")
-    for name, (res, args) in [*PROTOTYPES.items(), *EQUALISE_PROTOTYPES.items()]:
+    for name, (res, args) in [*PROTOTYPES.items(), *EQUALISE_PROTOTYPES.items(), *EDR_PROTOTYPES.items()]:
         try:
             fn = getattr(lib, name)
         except AttributeError:

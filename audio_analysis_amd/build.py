@@ -79,6 +79,9 @@ SOURCES = {
     # power sums, the pyramid's pairwise sums, the window sums and the quotients of the inversion round one operation at a
     # time: every kernel is held bit for bit to a NumPy restatement
     "ira_equalise.hip": ["-ffp-contract=off"],
+    # the row sums, the suffix sums of the backward integration and the noise subtraction round one operation at a time:
+    # the integration is held bit for bit to a NumPy restatement (the transform calls fma itself where it wants one)
+    "ira_edr.hip": ["-ffp-contract=off"],
 }
 COMMON = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function"]
 
@@ -126,7 +129,7 @@ def build_tuning(verbose: bool = True) -> Path:
 
 def build(force: bool = False, verbose: bool = False) -> Path:
     hipcc = _hipcc()
-    headers = list(CSRC.glob("*.h")) + [CSRC.parent.parent / "include" / h for h in ("ira.h", "ira_equalise.h")]
+    headers = list(CSRC.glob("*.h")) + [CSRC.parent.parent / "include" / h for h in ("ira.h", "ira_equalise.h", "ira_edr.h")]
     jobs = []
     objs = []
     for name, extra in SOURCES.items():

@@ -70,6 +70,12 @@ EQ_TILE = 1 << EQ_TILE_LOG2   # IRA_EQ_TILE
 EQ_MAX_MEMBERS = 256          # IRA_EQ_MAX_MEMBERS: channels one averaged row holds
 EQ_MAX_SMOOTHING = 48         # the narrowest smoothing, 1/48 octave
 EQ_SCRATCH_BYTES = 4 << 30    # equalise_cut: the device scratch of one sub-batch of rows stays under this
+EDR_FRAMES = 16               # IRA_EDR_FRAMES: frames per chunk of ira_edr_power and per store run of a row (include/ira_edr.h)
+EDR_BLOCK = 64                # IRA_EDR_BLOCK: frames per block of the backward sum, counted from the end
+EDR_MAX_ROWS = 256            # IRA_EDR_MAX_ROWS
+EDR_SERIAL = 16               # IRA_EDR_SERIAL: rows of up to this many bins are summed in ascending order by one thread
+EDR_DOUBLES = 4               # IRA_EDR_DOUBLES: S(0), N, max P, the first frame of that maximum
+EDR_MIN_FFT, EDR_MAX_FFT = 256, 8192
 MLS_MAX_PERIODS = 1024        # IRA_MLS_MAX_PERIODS
 MLS_TILE_LOG2 = 12            # IRA_MLS_TILE_LOG2: the tile order T of ira_mls_hadamard
 MLS_FOLD_THREADS = 256        # IRA_MLS_FOLD_THREADS
@@ -134,6 +140,16 @@ def xspec_frames(n, n_fft: int, hop: int) -> np.ndarray:
     """K = 1 + (n - n_fft) // hop frames of n samples, 0 when n < n_fft (int64, elementwise)."""
     n = np.asarray(n, dtype=np.int64)
     return np.where(n >= n_fft, 1 + (n - n_fft) // hop, 0).astype(np.int64)
+
+
+def edr_layout(frames, nrows: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+    """The two layouts of the energy decay relief for segments of `frames` frames and nrows rows -> (Tpad, p_off, c_off,
+    total doubles of P).  P(m, j) of segment s lies at p_off[s] + j * Tpad[s] + m with Tpad = ceil(T / EDR_FRAMES) *
+    EDR_FRAMES (every p_off a multiple of EDR_FRAMES: a store run of a row is 128 bytes and 128-byte aligned in a buffer
+    that is); the float32 curve L(m, j) at c_off[s] + j * T[s] + m, unpadded.  All int64."""
+    frames = np.asarray(frames, dtype=np.int64).reshape(-1)
+    tpad = -(-frames // EDR_FRAMES) * EDR_FRAMES
+    return tpad, exclusive_cumsum(tpad * int(nrows)), exclusive_cumsum(frames * int(nrows)), int(tpad.sum()) * int(nrows)
 
 
 def ned_positions(length, onset, step: int, kmax: int) -> np.ndarray:

@@ -1,7 +1,8 @@
 """
 The measure launchers of the device engine, one method per library call (or short chain of calls): ISO 3382-1 energy
 parameters and IACC, Lundeby, multi-slope fits, STI sums, harmonics, the echo criterion, echo density, reflections,
-transfer functions, FDW, burst decay, minimum phase, equalisation, MLS measurement, and the suffix-energy tables.  Each checks its
+transfer functions, the energy decay relief, FDW, burst decay, minimum phase, equalisation, MLS measurement, and the
+suffix-energy tables.  Each checks its
 tables on the host (engine_geometry holds what several share), allocates its outputs, uploads its job tables in one copy
 and enqueues the call.  MeasureLaunchers is a base class of engine.Engine, which supplies the plumbing (empty, out_view,
 job_tables, ...).
@@ -623,6 +624,81 @@ class MeasureLaunchers:
             check(self.lib.ira_xspec_finish(_ptr(partial), _ptr(d_n), npairs, max_frames, n_fft, hop, _ptr(out),
                                             self.stream), "ira_xspec_finish")
         return out
+
+    # ------------------------------------------------------------------ energy decay relief (Jot)
+    @staticmethod
+    def _edr_sizes(nseg: int, nrows: int) -> None:
+        if nseg > 65535:
+            raise ValueError("at most 65535 segments per launch")
+        if not 1 <= nrows <= EDR_MAX_ROWS:
+            raise ValueError(f"1 to {EDR_MAX_ROWS} rows, got {nrows}")
+
+    def edr_power(self, x_dev, x_off: np.ndarray, n: np.ndarray, n_fft: int, hop: int, use_hann: bool, first: np.ndarray,
+                  count: np.ndarray):
+        """Band powers of every frame (ira_edr_power).  Segment s: n[s] samples at x_off[s] of x_dev, T = 1 + (n[s] - n_fft)
+        // hop frames (none when n[s] < n_fft); row j: the rFFT bins first[j] .. first[j] + count[j] - 1 (count 0: an empty
+        row, powers 0.0).  The window is window(n_fft, use_hann, 64).  Returns (P float64 device, flat, in the layout of
+        edr_layout; frames int64 host (nseg,); p_off int64 host (nseg,))."""
+        t = self.torch
+        x_off, n = flat(x_off, np.int64), flat(n, np.int64)
+        first, count = flat(first, np.int32), flat(count, np.int32)
+        n_fft, hop = int(n_fft), int(hop)
+        nseg = same_rows("x_off and n must be (nseg,)", x_off, n)
+        nrows = same_rows("first and count must be (nrows,)", first, count)
+        self._edr_sizes(nseg, nrows)
+        if n_fft < EDR_MIN_FFT or n_fft > EDR_MAX_FFT or n_fft & (n_fft - 1):
+            raise ValueError(f"n_fft must be a power of two from {EDR_MIN_FFT} to {EDR_MAX_FFT}, got {n_fft}")
+        if not 1 <= hop <= n_fft:
+            raise ValueError(f"hop must be 1 .. n_fft, got {hop}")
+        if first.min() < 0 or count.min() < 0 or int((first.astype(np.int64) + count).max()) > n_fft // 2 + 1:
+            raise ValueError("a row's bins must lie in 0 .. n_fft / 2")
+        if nseg and (n.min() < 0 or x_off.min() < 0 or int((x_off + n).max()) > int(x_dev.numel())):
+            raise ValueError("a segment must lie inside x_dev")
+        frames = xspec_frames(n, n_fft, hop)
+        _, p_off, _, total = edr_layout(frames, nrows)
+        max_frames = int(frames.max()) if nseg else 0
+        if max_frames >= 1 << 31:
+            raise ValueError("too many frames for one launch")
+        p = self.empty(total, t.float64)
+        if nseg and max_frames:
+            win, tw = self.window(n_fft, use_hann, 64), self.twiddle(n_fft, 64)
+            d_xo, d_n, d_po, d_first, d_count = self.job_tables(x_off, n, p_off, first, count)
+            with self.tagged(f"[{n_fft}]"):
+                check(self.lib.ira_edr_power(_ptr(x_dev), _ptr(d_xo), _ptr(d_n), _ptr(d_po), nseg, max_frames, n_fft, hop,
+                                             _ptr(win), _ptr(tw), _ptr(d_first), _ptr(d_count), nrows, _ptr(p), self.stream),
+                      "ira_edr_power")
+        return p[:total], frames, p_off
+
+    def edr_integrate(self, p_dev, frames: np.ndarray, nrows: int, noise_frames: np.ndarray, eps: float, floor_db: float,
+                      with_sums: bool = False):
+        """Backward sums of the band powers along the frame axis, their records and float32 dB curves (ira_edr_integrate).
+        p_dev: P in the layout of edr_layout(frames, nrows) (what edr_power returns, or a host-made one); noise_frames[s] =
+        q, 0 <= q <= frames[s], the last frames whose mean level is subtracted (0: none).  Returns (curves float32 device,
+        flat: (nrows, T_s) at c_off[s]; c_off int64 host (nseg,); records (nseg, nrows, EDR_DOUBLES) float64 device: S(0), N,
+        max P, the first frame of that maximum; S float64 device in the layout of P, or None unless with_sums)."""
+        t = self.torch
+        frames, noise_frames = flat(frames, np.int64), flat(noise_frames, np.int64)
+        nrows = int(nrows)
+        nseg = same_rows("frames and noise_frames must be (nseg,)", frames, noise_frames)
+        self._edr_sizes(nseg, nrows)
+        eps, floor_db = float(eps), float(floor_db)
+        if not (math.isfinite(eps) and eps >= 0.0 and math.isfinite(floor_db)):
+            raise ValueError("eps must be finite and >= 0, floor_db finite")
+        if nseg and (frames.min() < 0 or frames.max() >= 1 << 31 or noise_frames.min() < 0 or np.any(noise_frames > frames)):
+            raise ValueError("frames must be 0 .. 2^31 - 1 and noise_frames 0 .. frames")
+        _, p_off, c_off, total = edr_layout(frames, nrows)
+        if total > int(p_dev.numel()):
+            raise ValueError("p_dev is smaller than the layout of frames and nrows")
+        ncurve = int(frames.sum()) * nrows
+        curves = self.empty(ncurve, t.float32)
+        rec = self.out_view(t.float64, nseg, nrows, EDR_DOUBLES)
+        sums = self.empty(total, t.float64) if with_sums else None
+        if nseg:
+            d_po, d_t, d_q, d_co = self.job_tables(p_off, frames.astype(np.int32), noise_frames.astype(np.int32), c_off)
+            check(self.lib.ira_edr_integrate(_ptr(p_dev), _ptr(d_po), _ptr(d_t), _ptr(d_q), _ptr(d_co), nseg, nrows, eps,
+                                             floor_db, _ptr(curves), _ptr(rec), _ptr(sums), self.stream),
+                  "ira_edr_integrate")
+        return curves[:ncurve], c_off, rec, (sums[:total] if with_sums else None)
 
     # ------------------------------------------------------------------ ISO 3382-1 inter-channel cross-correlation
     def xcorr_windows(self, x_dev, l_off: np.ndarray, r_off: np.ndarray, seg_len: np.ndarray, lchan_of_seg: np.ndarray,
